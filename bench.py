@@ -3,12 +3,18 @@
 synthetic polymer batches of 64 graphs, depth 3, hidden 300 (BASELINE.json metric), inputs packed
 and resident in HBM before the timed region.
 
-    python bench.py [--gpus N] [--steps K] [--warmup W]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--dump-outputs DIR] [--full]
     python -m torch.distributed.run --nproc-per-node N --master-addr 127.0.0.1 bench.py --gpus N
 
 One process per GPU.  Every rank encodes its own disjoint synthetic batches (seed = base + rank):
 the path shards as independent graphs with no data-path collective (weak scaling); the only
 collectives are the barrier and the max-over-ranks of the elapsed time.
+
+A plain run does what the headline figure needs and no more: resident inputs, W warm-up steps, the K
+timed steps, the result line.  --dump-outputs DIR also writes what the last timed step returned
+(DIR/mol_vecs.npy, float32; the inputs are seeded, so two builds compare output for output).  --full
+adds every other leg: one batch in flight, forward_many, the per-kernel roofline pass, the streamed
+workloads, the packing report, the secondary workloads and the CPU baseline.
 
 Rank 0 prints ONE JSON line (stdout).  Diagnostics go to stderr.
 """
@@ -470,6 +476,110 @@ def packing_report(a, device, t_fwd):
     return rep
 
 
+DUMP_MAX_BYTES = 64 << 20
+
+
+def dump_outputs(out_dir, rank, out):
+    """--dump-outputs: the tensor the last timed step returned (what a caller of MPNEncoder.forward gets:
+    [molecules, hidden] fp32) as out_dir/mol_vecs.npy, float32.  An output above 64 MB is cut to a fixed,
+    seeded sample of its rows (sorted), so that two runs keep the same ones."""
+    import numpy as np
+    arr = out.detach().to('cpu', torch.float32).numpy()
+    if arr.nbytes > DUMP_MAX_BYTES:
+        keep = max(1, DUMP_MAX_BYTES // max(arr[0].nbytes, 1))
+        rows = np.sort(np.random.default_rng(0).choice(arr.shape[0], size=keep, replace=False))
+        arr = arr[rows]
+    os.makedirs(out_dir, exist_ok=True)
+    name = 'mol_vecs.npy' if rank == 0 else f'mol_vecs.rank{rank}.npy'
+    np.save(os.path.join(out_dir, name), np.ascontiguousarray(arr))
+
+
+def full_report(line, a, device, world, graphs, E_avg, elapsed, total_edges, single, many_dt, many_edges, kernel_ms,
+                n_launch, streamed, trained):
+    """--full: the legs besides the headline added to the result line -- the figures main() timed (one batch
+    in flight, forward_many, the event pass of the roofline, the streamed workloads) and the legs run here
+    (packing report, secondary workloads, CPU baseline)."""
+    H = a.hidden
+    st_dt, st_edges, st_graphs, st_h2d, st_info, cap = streamed
+    tr_dt, tr_edges, tr_steps = trained
+    # dominant kernel: one message-passing layer (mpn.py:110-124), E directed bonds, hidden H.
+    # Algorithmic FLOPs 2 E H^2 (W_h) + 2 E d H (weighted in-edge sums, d = CSR entries / row);
+    # algorithmic bytes (fp32, each tensor once): read M_{t-1}, inp, W_h, CSR; write M_t.
+    g0 = graphs[0]
+    nnz = float(g0.device_graph(device, False, get_bond_fdim()).nnz_msg)
+    d_avg = nnz / max(g0.n_bonds - 1, 1)
+    flops_launch = 2.0 * E_avg * H * H + 2.0 * E_avg * d_avg * H
+    bytes_launch = 4.0 * (3 * E_avg * H + H * H + H) + 8.0 * E_avg * d_avg + 4.0 * E_avg
+    avg_launch_s = (kernel_ms / 1e3 / n_launch) if n_launch else float('nan')
+    traffic, traffic_src = pmc_traffic('mp_layer_kernel<80')
+    alone_us, alone_src = rocprof_alone('mp_layer_kernel<80')
+    achieved = flops_launch / avg_launch_s / 1e12 if n_launch else None
+    hbm = bytes_launch / avg_launch_s / 1e9 if n_launch else None
+    line['single_stream'] = ({'value': total_edges / single, 'ms_per_step': single / a.steps * 1e3,
+                              'note': 'same steps, one batch in flight (each forward waits for the previous)'}
+                             if single else None)
+    line['forward_many'] = ({'value': many_edges / many_dt, 'ms_per_step': many_dt / (a.steps // a.many * a.many) * 1e3,
+                             'batches_per_call': a.many,
+                             'note': 'one stream, MPNEncoder.forward_many (wdmpnn_forward_many): the batches of a '
+                                     'call share one grid per kernel; every batch a full B=64 forward'}
+                            if many_dt else None)
+    line['roofline'] = {'bound': 'mfma',
+                        'kernel': 'mp_layer_kernel: one message-passing layer, W_h fp16-pair GEMM + in-block CSR '
+                                  'gather + residual/activation (mpn.py:110-124)',
+                        'achieved': achieved, 'peak': FP32_MFMA_PEAK_TFLOPS, 'unit': 'TFLOP/s',
+                        'frac': achieved / FP32_MFMA_PEAK_TFLOPS if achieved else None, 'traffic': traffic,
+                        'traffic_source': traffic_src,
+                        'peak_note': 'fp32 dense MFMA peak; the kernel issues fp16 MFMAs (3 per fp32 product), whose '
+                                     f'fp32-product equivalent peak is {BF16_MFMA_PEAK_TFLOPS / 3:.0f} TFLOP/s',
+                        'avg_launch_us': avg_launch_s * 1e6, 'flops_per_launch': flops_launch,
+                        'bytes_per_launch': bytes_launch, 'hbm_gbs': hbm,
+                        'hbm_frac': hbm / HBM_PEAK_GBS if hbm else None,
+                        'launches_timed': n_launch,
+                        'in_flight': {'avg_launch_us': avg_launch_s * 1e6,
+                                      'frac': achieved / FP32_MFMA_PEAK_TFLOPS if achieved else None,
+                                      'source': f'HIP events around the layer launches, {a.streams} batches in '
+                                                'flight (a second pass of the timed loop)'},
+                        'alone': ({'avg_launch_us': alone_us,
+                                   'frac': flops_launch / (alone_us * 1e-6) / 1e12 / FP32_MFMA_PEAK_TFLOPS,
+                                   'source': alone_src + ', one batch in flight'}
+                                  if alone_us else None)}
+    line['forward'] = forward_roofline(graphs, a, elapsed / a.steps)
+    if st_dt > 0:
+        line['streamed'] = {
+            'workload': 'configs[4]: synthetic polymer graphs streamed per rank in batches of 64 (native '
+                        'generation on producer threads, compact upload, device graph build, forward; all '
+                        'inside the timed region), disjoint seeds per rank, no data-path collective',
+            'graphs': st_graphs, 'graphs_per_rank': a.stream_graphs, 'n_gpus': world,
+            'value': st_edges / st_dt, 'unit': 'edges/s', 'graphs_per_s': st_graphs / st_dt, 'seconds': st_dt,
+            'h2d_bytes_per_edge': st_h2d / st_edges, 'scaling': 'weak',
+            'producers_per_rank': [i['producers'] for i in st_info], 'producer_cap': cap,
+            'shard_seed_ranges': [list(i['seed_range']) for i in st_info]}
+    if tr_dt > 0:
+        line['streamed_training'] = {
+            'workload': 'configs[4] as DP training: MoleculeModel (depth 3, hidden 300, regression, Adam) on '
+                        'streamed polymer batches of 128 per rank, one flat fp32 gradient all-reduce per step '
+                        f'({"RCCL" if world > 1 else "none at N=1"})',
+            'steps_per_rank': tr_steps, 'n_gpus': world, 'value': tr_edges / tr_dt, 'unit': 'edges/s',
+            'ms_per_step': tr_dt / tr_steps * 1e3, 'graphs_per_s': tr_steps * 128 * world / tr_dt,
+            'scaling': 'weak'}
+    log('[bench] packing report')
+    line['packing'] = packing_report(a, device, elapsed / a.steps)
+    if world == 1 and a.kind == 'polymer' and not a.no_secondary:
+        # (after the streamed legs the host-bound QM9 loop below takes 15-19 instead of 10.3-10.9 us per
+        # forward -- four in flight, same box, round 6; run before them it recovers and the streamed leg
+        # loses 60 %: whichever workload comes second pays -- not the hardware queues (8 change nothing),
+        # cause not isolated; the order stays, the north-star streamed leg first)
+        log('[bench] secondary workloads (qm9, zinc, training step)')
+        line['secondary'] = [secondary_workload(device, 'qm9', 64, 3, 300, 200),
+                             secondary_workload(device, 'zinc', 512, 5, 512, 30),
+                             training_workload(device), atom_messages_workload(device)]
+    if not a.no_cpu and world == 1:  # the CPU leg is timed at N=1 only
+        log(f'[bench] CPU baseline (~{a.cpu_seconds:.0f} s + a one-thread sample)')
+        cpu = cpu_baseline(TrainArgs(hidden_size=H, depth=a.depth, device=torch.device('cpu')), graphs[0],
+                           a.cpu_seconds)
+        line['cpu_baseline'] = cpu
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument('--gpus', type=int, default=1)
@@ -480,6 +590,13 @@ def main():
     ap.add_argument('--hidden', type=int, default=300)
     ap.add_argument('--kind', default='polymer', choices=['polymer', 'qm9', 'zinc'])
     ap.add_argument('--n-batches', type=int, default=8, help='distinct resident batches cycled per rank')
+    ap.add_argument('--full', action='store_true',
+                    help='also run every leg besides the headline (one batch in flight, forward_many, the roofline '
+                         'pass, streamed workloads, packing report, secondary workloads, CPU baseline); the options '
+                         'below that size or skip those legs act only with --full')
+    ap.add_argument('--dump-outputs', metavar='DIR', default=None,
+                    help='after the timed steps, write what the last timed step returned as DIR/mol_vecs.npy '
+                         '(float32 [molecules, hidden]; rank r > 0 of a multi-rank run writes mol_vecs.rank<r>.npy)')
     ap.add_argument('--cpu-seconds', type=float, default=12.0)
     ap.add_argument('--no-cpu', action='store_true')
     ap.add_argument('--no-secondary', action='store_true', help='skip the QM9 / ZINC-shaped secondary workloads')
@@ -498,6 +615,8 @@ def main():
     ap.add_argument('--stream-train-graphs', type=int, default=131_072,
                     help='configs[4] as DP training: streamed graphs per rank (batches of 128); 0 = skip')
     a = ap.parse_args()
+    if a.steps < 1:
+        ap.error('--steps must be at least 1')
 
     # one process per GPU over RCCL (backend "nccl"); BENCH_BACKEND=gloo rehearses the multi-rank path
     # with several ranks on one GPU (device = local rank modulo the visible GPUs).  The process group comes
@@ -564,16 +683,20 @@ def main():
         restore()
         barrier()
         t0 = time.perf_counter()
-        for i in range(a.steps):
+        for i in range(a.steps - 1):
             step(i)
+        last_out = step(a.steps - 1)  # (kept for --dump-outputs; the earlier outputs are dropped as they return)
         restore()
         barrier()
         elapsed = time.perf_counter() - t0
         my_edges = sum(edges[i % len(edges)] for i in range(a.steps))
+        if a.dump_outputs:
+            dump_outputs(a.dump_outputs, rank, last_out)
+        del last_out
 
         # the same K steps with one batch in flight (latency-bound: each forward waits for the last)
         single = None
-        if len(streams) > 1:
+        if a.full and len(streams) > 1:
             barrier()
             t2 = time.perf_counter()
             for i in range(a.steps):
@@ -585,7 +708,7 @@ def main():
         # the same K steps as MPNEncoder.forward_many calls of a.many batches on one stream (one set of
         # launches per call; the batches' tiles share one grid)
         many_dt = None
-        if a.many > 1 and a.steps >= a.many:
+        if a.full and a.many > 1 and a.steps >= a.many:
             sets = [[graphs[(i * a.many + j) % len(graphs)] for j in range(a.many)] for i in range(len(graphs))]
             for i in range(2):
                 enc.forward_many(sets[i % len(sets)])
@@ -599,28 +722,31 @@ def main():
 
         # second pass: HIP events around the dominant launches (the message-passing layers) on the
         # stream they run on
-        L = _native.lib()
-        pairs = a.steps  # one pair per forward around its depth - 1 layer launches (WdConfig.prof_pool)
-        pool = ctypes.c_void_p()
-        _native.check(L.wdmpnn_event_pool_create(pairs, ctypes.byref(pool)), 'event pool')
-        barrier()
-        t1 = time.perf_counter()
-        for i in range(a.steps):
-            step(i, (pool.value, i))
-        restore()
-        barrier()
-        elapsed_prof = time.perf_counter() - t1
-        enc._prof = None
-        kernel_ms = ctypes.c_float()
-        n_launch = a.steps * (a.depth - 1)
-        if n_launch:  # (the span of each pair also holds the ~0.1 us gaps between the layer launches)
-            _native.check(L.wdmpnn_event_pool_elapsed_ms(pool, 0, a.steps, ctypes.byref(kernel_ms)), 'events')
-        L.wdmpnn_event_pool_destroy(pool)
+        elapsed_prof, kernel_ms, n_launch = 0.0, ctypes.c_float(), 0
+        if a.full:
+            L = _native.lib()
+            pairs = a.steps  # one pair per forward around its depth - 1 layer launches (WdConfig.prof_pool)
+            pool = ctypes.c_void_p()
+            _native.check(L.wdmpnn_event_pool_create(pairs, ctypes.byref(pool)), 'event pool')
+            barrier()
+            t1 = time.perf_counter()
+            for i in range(a.steps):
+                step(i, (pool.value, i))
+            restore()
+            barrier()
+            elapsed_prof = time.perf_counter() - t1
+            enc._prof = None
+            n_launch = a.steps * (a.depth - 1)
+            if n_launch:  # (the span of each pair also holds the ~0.1 us gaps between the layer launches)
+                _native.check(L.wdmpnn_event_pool_elapsed_ms(pool, 0, a.steps, ctypes.byref(kernel_ms)), 'events')
+            L.wdmpnn_event_pool_destroy(pool)
 
     # configs[4]: streamed graphs (generation + upload + device build + forward, all timed), then the
     # same stream as data-parallel training with one gradient all-reduce per step
     st_dt = st_edges = st_graphs = st_h2d = tr_dt = tr_edges = tr_steps = 0
     st_info = None
+    if not a.full:
+        a.stream_graphs = a.stream_train_graphs = 0
     if a.stream_graphs > 0:
         if rank == 0:
             log(f'[bench] streamed workload: {a.stream_graphs} graphs per rank')
@@ -661,19 +787,6 @@ def main():
     if rank == 0:
         H = a.hidden
         E_avg = sum(edges[i % len(edges)] for i in range(a.steps)) / a.steps
-        # dominant kernel: one message-passing layer (mpn.py:110-124), E directed bonds, hidden H.
-        # Algorithmic FLOPs 2 E H^2 (W_h) + 2 E d H (weighted in-edge sums, d = CSR entries / row);
-        # algorithmic bytes (fp32, each tensor once): read M_{t-1}, inp, W_h, CSR; write M_t.
-        g0 = graphs[0]
-        nnz = float(g0.device_graph(device, False, get_bond_fdim()).nnz_msg)
-        d_avg = nnz / max(g0.n_bonds - 1, 1)
-        flops_launch = 2.0 * E_avg * H * H + 2.0 * E_avg * d_avg * H
-        bytes_launch = 4.0 * (3 * E_avg * H + H * H + H) + 8.0 * E_avg * d_avg + 4.0 * E_avg
-        avg_launch_s = (kernel_ms.value / 1e3 / n_launch) if n_launch else float('nan')
-        traffic, traffic_src = pmc_traffic('mp_layer_kernel<80')
-        alone_us, alone_src = rocprof_alone('mp_layer_kernel<80')
-        achieved = flops_launch / avg_launch_s / 1e12 if n_launch else None
-        hbm = bytes_launch / avg_launch_s / 1e9 if n_launch else None
         line = {
             'metric': 'edges/sec MPN forward, batch=64 polymer graphs, depth=3 hidden=300',
             'value': total_edges / elapsed,
@@ -701,73 +814,14 @@ def main():
                        'streams': a.streams,
                        'in_flight': f'{a.streams} independent batches in flight per GPU (round-robin over '
                                     f'{a.streams} HIP streams); every step is a full B={a.batch} forward'},
-            'single_stream': ({'value': total_edges / single, 'ms_per_step': single / a.steps * 1e3,
-                               'note': 'same steps, one batch in flight (each forward waits for the previous)'}
-                              if single else None),
-            'forward_many': ({'value': many_edges / many_dt, 'ms_per_step': many_dt / (a.steps // a.many * a.many) * 1e3,
-                              'batches_per_call': a.many,
-                              'note': 'one stream, MPNEncoder.forward_many (wdmpnn_forward_many): the batches of a '
-                                      'call share one grid per kernel; every batch a full B=64 forward'}
-                             if many_dt else None),
-            'roofline': {'bound': 'mfma',
-                         'kernel': 'mp_layer_kernel: one message-passing layer, W_h fp16-pair GEMM + in-block CSR '
-                                   'gather + residual/activation (mpn.py:110-124)',
-                         'achieved': achieved, 'peak': FP32_MFMA_PEAK_TFLOPS, 'unit': 'TFLOP/s',
-                         'frac': achieved / FP32_MFMA_PEAK_TFLOPS if achieved else None, 'traffic': traffic,
-                         'traffic_source': traffic_src,
-                         'peak_note': 'fp32 dense MFMA peak; the kernel issues fp16 MFMAs (3 per fp32 product), whose '
-                                      f'fp32-product equivalent peak is {BF16_MFMA_PEAK_TFLOPS / 3:.0f} TFLOP/s',
-                         'avg_launch_us': avg_launch_s * 1e6, 'flops_per_launch': flops_launch,
-                         'bytes_per_launch': bytes_launch, 'hbm_gbs': hbm,
-                         'hbm_frac': hbm / HBM_PEAK_GBS if hbm else None,
-                         'launches_timed': n_launch,
-                         'in_flight': {'avg_launch_us': avg_launch_s * 1e6,
-                                       'frac': achieved / FP32_MFMA_PEAK_TFLOPS if achieved else None,
-                                       'source': f'HIP events around the layer launches, {a.streams} batches in '
-                                                 'flight (a second pass of the timed loop)'},
-                         'alone': ({'avg_launch_us': alone_us,
-                                    'frac': flops_launch / (alone_us * 1e-6) / 1e12 / FP32_MFMA_PEAK_TFLOPS,
-                                    'source': alone_src + ', one batch in flight'}
-                                   if alone_us else None)},
             'host_cpus': {'pinned': PINNED_CPUS, 'usable': _usable_cores(1)[0]},
         }
-        line['forward'] = forward_roofline(graphs, a, elapsed / a.steps)
-        if st_dt > 0:
-            line['streamed'] = {
-                'workload': 'configs[4]: synthetic polymer graphs streamed per rank in batches of 64 (native '
-                            'generation on producer threads, compact upload, device graph build, forward; all '
-                            'inside the timed region), disjoint seeds per rank, no data-path collective',
-                'graphs': st_graphs, 'graphs_per_rank': a.stream_graphs, 'n_gpus': world,
-                'value': st_edges / st_dt, 'unit': 'edges/s', 'graphs_per_s': st_graphs / st_dt, 'seconds': st_dt,
-                'h2d_bytes_per_edge': st_h2d / st_edges, 'scaling': 'weak',
-                'producers_per_rank': [i['producers'] for i in st_info], 'producer_cap': cap,
-                'shard_seed_ranges': [list(i['seed_range']) for i in st_info]}
-        if tr_dt > 0:
-            line['streamed_training'] = {
-                'workload': 'configs[4] as DP training: MoleculeModel (depth 3, hidden 300, regression, Adam) on '
-                            'streamed polymer batches of 128 per rank, one flat fp32 gradient all-reduce per step '
-                            f'({"RCCL" if world > 1 else "none at N=1"})',
-                'steps_per_rank': tr_steps, 'n_gpus': world, 'value': tr_edges / tr_dt, 'unit': 'edges/s',
-                'ms_per_step': tr_dt / tr_steps * 1e3, 'graphs_per_s': tr_steps * 128 * world / tr_dt,
-                'scaling': 'weak'}
-        log('[bench] packing report')
-        line['packing'] = packing_report(a, device, elapsed / a.steps)
-        if world == 1 and a.kind == 'polymer' and not a.no_secondary:
-            # (after the streamed legs the host-bound QM9 loop below takes 15-19 instead of 10.3-10.9 us per
-            # forward -- four in flight, same box, round 6; run before them it recovers and the streamed leg
-            # loses 60 %: whichever workload comes second pays -- not the hardware queues (8 change nothing),
-            # cause not isolated; the order stays, the north-star streamed leg first)
-            log('[bench] secondary workloads (qm9, zinc, training step)')
-            line['secondary'] = [secondary_workload(device, 'qm9', 64, 3, 300, 200),
-                                 secondary_workload(device, 'zinc', 512, 5, 512, 30),
-                                 training_workload(device), atom_messages_workload(device)]
-        if not a.no_cpu and world == 1:  # the CPU leg is timed at N=1 only
-            log(f'[bench] CPU baseline (~{a.cpu_seconds:.0f} s + a one-thread sample)')
-            cpu = cpu_baseline(TrainArgs(hidden_size=H, depth=a.depth, device=torch.device('cpu')), graphs[0],
-                               a.cpu_seconds)
-            line['cpu_baseline'] = cpu
-        log(f'timed {a.steps} steps: {elapsed * 1e3:.2f} ms ({elapsed / a.steps * 1e6:.1f} us/step); with events '
-            f'{elapsed_prof / a.steps * 1e6:.1f} us/step')
+        log(f'timed {a.steps} steps: {elapsed * 1e3:.2f} ms ({elapsed / a.steps * 1e6:.1f} us/step)')
+        if a.full:
+            log(f'with events {elapsed_prof / a.steps * 1e6:.1f} us/step')
+            full_report(line, a, device, world, graphs, E_avg, elapsed, total_edges, single, many_dt, many_edges,
+                        kernel_ms.value, n_launch, (st_dt, st_edges, st_graphs, st_h2d, st_info, cap),
+                        (tr_dt, tr_edges, tr_steps))
         print(json.dumps(line), flush=True)
     if world > 1:
         dist.barrier()

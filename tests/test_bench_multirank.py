@@ -28,7 +28,7 @@ def test_bench_four_ranks_gloo_on_one_gpu():
     per_rank = 1280
     cmd = [sys.executable, '-m', 'torch.distributed.run', '--nnodes=1', '--nproc-per-node', '4',
            '--master-addr', '127.0.0.1', '--master-port', str(_free_port()), 'bench.py', '--gpus', '4',
-           '--steps', '5', '--warmup', '1', '--n-batches', '2', '--no-cpu', '--no-secondary',
+           '--steps', '5', '--warmup', '1', '--n-batches', '2', '--full', '--no-cpu', '--no-secondary',
            '--stream-graphs', str(per_rank), '--stream-train-graphs', '512']
     env = dict(os.environ, BENCH_BACKEND='gloo', MASTER_ADDR='127.0.0.1', OMP_NUM_THREADS='4')
     r = subprocess.run(cmd, cwd=ROOT, env=env, capture_output=True, text=True, timeout=280)

@@ -7,6 +7,6 @@ mkdir -p $D
 rc=0; timeout -k 10 900 python -u -m pytest -v --timeout 120 --timeout-method thread -m gpu tests/ > $D/pytest_gpu.log 2>&1 || rc=$?
 if [ $rc -ne 0 ] && [ $rc -ne 1 ]; then exit $rc; fi
 timeout -k 10 300 python -u -c "import __graft_entry__ as g; g.smoke(); print('smoke ok')" > $D/smoke.log 2>&1
-{ echo '$ python3 bench.py --gpus 1 --steps 20 --warmup 5'; timeout -k 10 400 python3 bench.py --gpus 1 --steps 20 --warmup 5; } > $D/bench_driver_cmd.log 2>&1
-{ echo '$ python3 bench.py --gpus 1 --steps 20 --warmup 5 --cpus 2 --no-cpu'; timeout -k 10 400 python3 bench.py --gpus 1 --steps 20 --warmup 5 --cpus 2 --no-cpu; } > $D/bench_cpus2.log 2>&1
+{ echo '$ python3 bench.py --gpus 1 --steps 20 --warmup 5 --full'; timeout -k 10 400 python3 bench.py --gpus 1 --steps 20 --warmup 5 --full; } > $D/bench_driver_cmd.log 2>&1
+{ echo '$ python3 bench.py --gpus 1 --steps 20 --warmup 5 --full --cpus 2 --no-cpu'; timeout -k 10 400 python3 bench.py --gpus 1 --steps 20 --warmup 5 --full --cpus 2 --no-cpu; } > $D/bench_cpus2.log 2>&1
 exit $rc

@@ -7,7 +7,7 @@ mkdir -p $D
 rc=0; timeout -k 10 900 python -u -m pytest -v --timeout 120 --timeout-method thread -m gpu tests/ > $D/pytest_gpu.log 2>&1 || rc=$?
 if [ $rc -ne 0 ] && [ $rc -ne 1 ]; then exit $rc; fi
 timeout -k 10 300 python3 -c "import __graft_entry__ as g; g.smoke()" > $D/smoke.log 2>&1
-timeout -k 10 300 python3 bench.py --gpus 1 --steps 20 --warmup 5 > $D/bench.log 2>&1
+timeout -k 10 300 python3 bench.py --gpus 1 --steps 20 --warmup 5 --full > $D/bench.log 2>&1
 timeout -k 10 300 rocprofv3 --kernel-trace --stats --output-format csv -d $D/prof -o run -- python3 bench.py --steps 200 --warmup 20 --no-cpu --no-secondary --streams 1 --many 0 --stream-graphs 0 --stream-train-graphs 0 > $D/prof.log 2>&1
 python3 tools/kstats.py $D/prof/run_kernel_stats.csv 8 > $D/kstats.txt
 exit $rc

@@ -6,7 +6,7 @@ mkdir -p gpurun_out
 for round in ${ROUNDS:-1 2}; do
   for v in "$@"; do
     export WDMPNN_LIB=$PWD/exp/libwdmpnn_$v.so
-    timeout -k 10 200 python bench.py --steps 20 --warmup 5 --no-cpu --no-secondary --many 0 --stream-graphs 300000 \
+    timeout -k 10 200 python bench.py --steps 20 --warmup 5 --full --no-cpu --no-secondary --many 0 --stream-graphs 300000 \
       --stream-train-graphs 16384 $SAB_ARGS > gpurun_out/sab_$v${SAB_TAG}.log 2>&1 || exit $?
     python - "$v" "$SAB_TAG" <<'PY'
 import json,sys
