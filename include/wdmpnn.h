@@ -44,7 +44,7 @@
 extern "C" {
 #endif
 
-#define WDMPNN_ABI_VERSION 11
+#define WDMPNN_ABI_VERSION 12
 #define WDMPNN_ELL_WIDTH 8
 
 enum WdActivation {     /* nn_utils.py:70-99 get_activation_function */
@@ -386,15 +386,24 @@ int wdmpnn_adam_step(const WdAdamTensor *tensors, int32_t n, const WdAdamHyper *
 int wdmpnn_adam_step_repack(const WdAdamTensor *tensors, int32_t n, const WdAdamHyper *h, const WdGraph *g,
                             const WdParams *p, const WdConfig *c, void *packed, size_t packed_bytes, void *stream);
 
-/* The training step's FFN head + masked MSE loss and their gradients in two launches (model.py:57-121
- * with ffn_num_layers = 2 and no dropout, train.py:55-74 with MSELoss): replaces the ~25 small torch ops
- * (and their host time) of ffn(emb), loss_func(preds, targets) * weights, .sum() / mask.sum() and their
- * autograd backward.  Row-major fp32 device arrays; w = target weight * data weight * mask per entry. */
+/* The training step's FFN head + masked loss and their gradients in two launches (model.py:57-121
+ * with ffn_num_layers = 2 and no dropout, train.py:55-74 with MSELoss, BCEWithLogitsLoss or per-task
+ * CrossEntropyLoss): replaces the ~25 small torch ops (and their host time) of ffn(emb),
+ * loss_func(preds, targets) * weights, .sum() / mask.sum() and their autograd backward.  Row-major fp32
+ * device arrays; w = target weight * data weight * mask per entry.
+ * Multiclass (loss_kind 2, ABI 12): the T outputs are tasks = T / n_classes groups of n_classes logits
+ * (model.py:189-190's reshape), the table holds one target per TASK -- the class index as a float -- and
+ * one weight per task: [B][ld_table] with ld_table >= 2 * tasks.  Per task, with m = max_c s_c and
+ * lse = m + log(sum_c exp(s_c - m)): loss += w (lse - s_y), dout[c] = w (exp(s_c - lse) - [c == y]) / n
+ * (the max-subtracted form: finite for any finite logits).  The class index is only compared, never used
+ * as an address: an index outside [0, n_classes) gives a wrong number, not a fault.  Requires
+ * n_classes >= 2 and T % n_classes == 0 (WD_ERR_SHAPE otherwise); kinds 0 and 1 require n_classes == 1.
+ * T <= 64 outputs in every kind (WD_ERR_UNSUPPORTED beyond). */
 typedef struct WdHead {
     const float *x; int32_t ld_x;          /* encoder output [B][ld_x], first F columns used        */
-    int32_t B, F, Hf, T;                   /* rows, input width, hidden width, outputs (tasks)      */
+    int32_t B, F, Hf, T;                   /* rows, input width, hidden width, FFN outputs (rows of W2) */
     const float *W1, *b1, *W2, *b2;        /* nn.Linear(F, Hf), nn.Linear(Hf, T) (biases may be NULL) */
-    const float *table; int32_t ld_table;  /* [B][ld_table]: targets [T], then weights w [T]        */
+    const float *table; int32_t ld_table;  /* [B][ld_table]: targets [T / n_classes], then weights w */
     float inv_n;                           /* 1 / mask.sum()                                        */
     int32_t act;                           /* WdActivation of the FFN (not PReLU)                   */
     float *a, *dh, *dout, *lossrow;        /* scratch [B][Hf], [B][Hf], [B][T], [B]                 */
@@ -403,9 +412,27 @@ typedef struct WdHead {
     float *loss;                           /* [1]                                                   */
     int32_t loss_kind;                     /* 0: MSELoss (regression), 1: BCEWithLogitsLoss         */
                                            /* (classification: the FFN's logits, train.py:55-74 with */
-                                           /* utils.py get_loss_func; sigmoid only at eval)           */
+                                           /* utils.py get_loss_func; sigmoid only at eval),          */
+                                           /* 2: CrossEntropyLoss per task (multiclass)               */
+    int32_t n_classes;                     /* classes per task: 1 for kinds 0 and 1, >= 2 for kind 2 */
 } WdHead;
 int wdmpnn_head_mse(const WdHead *h, void *stream);
+/* The same FFN at prediction time (model.py:152-194 in eval mode) in two launches: out = W2 act(W1 x +
+ * b1) + b2 followed by out_kind 0: nothing (regression), 1: sigmoid (classification, model.py:186-188),
+ * 2: softmax over each group of n_classes consecutive outputs (multiclass, model.py:189-192;
+ * max-subtracted).  Same size limits, activations and argument checks as wdmpnn_head_mse (n_classes == 1
+ * for kinds 0 and 1; n_classes >= 2 dividing T for kind 2).  B == 0 is a no-op. */
+typedef struct WdHeadPredict {
+    const float *x; int32_t ld_x;          /* encoder output [B][ld_x], first F columns used        */
+    int32_t B, F, Hf, T;                   /* rows, input width, hidden width, FFN outputs          */
+    const float *W1, *b1, *W2, *b2;        /* nn.Linear(F, Hf), nn.Linear(Hf, T) (biases may be NULL) */
+    int32_t act;                           /* WdActivation of the FFN (not PReLU)                   */
+    float *a;                              /* scratch [B][Hf]                                       */
+    float *out;                            /* [B][T]                                                */
+    int32_t out_kind;                      /* 0 identity, 1 sigmoid, 2 softmax per class group      */
+    int32_t n_classes;                     /* 1 for kinds 0 and 1, >= 2 for kind 2                  */
+} WdHeadPredict;
+int wdmpnn_head_predict(const WdHeadPredict *h, void *stream);
 /* p_i[0 .. n_i) *= *s (device scalar) for k <= 8 buffers: the head's gradients times the loss's
  * incoming gradient in one launch. */
 int wdmpnn_scale(float *const *p, const int64_t *n, int32_t k, const float *s, void *stream);

@@ -21,7 +21,7 @@ LIB_PATH = os.environ.get('WDMPNN_LIB', os.path.join(HERE, 'libwdmpnn.so'))
 ACTIVATIONS = {'ReLU': 0, 'LeakyReLU': 1, 'PReLU': 2, 'tanh': 3, 'SELU': 4, 'ELU': 5}
 ACT_IDENTITY = 6
 AGGREGATIONS = {'mean': 0, 'sum': 1, 'norm': 2}
-ABI_VERSION = 11
+ABI_VERSION = 12
 GRAPH_LEAN = 1  # WDMPNN_GRAPH_LEAN
 GRAPH_NO_PLANES = 2  # WDMPNN_GRAPH_NO_PLANES
 ERR_UNSUPPORTED = -1003  # WD_ERR_UNSUPPORTED
@@ -35,7 +35,7 @@ EXPORTED_SYMBOLS = ('wdmpnn_abi_version', 'wdmpnn_last_error', 'wdmpnn_workspace
                     'wdmpnn_saved_layout', 'wdmpnn_graph_bytes', 'wdmpnn_build_graph', 'wdmpnn_adam_step', 'wdmpnn_head_mse', 'wdmpnn_scale', 'wdmpnn_build_graph_ex',
                     'wdmpnn_forward_many', 'wdmpnn_feed_slot_bytes', 'wdmpnn_feed_create', 'wdmpnn_feed_next',
                     'wdmpnn_feed_release', 'wdmpnn_feed_forward_workspace_bytes', 'wdmpnn_feed_forward',
-                    'wdmpnn_feed_destroy', 'wdmpnn_adam_step_repack', 'wdmpnn_self_check')
+                    'wdmpnn_feed_destroy', 'wdmpnn_adam_step_repack', 'wdmpnn_self_check', 'wdmpnn_head_predict')
 
 
 class WdCsr(Structure):
@@ -114,7 +114,13 @@ class WdHead(Structure):
                 ('table', c_void_p), ('ld_table', c_int32), ('inv_n', c_float), ('act', c_int32),
                 ('a', c_void_p), ('dh', c_void_p), ('dout', c_void_p), ('lossrow', c_void_p), ('dx', c_void_p),
                 ('dW1', c_void_p), ('db1', c_void_p), ('dW2', c_void_p), ('db2', c_void_p), ('loss', c_void_p),
-                ('loss_kind', c_int32)]
+                ('loss_kind', c_int32), ('n_classes', c_int32)]
+
+
+class WdHeadPredict(Structure):
+    _fields_ = [('x', c_void_p), ('ld_x', c_int32), ('B', c_int32), ('F', c_int32), ('Hf', c_int32), ('T', c_int32),
+                ('W1', c_void_p), ('b1', c_void_p), ('W2', c_void_p), ('b2', c_void_p), ('act', c_int32),
+                ('a', c_void_p), ('out', c_void_p), ('out_kind', c_int32), ('n_classes', c_int32)]
 
 
 class NativeError(RuntimeError):
@@ -160,6 +166,7 @@ def lib() -> ctypes.CDLL:
                                              c_int32, c_void_p, c_int32, c_void_p]
     L.wdmpnn_build_graph_ex.argtypes = [POINTER(WdCompact), c_void_p, c_size_t, POINTER(WdGraph), c_int32, c_void_p]
     L.wdmpnn_head_mse.argtypes = [POINTER(WdHead), c_void_p]
+    L.wdmpnn_head_predict.argtypes = [POINTER(WdHeadPredict), c_void_p]
     L.wdmpnn_forward_many.argtypes = [c_int32, POINTER(WdGraph), POINTER(WdParams), POINTER(WdConfig),
                                       POINTER(c_void_p), POINTER(c_size_t), POINTER(c_void_p), c_void_p]
     L.wdmpnn_feed_slot_bytes.argtypes = [c_int32, c_int32, c_int32, c_int32, POINTER(c_size_t), POINTER(c_size_t)]
@@ -185,7 +192,7 @@ def lib() -> ctypes.CDLL:
                'wdmpnn_build_bond_features', 'wdmpnn_adam_step', 'wdmpnn_head_mse', 'wdmpnn_scale', 'wdmpnn_build_graph_ex') + \
             ('wdmpnn_forward_many', 'wdmpnn_feed_slot_bytes', 'wdmpnn_feed_create', 'wdmpnn_feed_next',
              'wdmpnn_feed_release', 'wdmpnn_feed_forward_workspace_bytes', 'wdmpnn_feed_forward',
-             'wdmpnn_feed_destroy', 'wdmpnn_adam_step_repack'):
+             'wdmpnn_feed_destroy', 'wdmpnn_adam_step_repack', 'wdmpnn_head_predict'):
         getattr(L, fn).restype = c_int
     v = L.wdmpnn_abi_version()
     if v != ABI_VERSION:

@@ -15,6 +15,10 @@ restated here:
 * split: ``split_type random`` with ``split_sizes`` and ``seed`` (data/utils.py:536-547), the default
   branch the fork lost in run_training.py:58-89 and that run_training_V0.py:74-81 still has;
 * targets scaled by a StandardScaler fit on the training set (scaler.py:6-63) for regression;
+  ``--dataset_type multiclass``: every target cell is a class index in ``[0, --multiclass_num_classes)``
+  (checked before training, the CSV row named on failure), no scaler, ``cross_entropy`` as the default
+  metric (args.py:557-558), ``test_preds.csv`` with one ``<task>_class_<k>`` column per class
+  (make_predictions.py:213);
 * MoleculeModel + initialize_weights after ``torch.manual_seed(pytorch_seed)`` (run_training.py:36,
   model.py:39), Adam (utils.py:295-310), NoamLR stepped per batch (utils.py:490-541, nn_utils.py:115-194),
   training batches reshuffled every epoch by one ``Random(seed)`` (data.py:537-587);
@@ -149,8 +153,12 @@ def random_split(n: int, sizes, seed: int):
 
 
 def metric_value(metric: str, targets: List[float], preds: List[float]) -> float:
-    """utils.py get_metric_func for the scalar metrics."""
-    from sklearn.metrics import mean_absolute_error, mean_squared_error, r2_score, roc_auc_score
+    """utils.py get_metric_func for the scalar metrics.  ``cross_entropy`` (multiclass: preds are per-class
+    probability lists) is ``log_loss`` over the labels ``0 .. C-1`` as evaluate.py:72-74 calls it, so a class
+    absent from ``targets`` keeps its column; ``accuracy`` (utils.py:416-432) takes the argmax of list
+    predictions and thresholds scalar ones at 0.5."""
+    from sklearn.metrics import accuracy_score, log_loss, mean_absolute_error, mean_squared_error, r2_score, \
+        roc_auc_score
     if metric == 'rmse':
         return math.sqrt(mean_squared_error(targets, preds))
     if metric == 'mse':
@@ -161,6 +169,16 @@ def metric_value(metric: str, targets: List[float], preds: List[float]) -> float
         return r2_score(targets, preds)
     if metric == 'auc':
         return roc_auc_score(targets, preds)
+    if metric == 'cross_entropy':
+        if isinstance(preds[0], (list, tuple)):
+            return log_loss(targets, preds, labels=list(range(len(preds[0]))))
+        return log_loss(targets, preds)
+    if metric == 'accuracy':
+        if isinstance(preds[0], (list, tuple)):  # multiclass
+            hard = [list(p).index(max(p)) for p in preds]
+        else:
+            hard = [1 if p > 0.5 else 0 for p in preds]
+        return accuracy_score(targets, hard)
     raise ValueError(f'Metric "{metric}" not supported.')
 
 
@@ -206,11 +224,38 @@ def read_csv(path: str):
     return header, smiles, targets
 
 
+def read_class_targets(path: str, num_classes: int) -> List[List[Optional[int]]]:
+    """The target cells of a multiclass CSV as class indices (empty = missing): every other cell must be an
+    integer in [0, num_classes), else ValueError naming the CSV row (1-based, the header being row 1)."""
+    with open(path) as f:
+        rows = list(csv.reader(f))
+    out = []
+    for n, r in enumerate(rows[1:], start=2):
+        if not r:
+            continue
+        row = []
+        for col, x in enumerate(r[1:], start=2):
+            if x.strip() == '':
+                row.append(None)
+                continue
+            try:
+                v = float(x)
+            except ValueError:
+                v = float('nan')
+            if not (v.is_integer() and 0 <= v < num_classes):  # (False for nan and inf)
+                raise ValueError(f'{path}, row {n}, column {col}: {x!r} is not an integer class index in '
+                                 f'[0, {num_classes})')
+            row.append(int(v))
+        out.append(row)
+    return out
+
+
 def parse_args(argv=None) -> argparse.Namespace:
     ap = argparse.ArgumentParser(prog='chemprop_train', description=__doc__.split('\n')[0])
     ap.add_argument('--data_path', required=True)
     ap.add_argument('--graphs_path', required=True, help='pre-featurised MolGraph records, one per CSV row')
-    ap.add_argument('--dataset_type', default='regression', choices=['regression', 'classification'])
+    ap.add_argument('--dataset_type', default='regression', choices=['regression', 'classification', 'multiclass'])
+    ap.add_argument('--multiclass_num_classes', type=int, default=3)
     ap.add_argument('--save_dir', required=True)
     ap.add_argument('--polymer', action='store_true')
     ap.add_argument('--split_type', default='random', choices=['random'])
@@ -253,15 +298,20 @@ def run_training(a: argparse.Namespace) -> Dict[str, list]:
                 if not np.isclose(deg, g.degree_of_polym, rtol=1e-6):
                     raise ValueError(f'graph degree_of_polym {g.degree_of_polym} != 1 + log10(Xn) = {deg} for {s}')
     num_tasks = len(header) - 1
-    metric = a.metric or ('rmse' if a.dataset_type == 'regression' else 'auc')
+    multiclass = a.dataset_type == 'multiclass'
+    if multiclass:  # class indices, checked here: a bad one must not reach the loss on the device
+        if a.multiclass_num_classes < 2:
+            raise ValueError('--multiclass_num_classes must be at least 2')
+        targets = read_class_targets(a.data_path, a.multiclass_num_classes)
+    metric = a.metric or {'regression': 'rmse', 'multiclass': 'cross_entropy'}.get(a.dataset_type, 'auc')
     metrics = [metric] + [m for m in a.extra_metrics if m != metric]
-    minimize = metric in ('rmse', 'mse', 'mae')
+    minimize = metric in ('rmse', 'mse', 'mae', 'cross_entropy')
     device = torch.device('cuda', a.gpu)
     args = TrainArgs(hidden_size=a.hidden_size, depth=a.depth, dropout=a.dropout, activation=a.activation,
                      aggregation=a.aggregation, aggregation_norm=a.aggregation_norm, bias=a.bias,
                      undirected=a.undirected, ffn_num_layers=a.ffn_num_layers,
                      ffn_hidden_size=a.ffn_hidden_size or a.hidden_size, dataset_type=a.dataset_type,
-                     num_tasks=num_tasks, device=device)
+                     num_tasks=num_tasks, multiclass_num_classes=a.multiclass_num_classes, device=device)
     torch.manual_seed(a.pytorch_seed)
     train_idx, val_idx, test_idx = random_split(len(smiles), a.split_sizes, a.seed)
     scaler = None
@@ -322,9 +372,13 @@ def run_training(a: argparse.Namespace) -> Dict[str, list]:
             w.writerow([name] + [scores[m][t] if t < len(scores[m]) else '' for m in metrics])
     with open(os.path.join(a.save_dir, 'test_preds.csv'), 'w', newline='') as f:
         w = csv.writer(f)
-        w.writerow(header)
+        if multiclass:  # one column per class (make_predictions.py:213)
+            w.writerow(header[:1] + [f'{name}_class_{k}' for name in header[1:]
+                                     for k in range(a.multiclass_num_classes)])
+        else:
+            w.writerow(header)
         for i, p in zip(test_idx, test_preds):
-            w.writerow([smiles[i]] + list(p))
+            w.writerow([smiles[i]] + ([x for task in p for x in task] if multiclass else list(p)))
     with open(os.path.join(a.save_dir, 'split_indices.json'), 'w') as f:
         json.dump({'train': train_idx, 'val': val_idx, 'test': test_idx, 'best_epoch': best_epoch}, f)
     return scores

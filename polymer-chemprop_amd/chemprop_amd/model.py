@@ -1,5 +1,6 @@
 """MoleculeModel (``chemprop/models/model.py:14-194``): the encoder runs on the HIP library, the
-small FFN head stays PyTorch (~1 % of the forward).  Module layout and
+small FFN head stays PyTorch (~1 % of the forward) except for multiclass
+prediction, which runs the native prediction head (``train.head_predict``).  Module layout and
 state_dict keys (``encoder.encoder.0.*``, ``ffn.1.*``, ``ffn.4.*`` ...) match the reference."""
 from __future__ import annotations
 
@@ -84,6 +85,15 @@ class MoleculeModel(nn.Module):
                 return_embeddings: bool = False):
         """model.py:152-194."""
         emb = self.encoder(batch, features_batch, atom_descriptors_batch, atom_features_batch, bond_features_batch)
+        if self.multiclass and not self.training and not torch.is_grad_enabled():
+            # multiclass prediction: ffn, the reshape and the softmax as two HIP launches (train.head_predict)
+            # when the head is the two-layer one the native head runs; the torch ops below otherwise
+            from .train import _predict_head, head_predict
+            head = _predict_head(self)
+            if head is not None and emb.dim() == 2 and emb.dtype == torch.float32 and \
+                    emb.device == head[0].weight.device:
+                out = head_predict(self, emb, head)
+                return (out, emb) if return_embeddings else out
         out = self.ffn(emb)
         if self.classification and not self.training:
             out = self.sigmoid(out)

@@ -230,9 +230,8 @@ def _host_table(rows: np.ndarray, dev: torch.device, zero_copy: bool = False):
     return table
 
 
-def _loss_table(target_batch, target_weights, data_weights, dev, zero_copy: bool = False):
-    """train.py:46-74's targets and weights as one device table [B][2T] (targets | w = target weight *
-    data weight * mask, rounded once to fp32) and the host count mask.sum()."""
+def _targets_and_mask(target_batch):
+    """train.py:46-48 on the host: (targets with 0 for the missing ones, mask), float64 [B][T]."""
     n_b = len(target_batch)
     n_t = len(target_batch[0]) if n_b else 0
     # missing targets are None (train.py:47-48); numpy's float conversion would turn them into NaN, so the
@@ -252,6 +251,37 @@ def _loss_table(target_batch, target_weights, data_weights, dev, zero_copy: bool
         present = obj != None  # noqa: E711 (elementwise)
         tgt = np.where(present, obj, 0.0).astype(np.float64)
         mask = present.astype(np.float64)
+    return tgt, mask
+
+
+def _check_class_indices(tgt: np.ndarray, mask: np.ndarray, num_classes: int) -> None:
+    """Every present target must be a class index: an integer in [0, num_classes).  torch's own check
+    (nll_loss) is a device-side assert that takes the process's GPU context down; this one runs on the
+    host before anything is launched."""
+    ok = (tgt == np.floor(tgt)) & (tgt >= 0) & (tgt < num_classes)  # (NaN compares false)
+    bad = (mask > 0) & ~ok
+    if bad.any():
+        r, t = (int(v) for v in np.argwhere(bad)[0])
+        raise ValueError(f'multiclass target {tgt[r, t]!r} in row {r}, task {t} is not an integer class index in '
+                         f'[0, {num_classes})')
+
+
+def check_class_targets(target_batch, num_classes: int) -> None:
+    """Raise ValueError unless every target of ``target_batch`` ([B][tasks], None = missing) is an integer
+    class index in [0, num_classes); the message names the first offending row and task."""
+    if len(target_batch):
+        _check_class_indices(*_targets_and_mask(target_batch), num_classes)
+
+
+def _loss_table(target_batch, target_weights, data_weights, dev, zero_copy: bool = False, num_classes: int = 0):
+    """train.py:46-74's targets and weights as one device table [B][2T] (targets | w = target weight *
+    data weight * mask, rounded once to fp32) and the host count mask.sum().  ``num_classes`` > 0
+    (multiclass): the targets are class indices, checked on the host (``_check_class_indices``)."""
+    n_b = len(target_batch)
+    n_t = len(target_batch[0]) if n_b else 0
+    tgt, mask = _targets_and_mask(target_batch)
+    if num_classes and n_b:
+        _check_class_indices(tgt, mask, num_classes)
     tw = np.ones(n_t) if target_weights is None else np.asarray(target_weights, dtype=np.float64)
     dw = np.ones(n_b) if data_weights is None else np.asarray(data_weights, dtype=np.float64)
     # targets and W travel as one host table (one pinned, asynchronous copy: pageable copies would each
@@ -285,7 +315,8 @@ def batch_loss(preds: torch.Tensor, target_batch: Sequence[Sequence[Optional[flo
 # 57-121), loss_func(preds, targets) * weights and .sum() / mask.sum() (train.py:55-74) and autograd runs
 # their backward: ~25 small torch ops whose host time left the GPU idle for most of the step
 # (profiles/round2_train_kernel_trace_v3.txt).  For the default head (two Linear layers, an activation, no
-# active dropout; MSELoss for regression, BCEWithLogitsLoss for classification) the loss and every gradient of the head come from two HIP
+# active dropout; MSELoss for regression, BCEWithLogitsLoss for classification, per-task CrossEntropyLoss for
+# multiclass) the loss and every gradient of the head come from two HIP
 # launches in the forward; the backward scales them by the loss's incoming gradient (one launch).
 # ------------------------------------------------------------------------------------------------
 def _head_act(m: nn.Module) -> Optional[int]:
@@ -304,15 +335,37 @@ def _head_act(m: nn.Module) -> Optional[int]:
 
 
 def _fusable_head(model: nn.Module, loss_func: Callable, dataset_type: str):
-    """(Linear 1, Linear 2, activation code) when the step's head + loss can run fused, else None."""
-    from .model import MoleculeModel
+    """(Linear 1, Linear 2, activation code, loss kind, classes per task) when the step's head + loss can
+    run fused, else None.  Classes per task is 1 but for multiclass (kind 2)."""
+    n_classes = 1
     if dataset_type == 'regression' and type(loss_func) is nn.MSELoss and loss_func.reduction == 'none':
         kind = 0
     elif dataset_type == 'classification' and type(loss_func) is nn.BCEWithLogitsLoss and \
             loss_func.reduction == 'none' and loss_func.weight is None and loss_func.pos_weight is None:
         kind = 1  # (the FFN's logits: MoleculeModel applies the sigmoid only outside training, model.py:186-188)
+    elif dataset_type == 'multiclass' and type(loss_func) is nn.CrossEntropyLoss and \
+            loss_func.reduction == 'none' and loss_func.weight is None and loss_func.ignore_index == -100 and \
+            loss_func.label_smoothing == 0:
+        kind = 2  # (one softmax cross-entropy per task over its num_classes logits, train.py:67-69)
+        n_classes = getattr(model, 'num_classes', 0) if getattr(model, 'multiclass', False) else 0
+        if not isinstance(n_classes, int) or n_classes < 2:
+            return None
     else:
         return None
+    st = _head_structure(model)
+    if st is None:
+        return None
+    l1, l2, code = st
+    if kind == 2 and (l2.out_features % n_classes or l2.out_features != getattr(model, 'output_size', -1)):
+        return None
+    return l1, l2, code, kind, n_classes
+
+
+def _head_structure(model: nn.Module):
+    """(Linear 1, Linear 2, activation code) of a MoleculeModel whose FFN the native head kernels can run
+    (Dropout / Linear / activation / Dropout / Linear on the GPU, no dropout while training, at most 64
+    outputs), else None."""
+    from .model import MoleculeModel
     if not isinstance(model, MoleculeModel) or type(model).forward is not MoleculeModel.forward:
         return None
     ffn = model.ffn
@@ -332,14 +385,14 @@ def _fusable_head(model: nn.Module, loss_func: Callable, dataset_type: str):
             return None
     if l1.in_features > 4096 or l1.out_features > 4096 or l2.out_features > 64:
         return None
-    return l1, l2, code, kind
+    return l1, l2, code
 
 
 class _HeadMSE(torch.autograd.Function):
     """loss = sum(w (W2 act(W1 x + b1) + b2 - y)^2) / n, with every gradient computed in the forward."""
 
     @staticmethod
-    def forward(ctx, x, W1, b1, W2, b2, table, inv_n, act, kind):
+    def forward(ctx, x, W1, b1, W2, b2, table, inv_n, act, kind, n_classes):
         from . import _native
         x = x.contiguous()
         dev = x.device
@@ -355,7 +408,7 @@ class _HeadMSE(torch.autograd.Function):
         sp = scratch.data_ptr()
         h = _native.WdHead(ptr(x), F, B, F, Hf, T, ptr(W1), ptr(b1), ptr(W2), ptr(b2), ptr(table), table.shape[1],
                            float(inv_n), act, sp, sp + 4 * B * Hf, sp + 8 * B * Hf, sp + 4 * B * (2 * Hf + T),
-                           ptr(dx), ptr(dW1), ptr(db1), ptr(dW2), ptr(db2), ptr(loss), kind)
+                           ptr(dx), ptr(dW1), ptr(db1), ptr(dW2), ptr(db2), ptr(loss), kind, n_classes)
         _native.check(_native.lib().wdmpnn_head_mse(ctypes.byref(h), _native.current_stream(dev)), 'FFN head + loss')
         ctx.grads = (dx, dW1, db1, dW2, db2)
         return loss
@@ -370,21 +423,71 @@ class _HeadMSE(torch.autograd.Function):
         ns = (ctypes.c_int64 * len(live))(*[g.numel() for g in live])
         _native.check(_native.lib().wdmpnn_scale(ptrs, ns, len(live), gl.data_ptr(),
                                                  _native.current_stream(gl.device)), 'scale')
-        return grads + (None, None, None, None)
+        return grads + (None, None, None, None, None)
 
 
 def head_loss(emb: torch.Tensor, head, target_batch, target_weights=None, data_weights=None) -> torch.Tensor:
     """``batch_loss(model.ffn(emb), ...)`` for a head accepted by ``_fusable_head`` (regression with MSE,
-    classification with BCE on logits)."""
-    l1, l2, act, kind = head
-    table, n_t, n_mask = _loss_table(target_batch, target_weights, data_weights, emb.device)
-    if n_t != l2.out_features:
+    classification with BCE on logits, multiclass with one cross-entropy per task: the targets are then
+    class indices, one per task, checked on the host)."""
+    l1, l2, act, kind, n_classes = head
+    table, n_t, n_mask = _loss_table(target_batch, target_weights, data_weights, emb.device,
+                                     num_classes=n_classes if kind == 2 else 0)
+    if n_t * n_classes != l2.out_features:
         raise ValueError(f'{n_t} targets per row for {l2.out_features} outputs')
     if table.shape[0] != emb.shape[0] or emb.dim() != 2 or emb.shape[1] != l1.in_features:
         raise ValueError(f'{table.shape[0]} target rows for encodings of shape {tuple(emb.shape)} '
                          f'(FFN input {l1.in_features})')
     inv_n = 1.0 / n_mask if n_mask else float('inf')
-    return _HeadMSE.apply(emb, l1.weight, l1.bias, l2.weight, l2.bias, table, inv_n, act, kind)
+    return _HeadMSE.apply(emb, l1.weight, l1.bias, l2.weight, l2.bias, table, inv_n, act, kind, n_classes)
+
+
+def _predict_head(model: nn.Module):
+    """(Linear 1, Linear 2, activation code, output kind, classes per task) when ``head_predict`` can run
+    the model's FFN and output activation (model.py:186-192), else None."""
+    st = _head_structure(model)
+    if st is None:
+        return None
+    l2 = st[1]
+    if getattr(model, 'multiclass', False):
+        c = getattr(model, 'num_classes', 0)
+        if not isinstance(c, int) or c < 2 or l2.out_features % c:
+            return None
+        return st + (2, c)
+    return st + (1 if getattr(model, 'classification', False) else 0, 1)
+
+
+def head_predict(model: nn.Module, emb: torch.Tensor, head=None) -> torch.Tensor:
+    """The eval-mode predictions of ``model`` from the encodings ``emb`` (model.py:152-194 after the
+    encoder: ``ffn``, then nothing for regression, the sigmoid for classification, the softmax over each
+    task's classes for multiclass) as two HIP launches (``wdmpnn_head_predict``).  ``[B][T]`` for
+    regression and classification, ``[B][tasks][classes]`` for multiclass.  No autograd graph is built.
+    The model must be in eval mode with the two-layer head the fused training head accepts
+    (``NotImplementedError`` otherwise: there is no torch fallback here)."""
+    from . import _native
+    if model.training:
+        raise ValueError('head_predict is the eval-mode head: call model.eval() first')
+    if head is None:
+        head = _predict_head(model)
+    if head is None:
+        raise NotImplementedError('head_predict: the model\'s FFN is not the two-layer head (<= 64 outputs, no PReLU) '
+                                  'the native head runs')
+    l1, l2, act, kind, n_classes = head
+    if emb.dim() != 2 or emb.shape[1] != l1.in_features or emb.device != l1.weight.device or \
+            emb.dtype != torch.float32:
+        raise ValueError(f'encodings of shape {tuple(emb.shape)} ({emb.dtype}, {emb.device}) for an FFN input of '
+                         f'{l1.in_features} on {l1.weight.device}')
+    x = emb.detach().contiguous()
+    B, F = x.shape
+    Hf, T = l1.out_features, l2.out_features
+    a = torch.empty((B, Hf), dtype=torch.float32, device=x.device)
+    out = torch.empty((B, T), dtype=torch.float32, device=x.device)
+    ptr = _native.ptr
+    h = _native.WdHeadPredict(ptr(x), F, B, F, Hf, T, ptr(l1.weight), ptr(l1.bias), ptr(l2.weight), ptr(l2.bias),
+                              act, ptr(a), ptr(out), kind, n_classes)
+    _native.check(_native.lib().wdmpnn_head_predict(ctypes.byref(h), _native.current_stream(x.device)),
+                  'FFN head (predict)')
+    return out.view(B, T // n_classes, n_classes) if kind == 2 else out
 
 
 def _grad_buffer(p: torch.Tensor) -> torch.Tensor:
@@ -449,17 +552,19 @@ def _direct_step(model, enc, graph, head, target_batch, target_weights, data_wei
     parameters' .grad buffers.  The same launches as the autograd path minus its host gaps (the engine
     hand-off, the gradient-seed fill and the scale by 1; profiles/round3_*)."""
     from . import _native
-    l1, l2, act, kind = head
+    l1, l2, act, kind, n_classes = head
+    nc = n_classes if kind == 2 else 0  # (multiclass: _loss_table checks the class indices on the host)
     out, state = enc._train_forward(graph)
     # the loss table read by the head kernel straight from its pinned host buffer (no copy launch in the
     # step: the copy kernel and its gap were ~10 us, profiles/round4_train_kernel_trace_v1.txt)
-    zc, n_t, n_mask, tshape = _loss_table(target_batch, target_weights, data_weights, out.device, zero_copy=True)
+    zc, n_t, n_mask, tshape = _loss_table(target_batch, target_weights, data_weights, out.device, zero_copy=True,
+                                          num_classes=nc)
     if zc is None:
-        table, n_t, n_mask = _loss_table(target_batch, target_weights, data_weights, out.device)
+        table, n_t, n_mask = _loss_table(target_batch, target_weights, data_weights, out.device, num_classes=nc)
         tab_ptr, tshape = table.data_ptr(), tuple(table.shape)
     else:
         tab_ptr = zc[0]
-    if n_t != l2.out_features:
+    if n_t * n_classes != l2.out_features:
         raise ValueError(f'{n_t} targets per row for {l2.out_features} outputs')
     if tshape[0] != out.shape[0] or out.shape[1] != l1.in_features:
         raise ValueError(f'{tshape[0]} target rows for encodings of shape {tuple(out.shape)} '
@@ -478,7 +583,7 @@ def _direct_step(model, enc, graph, head, target_batch, target_weights, data_wei
     sp = scratch.data_ptr()
     h = _native.WdHead(ptr(out), F, B, F, Hf, T, ptr(l1.weight), ptr(l1.bias), ptr(l2.weight), ptr(l2.bias), tab_ptr,
                        tshape[1], float(inv_n), act, sp, sp + 4 * B * Hf, sp + 8 * B * Hf, sp + 4 * B * (2 * Hf + T),
-                       ptr(dx), ptr(dW1), ptr(db1), ptr(dW2), ptr(db2), ptr(loss), kind)
+                       ptr(dx), ptr(dW1), ptr(db1), ptr(dW2), ptr(db2), ptr(loss), kind, n_classes)
     _native.check(_native.lib().wdmpnn_head_mse(ctypes.byref(h), _native.current_stream(dev)), 'FFN head + loss')
     if zc is not None:
         zc[1].record(torch.cuda.current_stream(dev))  # (the pinned buffer's last reader)
@@ -494,7 +599,7 @@ def train_step(model: nn.Module, mol_batch, target_batch, loss_func: Callable, o
                bucket: GradBucket = None, fused_head: bool = True, direct: bool = True) -> torch.Tensor:
     """One optimisation step (train.py:55-86).  With ``bucket`` the gradients are averaged over the
     data-parallel ranks (one all-reduce) before clipping and the optimizer step.  ``fused_head``: the
-    default regression / classification head + loss run as ``wdmpnn_head_mse`` (same loss and gradients within fp32
+    default regression / classification / multiclass head + loss run as ``wdmpnn_head_mse`` (same loss and gradients within fp32
     summation order; ``False`` = the torch ops of the reference).  ``direct``: with the fused head and a
     plain one-molecule encoder, skip the autograd engine (``_direct_step``: the same launches and results,
     bitwise, without the engine's host gaps).  The direct step keeps one packed copy of the encoder weights

@@ -786,6 +786,9 @@ __global__ __launch_bounds__(256) void adam_kernel(AdamLaunch A) {
 // dx = W1^T dh, dW1 = sum_rows dh x^T, db1 = sum dh, dW2 = sum dout a^T, db2 = sum dout.  Three launches:
 // the H GEMM, one wave per row for the loss and dh, then the dX and dW1 GEMMs and the small sums (fixed
 // summation orders).  fp32 FMA throughout (the GEMMs are 128 x 300 x 300: latency, not FLOPs).
+// loss_kind 1 swaps in BCE on the logits, loss_kind 2 (head_rows_ce_kernel) one softmax cross-entropy per
+// task over its n_classes outputs; only the row kernel's loss terms and dout differ.  The prediction head
+// (wdmpnn_head_predict) is the same H GEMM followed by head_predict_rows_kernel.
 // ------------------------------------------------------------------------------------------------
 namespace wd {
 constexpr int HEAD_MAX_F = 4096, HEAD_MAX_H = 4096, HEAD_MAX_T = 64;
@@ -971,6 +974,99 @@ __global__ __launch_bounds__(256) void head_rows_kernel(WdHead P) {
             h[j] = act_fwd(ACT, z, 0.f);
         }
     });
+}
+
+// One group of C logits s[0 .. C) (a wave's LDS row): m = max_c s_c and e = sum_c exp(s_c - m), in [1, C].
+// Every lane that calls it runs the same loop in the same order.
+__device__ __forceinline__ void group_max_sum(const float *s, int C, float &m, float &e) {
+    m = s[0];
+    for (int c = 1; c < C; ++c) m = fmaxf(m, s[c]);
+    e = 0.f;
+    for (int c = 0; c < C; ++c) e += expf(s[c] - m);
+}
+
+// head step 2 for the multiclass loss (loss_kind 2), one wave per row: all T = tasks x C logits first
+// (into the wave's LDS row), then per task the max-subtracted softmax cross-entropy (train.py:67-69 with
+// CrossEntropyLoss): loss += w (log(sum_c exp(s_c - m)) - (s_y - m)), dout = w (softmax_c - [c == y]) / n;
+// then dh and act(h) as head_rows_kernel.  The class index y (a float in the table) is only compared with
+// c: an index outside [0, C) selects no logit.
+__global__ __launch_bounds__(256) void head_rows_ce_kernel(WdHead P) {
+    __shared__ float dsh[4][HEAD_MAX_T];  // the row's logits, then its dout (every lane writes the same values)
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6, row = blockIdx.x * 4 + wave;
+    if (row >= P.B) return;
+    const int Hf = P.Hf, T = P.T, C = P.n_classes, K = T / C;  // (C >= 2 and T <= 64: 2 K <= 64 table entries)
+    float *h = P.a + (size_t)row * Hf;
+    const float *tab = P.table + (size_t)row * P.ld_table;
+    // the row's targets | weights, one per lane, loaded first (head_rows_kernel: the table may be pinned host memory)
+    const float tv = lane < 2 * K ? tab[lane] : 0.f;
+    float *ds = dsh[wave];
+    with_act(P.act, [&](auto act_c) {
+        constexpr int ACT = decltype(act_c)::value;
+        for (int t = 0; t < T; ++t) {
+            const float *w2 = P.W2 + (size_t)t * Hf;
+            float s = 0.f;
+            for (int j = lane; j < Hf; j += 64) s = fmaf(w2[j], act_fwd(ACT, h[j], 0.f), s);
+            ds[t] = wave_sum(s) + (P.b2 ? P.b2[t] : 0.f);
+        }
+        float l = 0.f;
+        for (int k = 0; k < K; ++k) {
+            const float y = __shfl(tv, k, 64), w = __shfl(tv, K + k, 64);
+            float *s = ds + k * C;
+            float m, e;
+            group_max_sum(s, C, m, e);
+            const float logsum = logf(e);
+            float sy = 0.f;  // s_y - m
+            for (int c = 0; c < C; ++c) {
+                const float z = s[c] - m;
+                const bool hit = (float)c == y;
+                sy = hit ? z : sy;
+                const float d = w * (expf(z - logsum) - (hit ? 1.f : 0.f)) * P.inv_n;
+                s[c] = d;
+                if (lane == 0) P.dout[(size_t)row * T + k * C + c] = d;
+            }
+            l = fmaf(w, logsum - sy, l);
+        }
+        if (lane == 0) P.lossrow[row] = l;
+        for (int j = lane; j < Hf; j += 64) {
+            float s = 0.f;
+            for (int t = 0; t < T; ++t) s = fmaf(ds[t], P.W2[(size_t)t * Hf + j], s);
+            const float z = h[j];
+            P.dh[(size_t)row * Hf + j] = s * act_grad(ACT, z, 0.f);
+            h[j] = act_fwd(ACT, z, 0.f);
+        }
+    });
+}
+
+// prediction head step 2 (wdmpnn_head_predict), one wave per row: out = W2 act(h) + b2 into the wave's LDS
+// row, then lane t finishes output t: identity, sigmoid, or the max-subtracted softmax over its group of
+// C outputs (model.py:186-192)
+__global__ __launch_bounds__(256) void head_predict_rows_kernel(WdHeadPredict P) {
+    __shared__ float osh[4][HEAD_MAX_T];
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6, row = blockIdx.x * 4 + wave;
+    if (row >= P.B) return;
+    const int Hf = P.Hf, T = P.T;
+    const float *h = P.a + (size_t)row * Hf;
+    float *os = osh[wave];
+    with_act(P.act, [&](auto act_c) {
+        constexpr int ACT = decltype(act_c)::value;
+        for (int t = 0; t < T; ++t) {
+            const float *w2 = P.W2 + (size_t)t * Hf;
+            float s = 0.f;
+            for (int j = lane; j < Hf; j += 64) s = fmaf(w2[j], act_fwd(ACT, h[j], 0.f), s);
+            os[t] = wave_sum(s) + (P.b2 ? P.b2[t] : 0.f);
+        }
+    });
+    if (lane >= T) return;
+    float v = os[lane];
+    if (P.out_kind == 1) {
+        v = 1.f / (1.f + expf(-v));
+    } else if (P.out_kind == 2) {
+        const int C = P.n_classes;
+        float m, e;
+        group_max_sum(os + (lane / C) * C, C, m, e);
+        v = expf(v - m) / e;
+    }
+    P.out[(size_t)row * T + lane] = v;
 }
 
 // head step 3: dX = dH W1 (tiles 0 .. n1), dW1 = dH^T X (next n2 tiles), then db1, dW2, db2 and the loss

@@ -2142,15 +2142,25 @@ int wdmpnn_adam_step_repack(const WdAdamTensor *tensors, int32_t n, const WdAdam
     return 0;
 }
 
+// the size, activation and class-count checks wdmpnn_head_mse and wdmpnn_head_predict share (kind: the
+// loss or output kind, 2 = grouped by n_classes)
+static int head_check(int B, int F, int Hf, int T, int ld_x, int act, int kind, int n_classes) {
+    if (B < 0 || F <= 0 || Hf <= 0 || T <= 0 || ld_x < F) return fail(WD_ERR_SHAPE, "head: bad sizes");
+    if (F > HEAD_MAX_F || Hf > HEAD_MAX_H || T > HEAD_MAX_T)
+        return fail(WD_ERR_UNSUPPORTED, "head: F, Hf <= 4096 and T <= 64");
+    if (act < 0 || act > WD_ACT_ELU || act == WD_ACT_PRELU) return fail(WD_ERR_UNSUPPORTED, "head activation");
+    if (kind < 0 || kind > 2) return fail(WD_ERR_UNSUPPORTED, "head kind %d", kind);
+    if (kind == 2 ? n_classes < 2 || T % n_classes != 0 : n_classes != 1)
+        return fail(WD_ERR_SHAPE, "head: kind %d with %d outputs and n_classes %d (kind 2: n_classes >= 2 dividing "
+                                  "the outputs; kinds 0 and 1: n_classes 1)", kind, T, n_classes);
+    return 0;
+}
+
 int wdmpnn_head_mse(const WdHead *h, void *stream) {
     WD_KERNELS_OK();
     if (!h) return fail(WD_ERR_ARG, "null head");
-    if (h->B < 0 || h->F <= 0 || h->Hf <= 0 || h->T <= 0 || h->ld_x < h->F || h->ld_table < 2 * h->T)
-        return fail(WD_ERR_SHAPE, "head: bad sizes");
-    if (h->F > HEAD_MAX_F || h->Hf > HEAD_MAX_H || h->T > HEAD_MAX_T)
-        return fail(WD_ERR_UNSUPPORTED, "head: F, Hf <= 4096 and T <= 64");
-    if (h->act < 0 || h->act > WD_ACT_ELU || h->act == WD_ACT_PRELU) return fail(WD_ERR_UNSUPPORTED, "head activation");
-    if (h->loss_kind != 0 && h->loss_kind != 1) return fail(WD_ERR_UNSUPPORTED, "head loss kind %d", h->loss_kind);
+    WD_TRY(head_check(h->B, h->F, h->Hf, h->T, h->ld_x, h->act, h->loss_kind, h->n_classes));
+    if (h->ld_table < 2 * (h->T / h->n_classes)) return fail(WD_ERR_SHAPE, "head: bad sizes (ld_table)");
     if (!h->W1 || !h->W2 || !h->a || !h->dh || !h->dout || !h->lossrow || !h->dW1 || !h->dW2 || !h->loss ||
         (h->B && (!h->x || !h->table || !h->dx)))
         return fail(WD_ERR_ARG, "head: null pointer");
@@ -2158,13 +2168,31 @@ int wdmpnn_head_mse(const WdHead *h, void *stream) {
     if (h->B > 0) {
         hipLaunchKernelGGL(head_h_kernel, dim3(head_tiles(h->B, h->Hf, HEAD_H_TS)), dim3(256), 0, st, *h);
         WD_CHECK_LAUNCH("head_h");
-        hipLaunchKernelGGL(head_rows_kernel, dim3((h->B + 3) / 4), dim3(256), 0, st, *h);
+        if (h->loss_kind == 2) hipLaunchKernelGGL(head_rows_ce_kernel, dim3((h->B + 3) / 4), dim3(256), 0, st, *h);
+        else hipLaunchKernelGGL(head_rows_kernel, dim3((h->B + 3) / 4), dim3(256), 0, st, *h);
         WD_CHECK_LAUNCH("head_rows");
     }
     const long long rest = h->Hf + (long long)h->T * h->Hf + h->T + 1;
     const long long blocks = head_tiles(h->B, h->F, HEAD_H_TS) + head_tiles(h->Hf, h->F, HEAD_G_TS) + (rest + 255) / 256;
     hipLaunchKernelGGL(head_grads_kernel, dim3((unsigned)blocks), dim3(256), 0, st, *h);
     WD_CHECK_LAUNCH("head_grads");
+    return 0;
+}
+
+int wdmpnn_head_predict(const WdHeadPredict *h, void *stream) {
+    WD_KERNELS_OK();
+    if (!h) return fail(WD_ERR_ARG, "null head");
+    WD_TRY(head_check(h->B, h->F, h->Hf, h->T, h->ld_x, h->act, h->out_kind, h->n_classes));
+    if (!h->W1 || !h->W2 || (h->B && (!h->x || !h->a || !h->out))) return fail(WD_ERR_ARG, "head: null pointer");
+    if (h->B == 0) return 0;
+    hipStream_t st = (hipStream_t)stream;
+    WdHead v{};  // head_h_kernel's view: H = X W1^T + b1 -> a
+    v.x = h->x; v.ld_x = h->ld_x; v.B = h->B; v.F = h->F; v.Hf = h->Hf; v.T = h->T;
+    v.W1 = h->W1; v.b1 = h->b1; v.a = h->a;
+    hipLaunchKernelGGL(head_h_kernel, dim3(head_tiles(h->B, h->Hf, HEAD_H_TS)), dim3(256), 0, st, v);
+    WD_CHECK_LAUNCH("head_h");
+    hipLaunchKernelGGL(head_predict_rows_kernel, dim3((h->B + 3) / 4), dim3(256), 0, st, *h);
+    WD_CHECK_LAUNCH("head_predict_rows");
     return 0;
 }
 
