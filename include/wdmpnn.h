@@ -24,7 +24,7 @@
  *    accumulation over exact splits of the fp32 operands: fp16 hi / lo pairs with a power-of-two scale
  *    (three products per fp32 product, the message layers and the backward's W_h GEMMs) or three bf16
  *    planes (six products: W_o, W_i and the unblocked path).  Error against fp64 stays that of an fp32
- *    GEMM; WdConfig.gemm_variant 9 selects plain f32-in MFMA on the unblocked path.
+ *    GEMM; WdConfig.gemm_variant WD_VARIANT_F32 selects plain f32-in MFMA on the unblocked path.
  *  - Padding: f_atoms / f_bonds / atom_desc rows are allocated up to a multiple of 128 and their row
  *    stride covers the feature width rounded up to 32; padding is zero.  (The host packer,
  *    BatchMolGraph.device_graph, lays them out this way.)  Weights are the unpadded nn.Linear
@@ -60,6 +60,31 @@ enum WdError {
     WD_OK = 0, WD_ERR_ARG = -1000, WD_ERR_SHAPE = -1001, WD_ERR_WORKSPACE = -1002,
     WD_ERR_UNSUPPORTED = -1003
 };
+
+/* Values of WdConfig.gemm_variant (an A/B and debugging knob; any other value is not rejected). */
+enum WdVariant {
+    /* fp32-accurate split GEMMs with the molecule-blocked fused inference forward when
+     * WdGraph.blocks allow it: its message layers and W_o read fp16 pair tiles their producers wrote (bond
+     * messages, hidden rounded to 64 a multiple of 80), QM9-sized blocks take the one-launch forward */
+    WD_VARIANT_DEFAULT = 0,
+    /* f32-MFMA GEMMs on the unblocked path (precision A/B) */
+    WD_VARIANT_F32 = 9,
+    /* the fused four-launch forward also for QM9-sized blocks (no one-launch forward) */
+    WD_VARIANT_FOUR_LAUNCH = 11,
+    /* as FOUR_LAUNCH, the message layers staging M_{t-1} from fp32 Z_t rows through registers (the round-5
+     * default); neither the packed weights nor the workspace then hold pair tiles */
+    WD_VARIANT_STAGED = 12,
+    /* as FOUR_LAUNCH, on pair tiles */
+    WD_VARIANT_PAIRS = 13,
+    /* Debug (tools/debug_pairs.py), 1ab = WD_VARIANT_DEBUG + 10 a + b: the four-launch forward with a =
+     * WD_DEBUG_PAIRS pair layers or WD_DEBUG_STAGED register-staged layers (the workspace and the pack keep
+     * their pair tiles either way), returning after stage b = 1 the embed, 1 + t message layer t, 0 none: the
+     * intermediate buffers stay in the workspace (wdmpnn_debug_fwd_offsets).  b = WD_DEBUG_WO_DUMP at depth 3
+     * (no stop left to reach) also writes the W_o pre-activation into the free second ping-pong buffer. */
+    WD_VARIANT_DEBUG = 100,
+    WD_DEBUG_PAIRS = 1, WD_DEBUG_STAGED = 2, WD_DEBUG_WO_DUMP = 4
+};
+#define WD_VARIANT_DEBUG_STOP(a, b) (WD_VARIANT_DEBUG + 10 * (a) + (b))
 
 /* One row-gather list: row r of the gathered operand = sum_{e=ptr[r]}^{ptr[r+1]-1} coef[e] * src[idx[e]].
  * idx and coef must be readable (any value) for 8 entries past ptr[rows]: the gather kernels fetch the
@@ -193,14 +218,7 @@ typedef struct WdConfig {
     void   *prof_pool;      /* optional WdEventPool: one event pair (pair prof_slot) is recorded around
                                the depth - 1 message-passing launches (the dominant kernel) of this
                                forward: before the first, after the last                          */
-    int32_t gemm_variant;   /* 0 (default): fp32-accurate split GEMMs with the molecule-blocked
-                               fused inference forward when WdGraph.blocks allow it: its message layers and
-                               W_o read fp16 pair tiles their producers wrote (bond messages, hidden rounded
-                               to 64 a multiple of 80), QM9-sized blocks take the one-launch forward;
-                               9: f32-MFMA GEMMs on the unblocked path (precision A/B); 11: the fused
-                               four-launch forward also for QM9-sized blocks (no one-launch forward);
-                               12: as 11, the message layers staging M_{t-1} from fp32 Z_t rows through
-                               registers (the round-5 default); 13: as 11, on pair tiles.            */
+    int32_t gemm_variant;   /* WdVariant (0 = WD_VARIANT_DEFAULT)                                      */
 } WdConfig;
 
 /* Gradients (device, caller-zeroed NOT required: every pointer is fully overwritten). NULL = skip. */

@@ -25,6 +25,14 @@ ABI_VERSION = 12
 GRAPH_LEAN = 1  # WDMPNN_GRAPH_LEAN
 GRAPH_NO_PLANES = 2  # WDMPNN_GRAPH_NO_PLANES
 ERR_UNSUPPORTED = -1003  # WD_ERR_UNSUPPORTED
+# WdConfig.gemm_variant (wdmpnn.h WdVariant, which describes them)
+VARIANT_DEFAULT, VARIANT_F32, VARIANT_FOUR_LAUNCH, VARIANT_STAGED, VARIANT_PAIRS, VARIANT_DEBUG = 0, 9, 11, 12, 13, 100
+DEBUG_PAIRS, DEBUG_STAGED, DEBUG_WO_DUMP = 1, 2, 4
+
+
+def variant_debug(layers: int, stage: int) -> int:
+    """WD_VARIANT_DEBUG_STOP: DEBUG_PAIRS or DEBUG_STAGED layers, returning after ``stage`` (0: none)."""
+    return VARIANT_DEBUG + 10 * layers + stage
 
 EXPORTED_SYMBOLS = ('wdmpnn_abi_version', 'wdmpnn_last_error', 'wdmpnn_workspace_bytes',
                     'wdmpnn_backward_workspace_bytes', 'wdmpnn_forward', 'wdmpnn_backward',

@@ -121,28 +121,73 @@ int ew_blocks(size_t total) {
 // ------------------------------------------------------------------------------------------------
 // dimensions
 // ------------------------------------------------------------------------------------------------
-struct Dims {
-    int H, Hk, T, R, Rp, Va, Vap, B, Fa, Fak, Fb, Fbk, d, dk, Hd, Hdk, Kin, Kink;
-    int ldx, Ko, Kd;
-    bool atom, undirected, save, desc;
-    bool f32;  // WdConfig.gemm_variant 9: f32-MFMA GEMMs (gemm_nt16_kernel) on the unblocked path
-    bool x6;   // plane-tile pipeline: gathers emit bf16x3 plane tiles, GEMMs run gemm_x6g_kernel
-    bool blocked;  // molecule-blocked fused inference forward (fused_mp.hpp)
-    bool small;    // ... as ONE launch, a workgroup per block (small_fwd.hpp: blocks <= 32 rows, Hk 320)
-    bool pairs;    // ... hands M_t between the launches as fp16 pair tiles (LDS-DMA layer operands): the
-                   // workspace holds them (fused_forward: unless gemm_variant 12)
-    bool pack_pairs;  // the packed weights hold W_o's pair tiles (a function of the encoder and config only:
-                      // one inference pack serves every graph)
-    int nblk;
+// WdConfig.gemm_variant (wdmpnn.h WdVariant), decoded once (decode_variant; Dims.V)
+struct Variant {
+    bool f32;         // WD_VARIANT_F32: f32-MFMA GEMMs (gemm_nt16_kernel) on the unblocked path
+    bool one_launch;  // QM9-sized blocks may take the one-launch forward (none of FOUR_LAUNCH, STAGED, PAIRS, debug)
+    bool staged;      // register-staged layers forced (WD_VARIANT_STAGED; debug 12b, and any other debug a but 1)
+    bool pairs;       // pair layers forced, also for QM9-sized blocks (WD_VARIANT_PAIRS; debug 11b)
+    bool pair_tiles;  // the pack and the workspace may hold pair tiles (all but F32 and STAGED: debug 12b too)
+    int stop;         // debug: the fused forward returns after this stage (1 embed, 1 + t layer t); 0 none
+    bool wo_dump;     // debug: the W_o pre-activation into the free second ping-pong buffer (depth 3)
 };
+Variant decode_variant(int v) {
+    const bool dbg = v >= WD_VARIANT_DEBUG;
+    Variant V{};
+    V.f32 = v == WD_VARIANT_F32;
+    V.pairs = dbg ? (v / 10) % 10 == WD_DEBUG_PAIRS : v == WD_VARIANT_PAIRS;
+    V.staged = dbg ? !V.pairs : v == WD_VARIANT_STAGED;
+    V.one_launch = !V.staged && !V.pairs && v != WD_VARIANT_FOUR_LAUNCH;
+    V.pair_tiles = v != WD_VARIANT_F32 && v != WD_VARIANT_STAGED;
+    V.stop = dbg ? v % 10 : 0;
+    V.wo_dump = dbg && v % 10 == WD_DEBUG_WO_DUMP;
+    return V;
+}
 
-// WdConfig.gemm_variant values that run the fused forward's layers on fp16 pair operands where the layout
-// allows (all but 9, the f32-MFMA A/B, and 12, the register-staged layers)
-inline bool pair_variant(int v) { return v != 9 && v != 12; }
 #ifndef WD_EMBED_PAIR_BN
 #define WD_EMBED_PAIR_BN 32
 #endif
 constexpr int EPB = WD_EMBED_PAIR_BN;  // the pair path's embed tile width (a multiple of 16 dividing every Hk: 32, 64)
+// 40-column tiles for the embed when they divide Hk: twice the workgroups of the layer tiling (two per
+// CU at the benchmark size, 37 KB of LDS each), so one's staging overlaps the other's sums
+#ifndef WD_EMBED40
+#define WD_EMBED40 1
+#endif
+
+struct Dims {
+    int H, Hk, T, R, Rp, Va, Vap, B, Fa, Fak, Fb, Fbk, d, dk, Hd, Hdk, Kin, Kink;
+    int ldx, Ko, Kd;
+    bool atom, undirected, save, desc;
+    Variant V;
+    bool x6;   // plane-tile pipeline: gathers emit bf16x3 plane tiles, GEMMs run gemm_x6g_kernel
+    bool codes;    // categorical codes (compact graphs): the input layer and the f_atoms half of W_o as sums of
+                   // weight columns instead of GEMMs over the one-hot rows (fused_mp.hpp embed_kernel)
+    bool blocked;  // molecule-blocked fused inference forward (fused_mp.hpp)
+    bool small;    // ... as ONE launch, a workgroup per block (small_fwd.hpp: blocks <= 32 rows, Hk 320)
+    bool pairs;    // ... the workspace holds M_t as fp16 pair tiles (LDS-DMA layer operands)
+    bool lay_pairs;   // ... and this call's layers hand M_t on in them (pairs, unless V.staged: debug stops)
+    bool wo_pairs;    // ... and W_o + readout reads A as pair tiles the last layer wrote (else bf16x3 planes)
+    bool pack_pairs;  // the packed weights hold W_o's pair tiles (a function of the encoder and config only:
+                      // one inference pack serves every graph)
+    int bn;  // fused column tile: 80 when it divides Hk (Hk 320: 4 tiles, a workgroup per CU at the benchmark size), else 64
+    int ebn, etiles;  // the embed's tile width and count: EPB on the pair path, else 40 when it divides Hk, else bn
+    int nblk;
+};
+
+// the padded sizes (H .. Kd) from plain numbers: a graph's (get_dims) or a feed's bounds (feed_batch_workspace)
+void fill_sizes(Dims &D, int hidden, int depth, int n_atoms, int n_bonds, int atom_fdim, int bond_fdim, int desc_dim,
+                bool atom) {
+    D.H = hidden; D.Hk = rup(D.H, 64); D.T = depth; D.atom = atom;
+    D.Va = n_atoms; D.Vap = rup(D.Va, 128);
+    D.R = D.atom ? n_atoms : n_bonds; D.Rp = rup(D.R, 128);
+    D.Fa = atom_fdim; D.Fak = rup(D.Fa, 32); D.Fb = bond_fdim; D.Fbk = rup(D.Fb, 32);
+    D.desc = desc_dim > 0; D.d = desc_dim; D.dk = rup(D.d, 32);
+    D.Hd = D.H + D.d; D.Hdk = rup(D.Hd, 64);
+    D.Kin = D.atom ? D.Fa : D.Fb; D.Kink = D.atom ? D.Fak : D.Fbk;
+    D.ldx = D.atom ? D.Hk + D.Fbk : D.Hk;
+    D.Ko = D.Fak + D.Hk;
+    D.Kd = D.Hk + D.dk;
+}
 
 int get_dims(const WdGraph *g, const WdParams *p, const WdConfig *c, Dims &D) {
     if (!g || !p || !c) return fail(WD_ERR_ARG, "null graph/params/config");
@@ -153,56 +198,51 @@ int get_dims(const WdGraph *g, const WdParams *p, const WdConfig *c, Dims &D) {
     if (c->aggregation < 0 || c->aggregation > WD_AGG_NORM) return fail(WD_ERR_ARG, "bad aggregation %d", c->aggregation);
     if (c->activation == WD_ACT_PRELU && !p->prelu) return fail(WD_ERR_ARG, "PReLU needs a slope pointer");
     if (!(c->dropout >= 0.f && c->dropout < 1.f)) return fail(WD_ERR_ARG, "dropout must be in [0, 1)");
-    D.H = p->hidden; D.Hk = rup(D.H, 64); D.T = c->depth;
-    D.atom = g->atom_messages != 0; D.undirected = c->undirected != 0; D.save = c->save_for_backward != 0;
-    D.Va = g->n_atoms; D.Vap = rup(D.Va, 128); D.B = g->n_mols;
-    D.R = D.atom ? g->n_atoms : g->n_bonds; D.Rp = rup(D.R, 128);
-    D.Fa = g->atom_fdim; D.Fak = rup(D.Fa, 32); D.Fb = g->bond_fdim; D.Fbk = rup(D.Fb, 32);
-    D.desc = g->atom_desc != nullptr && g->desc_dim > 0;
-    D.d = D.desc ? g->desc_dim : 0; D.dk = rup(D.d, 32);
-    D.Hd = D.H + D.d; D.Hdk = rup(D.Hd, 64);
-    D.Kin = D.atom ? D.Fa : D.Fb; D.Kink = D.atom ? D.Fak : D.Fbk;
-    D.ldx = D.atom ? D.Hk + D.Fbk : D.Hk;
-    D.Ko = D.Fak + D.Hk;
-    D.Kd = D.Hk + D.dk;
-    // default (0) = 10: bf16x6 split-plane GEMMs (fp32-accurate)
-    D.f32 = c->gemm_variant == 9;
-    D.x6 = !D.f32 && !D.atom;
+    const Variant V = D.V = decode_variant(c->gemm_variant);
+    fill_sizes(D, p->hidden, c->depth, g->n_atoms, g->n_bonds, g->atom_fdim, g->bond_fdim,
+               g->atom_desc != nullptr && g->desc_dim > 0 ? g->desc_dim : 0, g->atom_messages != 0);
+    D.undirected = c->undirected != 0; D.save = c->save_for_backward != 0; D.B = g->n_mols;
+    // default: bf16x6 split-plane GEMMs (fp32-accurate)
+    D.x6 = !V.f32 && !D.atom;
+    D.bn = D.Hk % 80 == 0 ? 80 : 64;
     // molecule-blocked fused forward, also for training (the fused kernels then save Z_t, A and Zo in
     // natural rows for the backward)
     // (an embed-capable graph -- categorical codes -- needs no feature planes)
-    const bool codes = g->atom_codes && g->bond_src_blk && g->bond_tail && D.Fb <= WO_MAXK && D.Fa <= WO_MAXK;
+    D.codes = g->atom_codes && g->bond_src_blk && g->bond_tail && D.Fb <= WO_MAXK && D.Fa <= WO_MAXK;
     // (any Hk: a consumer folds its block's h2 scale words 64 at a time, planes.hpp lane_word)
     const bool blk_common = !D.desc && D.T >= 2 && g->n_blocks > 0 && g->blocks &&
                             g->atom_ell_idx && g->atom_ell_coef;
     // atom-message mode (inference): the a2a gather's pad slots read atom 0, whose message is act(b_i) and
     // later act(b_i + W_h(...)) -- zero without biases, so the block-local lists drop them; with biases,
     // or for training, the unblocked path runs
-    const bool atom_blk = D.atom && !D.f32 && !D.save && !D.undirected && !p->b_i && !p->b_h &&
-                          g->f_atoms_x6 &&
-                          g->f_atoms_blk_x6 && g->bond_feat_gather.ptr && g->msg_ell_idx && g->msg_ell_coef &&
+    const bool atom_blk = D.atom && !V.f32 && !D.save && !D.undirected && !p->b_i && !p->b_h &&
+                          g->f_atoms_x6 && g->f_atoms_blk_x6 && g->bond_feat_gather.ptr && g->msg_ell_idx && g->msg_ell_coef &&
                           g->msg_gather.ptr && D.Fbk == 32;
-    D.blocked = blk_common && (atom_blk || (D.x6 && g->bond_blk_row && (codes || (g->f_atoms_blk_x6 && g->f_bonds_x6)) &&
+    D.blocked = blk_common && (atom_blk || (D.x6 && g->bond_blk_row && (D.codes || (g->f_atoms_blk_x6 && g->f_bonds_x6)) &&
                                             g->bond_src_blk && g->b2revb));
     D.nblk = D.blocked ? g->n_blocks : 0;
-    // QM9-sized blocks, inference: the one-launch forward (WdConfig.gemm_variant 11 / 12 / 13 keep the four launches)
-    D.small = D.blocked && codes && !D.atom && !D.save && c->dropout == 0.f && D.Hk == SF_HK && !D.undirected &&
-              c->gemm_variant != 11 && c->gemm_variant != 12 && c->gemm_variant != 13 && c->gemm_variant < 100 &&
-              g->blk_max_bonds > 0 && g->blk_max_bonds <= SF_ROWS &&
-              g->blk_max_atoms <= SF_ATOMS && D.Fa <= WO_MAXK && D.Fb <= WO_MAXK && D.Fb - D.Fa <= SF_ROWS;
+    // QM9-sized blocks, inference: the one-launch forward
+    D.small = D.blocked && D.codes && !D.atom && !D.save && c->dropout == 0.f && D.Hk == SF_HK && !D.undirected &&
+              V.one_launch && g->blk_max_bonds > 0 && g->blk_max_bonds <= SF_ROWS && g->blk_max_atoms <= SF_ATOMS &&
+              D.Fa <= WO_MAXK && D.Fb <= WO_MAXK && D.Fb - D.Fa <= SF_ROWS;
     // inference through the embed (codes), bond messages, 80-column layer tiles, <= 64 embed words per block:
-    // the layers read M_{t-1} as fp16 pair tiles written by its producer (fused_mp.hpp PAIRS; WdConfig.gemm_variant
-    // 12 keeps the register-staged layers that read Z_t, 13 the pair layers also for QM9-sized blocks)
-    D.pack_pairs = !D.atom && !D.save && D.Hk % 80 == 0 && D.Hk / 32 <= 64 && pair_variant(c->gemm_variant);
-    // (debug variants 1ab: a = 1 pair layers / 2 register-staged layers, the fused forward stopped after stage
-    // b = 1 embed, 2 first layer, ...: intermediate buffers left for tools/debug_pairs.py)
-    D.pairs = D.pack_pairs && D.blocked && codes;
+    // the layers read M_{t-1} as fp16 pair tiles written by its producer (fused_mp.hpp PAIRS; DESIGN.md §4 "Pair
+    // operands") wherever the layout allows: round 6, one box, 190.1 vs 178.8 M edges/s three batches in flight,
+    // 121.2 vs 118.1 M one, 203.0 vs 175.0 M forward_many(4) (profiles/round6_pairs_default_ab.txt)
+    D.pack_pairs = !D.atom && !D.save && D.bn == 80 && D.Hk / 32 <= 64 && V.pair_tiles;
+    D.pairs = D.pack_pairs && D.blocked && D.codes;
+    D.lay_pairs = D.pairs && !V.staged;
+    D.wo_pairs = D.lay_pairs && WD_WO_PAIRS;
+    // (the pair path: EPB-column embed tiles, one scale word per tile of M_0; measured, same box: 64-column
+    // tiles -- 320 workgroups, one round at B = 64 -- 11.29 vs 9.63 us for 32, 186.5 vs 194.0 M edges/s)
+    D.ebn = D.lay_pairs ? EPB : (WD_EMBED40 && D.Hk % 40 == 0 ? 40 : D.bn);
+    D.etiles = D.Hk / D.ebn;
     if (D.atom && D.undirected)
         return fail(WD_ERR_UNSUPPORTED, "undirected with atom_messages (the reference indexes atom messages "
                                         "with b2revb, mpn.py:101-102)");
     // (a lean graph has neither table; two distinct arrays of a real graph cannot both sit at address 0 --
     // host-only tests pass buffer offsets as pointers)
-    if (!g->f_atoms && !g->f_bonds && !(D.blocked && codes && !D.save))
+    if (!g->f_atoms && !g->f_bonds && !(D.blocked && D.codes && !D.save))
         return fail(WD_ERR_UNSUPPORTED, "graph built without feature rows (WDMPNN_GRAPH_LEAN): only the fused "
                                         "inference forward runs on it");
     if (D.desc && (!p->W_d || !p->b_d)) return fail(WD_ERR_ARG, "atom descriptors need W_d and b_d");
@@ -221,10 +261,10 @@ int get_dims(const WdGraph *g, const WdParams *p, const WdConfig *c, Dims &D) {
 struct PackLayout {
     size_t Wi = 0, bi = 0, Wh = 0, bh = 0, Wo = 0, bo = 0, Wd = 0, bd = 0, WhT = 0, WoT = 0, WdT = 0, total = 0;
     size_t WiX = 0, WhX = 0, WoX = 0;  // bf16x3 plane tiles (64-row blocks) of W_i / W_h / W_o
-    size_t WhX80 = 0, WoX80 = 0;       // the same with 80-row blocks (fused forward, Hk % 80 == 0)
+    size_t WhX80 = 0, WoX80 = 0;       // the same with 80-row blocks (fused forward, D.bn == 80)
     size_t WiT = 0, WoaT = 0;          // W_i^T [Kink][Hk] and W_o[:, :Fa]^T [Fak][Hk]: weight columns as rows
                                        // (the categorical-code embedding of the fused forward)
-    size_t WhH = 0;                    // h2 plane tiles of W_h (fused layers; BN-row blocks, BN = fused_bn)
+    size_t WhH = 0;                    // h2 plane tiles of W_h (fused layers; BN-row blocks, BN = D.bn)
     size_t amax = 0;                   // W_h's h2 scale: pack_kernel's 64 per-workgroup maxima + their max (u32)
     // atom-message mode: the fused forward's input GEMM [f_atoms | Fs] B^T with B [3 Hk][Fak + Fbk] =
     // [[W_i, 0], [W_i, W_h[:, H:]], [W_o[:, :Fa], 0]] -> inp | inp + Fs W_h[:, H:]^T | f_atoms W_o[:, :Fa]^T
@@ -233,10 +273,6 @@ struct PackLayout {
     // 80-row blocks (wo_readout_kernel<..., PAIRS>'s B) and its scale: pack_kernel's 64 maxima + their max
     size_t WoH = 0, wo_amax = 0;
 };
-
-// column tile of the fused kernels: 80 when it divides Hk (Hk = 320: 4 tiles, one workgroup per CU at the
-// benchmark size), else 64
-int fused_bn(int Hk) { return Hk % 80 == 0 ? 80 : 64; }
 
 PackLayout pack_layout(const Dims &D) {
     PackLayout L;
@@ -255,7 +291,7 @@ PackLayout pack_layout(const Dims &D) {
     L.WiX = take((size_t)D.Hk * D.Kink * 3 / 2);  // 3 bf16 planes = 1.5 floats per value
     L.WhX = take((size_t)D.Hk * D.ldx * 3 / 2);
     L.WoX = take((size_t)D.Hk * D.Ko * 3 / 2);
-    if (D.Hk % 80 == 0) {
+    if (D.bn == 80) {
         L.WhX80 = take((size_t)D.Hk * D.ldx * 3 / 2);
         L.WoX80 = take((size_t)D.Hk * D.Ko * 3 / 2);
     }
@@ -348,7 +384,7 @@ int pack_params(const Dims &D, const WdParams *p, char *base, hipStream_t st) {
     split(L.Wi, L.WiX, D.Kink, 64);
     split(L.Wh, L.WhX, D.ldx, 64);
     split(L.Wo, L.WoX, D.Ko, 64);
-    if (D.Hk % 80 == 0) {
+    if (D.bn == 80) {
         split(L.Wh, L.WhX80, D.ldx, 80);
         split(L.Wo, L.WoX80, D.Ko, 80);
     }
@@ -362,7 +398,7 @@ int pack_params(const Dims &D, const WdParams *p, char *base, hipStream_t st) {
     WD_CHECK_LAUNCH("pack_params planes");
     // fp16 hi / lo tiles of W_h[:, :Hk] for the fused layers, scaled by its published maximum
     hipLaunchKernelGGL(split_h2_kernel, dim3(ew_blocks((size_t)D.Hk * D.Hk / 8)), dim3(256), 0, st, (const float *)F(L.Wh),
-                       D.ldx, D.Hk, D.Hk, fused_bn(D.Hk), (uint8_t *)(base + L.WhH), wh_amax, 64, wh_amax + 64);
+                       D.ldx, D.Hk, D.Hk, D.bn, (uint8_t *)(base + L.WhH), wh_amax, 64, wh_amax + 64);
     WD_CHECK_LAUNCH("pack_params h2");
     if (D.pack_pairs) {  // W_o[:, Fa:] (columns Fak.. of the padded copy) as fp16 pair tiles, 80-row blocks
         hipLaunchKernelGGL(split_h2_kernel, dim3(ew_blocks((size_t)D.Hk * D.Hk / 8)), dim3(256), 0, st,
@@ -858,12 +894,9 @@ struct FusedJob {
     float *out;
 };
 
-bool fused_codes(const WdGraph *g, const Dims &D) {
-    return g->atom_codes && g->bond_src_blk && g->bond_tail && D.Fb <= WO_MAXK && D.Fa <= WO_MAXK;
-}
-
+// fills M with the jobs' parameters and tile ranges; returns the grid (all their tiles)
 template <typename T, typename Fill>
-int launch_multi(const FusedJob *jobs, int n, int tiles_per_blk, Fill &&fill, Multi<T> &M, int &grid) {
+int launch_multi(const FusedJob *jobs, int n, int tiles_per_blk, Fill &&fill, Multi<T> &M) {
     M = Multi<T>{};
     M.n = n;
     int t = 0;
@@ -873,8 +906,7 @@ int launch_multi(const FusedJob *jobs, int n, int tiles_per_blk, Fill &&fill, Mu
         t += jobs[j].D.nblk * tiles_per_blk;
     }
     for (int j = n; j <= WD_MULTI; ++j) M.t0[j] = t;
-    grid = t;
-    return 0;
+    return t;
 }
 // the one-batch form of a filled Multi (a launch's host cost grows with its kernel-argument bytes)
 template <typename T>
@@ -883,6 +915,214 @@ Multi<T, 1> one_job(const Multi<T> &M) {
     o.p[0] = M.p[0]; o.t0[0] = M.t0[0]; o.t0[1] = M.t0[1]; o.n = 1;
     return o;
 }
+// launch(kernel argument, its batches-per-launch constant): one batch takes the one-batch form
+template <typename T, typename Launch>
+void with_jobs(int n, const Multi<T> &M, Launch &&launch) {
+    if (n == 1) launch(one_job(M), std::integral_constant<int, 1>{});
+    else launch(M, std::integral_constant<int, WD_MULTI>{});
+}
+
+// what the stages of one fused forward share (D0: the layout facts every job agrees in, fused_forward)
+struct FusedCtx {
+    const FusedJob *jobs;
+    int n;
+    const WdParams *p;
+    const WdConfig *c;
+    const PackLayout &PL;
+    const char *pk;
+    hipStream_t st;
+    const Dims &D0;
+    int Hk, BN;  // (D0.Hk, D0.bn)
+    const float *W(size_t off) const { return (const float *)(pk + off); }
+    static float *F(const FusedJob &J, size_t off) { return (float *)(J.ws + off); }
+    // h2 scale words of M_t (written by the embed for t = 0, by layer t after): [nblk][tiles of the producer]
+    static uint32_t *slot(const FusedJob &J, int t) { return (uint32_t *)(J.ws + J.L.amax[t & 1]); }
+};
+
+// inp (and M_0's scale words): the embed of the categorical codes, else the W_i GEMM on plane tiles
+int fused_input(const FusedCtx &X) {
+    const Dims &D0 = X.D0;
+    const PackLayout &PL = X.PL;
+    const int Hk = X.Hk;
+    if (D0.codes) {
+        Multi<EmbedP> M;
+        const int grid = launch_multi(X.jobs, X.n, D0.etiles, [&](EmbedP &E, const FusedJob &J) {
+            const WdGraph *g = J.g;
+            E.codes = g->atom_codes; E.src_blk = g->bond_src_blk; E.tail = g->bond_tail;
+            E.wt = X.W(PL.WiT); E.woat = X.W(PL.WoaT); E.eo = X.F(J, J.L.Eo); E.bias = X.p->b_i ? X.W(PL.bi) : nullptr;
+            E.blocks = g->blocks;
+            E.Fa = J.D.Fa; E.Fb = J.D.Fb; E.Hk = Hk; E.n_tiles = D0.etiles;
+            E.inp = X.F(J, J.L.Z[0]);
+            E.slope = X.p->prelu; E.amax = X.slot(J, 0);
+            E.m0 = D0.lay_pairs ? (uint8_t *)(J.ws + J.L.Mp[0]) : nullptr;
+        }, M);
+        host_with_act(X.c->activation, [&](auto act_c) {
+            constexpr int A = decltype(act_c)::value;
+            with_jobs(X.n, M, [&](const auto &Mn, auto nj) {
+                constexpr int NJ = decltype(nj)::value;
+                if (D0.lay_pairs) hipLaunchKernelGGL((embed_kernel<EPB, A, NJ, true>), dim3(grid), dim3(512), 0, X.st, Mn);
+                else if (D0.ebn == 40) hipLaunchKernelGGL((embed_kernel<40, A, NJ>), dim3(grid), dim3(512), 0, X.st, Mn);
+                else if (D0.ebn == 80) hipLaunchKernelGGL((embed_kernel<80, A, NJ>), dim3(grid), dim3(512), 0, X.st, Mn);
+                else hipLaunchKernelGGL((embed_kernel<64, A, NJ>), dim3(grid), dim3(512), 0, X.st, Mn);
+            });
+        });
+        WD_CHECK_LAUNCH("embed");
+        return 0;
+    }
+    for (int j = 0; j < X.n; ++j) {
+        const FusedJob &J = X.jobs[j];
+        if (J.D.atom) {
+            // atom messages: per atom Fs = the sum of its in-bonds' feature rows (mpn.py:105-107, as plane
+            // tiles), then ONE GEMM [f_atoms | Fs] [[W_i, 0], [W_i, W_h[:, H:]], [W_o[:, :Fa], 0]]^T ->
+            // inp (mpn.py:93) | inp + Fs W_h[:, H:]^T (every layer's residual: the bond-feature half of
+            // W_h is the same in each layer) | f_atoms W_o[:, :Fa]^T (the f_atoms half of W_o), whose
+            // epilogue also publishes the first layer's h2 scale words per 64 x 64 tile of inp
+            const void *fs = J.g->atom_feat_sum_x6;  // (built with the graph, or gathered here)
+            int kpf = J.g->ld_bonds;
+            if (!fs) {
+                kpf = J.D.Fbk;
+                WD_TRY(gather8(J.g->f_bonds, J.g->ld_bonds, J.D.Fbk, J.g->bond_feat_gather, nullptr, nullptr, 0,
+                               J.ws + J.L.Fs, J.D.Fbk, 0, J.D.R, J.D.Rp, X.st));
+                fs = J.ws + J.L.Fs;
+            }
+            Epi e = epi_act(ACT_IDENTITY, nullptr, nullptr, nullptr, nullptr, X.F(J, J.L.In3), 3 * Hk, X.c, 0);
+            e.amax = X.slot(J, 0); e.amax_cols = Hk; e.amax_act = X.c->activation; e.slope = X.p->prelu;
+            if (!x6g_eligible(e)) return fail(WD_ERR_SHAPE, "fused forward: unaligned buffers");
+            WD_TRY(gemm_x6g(J.g->f_atoms_x6, J.g->ld_atoms, J.D.Fak, fs, kpf, J.D.Fbk, X.pk + PL.WiAX,
+                            J.D.Rp, 3 * Hk, e, X.st));
+            continue;
+        }
+        // inp only: the first layer stages M_0 = act(inp) itself
+        Epi e = epi_act(ACT_IDENTITY, nullptr, X.W(PL.bi), nullptr, X.F(J, J.L.Z[0]), nullptr, Hk, X.c, 0);
+        if (!x6g_eligible(e)) return fail(WD_ERR_SHAPE, "fused forward: unaligned buffers");
+        WD_TRY(gemm_x6g(J.g->f_bonds_x6, J.g->ld_bonds, J.D.Kink, nullptr, 0, 0, X.pk + PL.WiX, J.D.Rp, Hk, e, X.st));
+        host_with_act(X.c->activation, [&](auto act_c) {
+            hipLaunchKernelGGL(absmax_blocks_kernel<decltype(act_c)::value>, dim3(J.D.nblk), dim3(256), 0, X.st,
+                               (const float *)X.F(J, J.L.Z[0]), Hk, Hk, J.g->blocks, X.p->prelu, X.slot(J, 0), 0);
+        });
+        WD_CHECK_LAUNCH("absmax");
+    }
+    return 0;
+}
+
+// message layer t (1 .. T-1): M_t = act(inp + gather(M_{t-1}) W_h^T (+ b_h)); the last one sums A instead
+int fused_layer(const FusedCtx &X, int t) {
+    const Dims &D0 = X.D0;
+    const PackLayout &PL = X.PL;
+    const int Hk = X.Hk, BN = X.BN;
+    const bool last = t == D0.T - 1, pairs = D0.lay_pairs;
+    Multi<MpLayerP> M;
+    const int grid = launch_multi(X.jobs, X.n, Hk / BN, [&](MpLayerP &Q, const FusedJob &J) {
+        const WdGraph *g = J.g;
+        // Z_{t-1} in, Z_t out (the last layer: none): a training forward keeps every Z_t (L.Z), inference
+        // ping-pongs two buffers after inp
+        auto zbuf = [&](int k) { return k == 0 || J.D.save ? X.F(J, J.L.Z[k]) : X.F(J, J.L.Zb[k & 1]); };
+        const bool a3 = J.D.atom && t == 1;  // (the atom-message input GEMM's inp columns)
+        Q.zin = a3 ? X.F(J, J.L.In3) : zbuf(t - 1);
+        Q.ldz = a3 ? 3 * Hk : Hk;
+        Q.amax_in = X.slot(J, t - 1);
+        Q.amax_in_n = t > 1 ? Hk / BN : (D0.codes ? D0.etiles : (J.D.atom ? Hk / 64 : 1));
+        Q.amax_rt = a3 ? 64 : 0;
+        Q.p_drop_in = t - 1 == 0 ? 0.f : X.c->dropout;
+        Q.zout = last ? nullptr : zbuf(t);
+        Q.amax_out = last ? nullptr : X.slot(J, t);
+        Q.kp = Hk;
+        Q.wh = (const uint8_t *)(X.pk + PL.WhH); Q.wh_amax = (const uint32_t *)(X.pk + PL.amax) + 64;
+        Q.inp = J.D.atom ? X.F(J, J.L.In3) + Hk : X.F(J, J.L.Z[0]);
+        Q.ldr = J.D.atom ? 3 * Hk : Hk;
+        Q.bias = X.p->b_h ? X.W(PL.bh) : nullptr;
+        Q.mell_idx = g->msg_ell_idx; Q.mell_coef = g->msg_ell_coef;
+        Q.mptr = g->msg_gather.ptr; Q.midx = g->msg_gather.idx; Q.mcoef = g->msg_gather.coef;
+        Q.blocks = g->blocks;
+        Q.rev = g->b2revb; Q.src_blk = g->bond_src_blk; Q.undirected = J.D.undirected;
+        Q.act = X.c->activation; Q.slope = X.p->prelu; Q.p_drop = X.c->dropout; Q.seed = X.c->seed; Q.layer = t;
+        Q.aptr = g->atom_gather.ptr; Q.aidx = g->atom_gather.idx; Q.acoef = g->atom_gather.coef;
+        Q.aell_idx = g->atom_ell_idx; Q.aell_coef = g->atom_ell_coef;
+        Q.aplanes = (uint8_t *)(J.ws + J.L.Ab);
+        Q.n_tiles = Hk / BN;
+        Q.zsave = J.D.save && last ? X.F(J, J.L.Z[t]) : nullptr;
+        Q.asave = J.D.save && last ? X.F(J, J.L.A) : nullptr;
+        if (pairs) {  // M_{t-1} from the pair tiles of its producer (no Z_t in inference)
+            Q.ain = (const uint8_t *)(J.ws + J.L.Mp[(t - 1) & 1]);
+            Q.ain_g = t == 1 ? D0.ebn : BN;
+            Q.aout = last ? nullptr : (uint8_t *)(J.ws + J.L.Mp[t & 1]);
+            Q.zin = nullptr;
+            Q.zout = nullptr;
+            // the last layer: A as pair tiles (D.wo_pairs), its words in the slot this layer does not read; else
+            // bf16x3 plane tiles
+            Q.apairs = last && D0.wo_pairs ? (uint8_t *)(J.ws + J.L.Ab) : nullptr;
+            Q.amax_out = X.slot(J, t);
+        }
+    }, M);
+    // one instantiation per (tile width, last layer, activation, batches per launch)
+    auto go = [&](auto bn_c, auto last_c) {
+        constexpr int BNc = decltype(bn_c)::value;
+        constexpr bool LAST = decltype(last_c)::value;
+        host_with_act(X.c->activation, [&](auto act_c) {
+            constexpr int A = decltype(act_c)::value;
+            if (D0.atom)  // (the atom-row layer kernel: one batch per launch only, fused_forward)
+                hipLaunchKernelGGL((mp_layer_kernel<BNc, LAST, A, true, 1>), dim3(grid), dim3(MP_THREADS), 0, X.st, one_job(M));
+            else with_jobs(X.n, M, [&](const auto &Mn, auto nj) {
+                constexpr int NJ = decltype(nj)::value;
+                if (BNc != 80 || !pairs)
+                    hipLaunchKernelGGL((mp_layer_kernel<BNc, LAST, A, false, NJ>), dim3(grid), dim3(MP_THREADS), 0, X.st, Mn);
+                else if constexpr (BNc == 80)  // (the pair layers: 80-column tiles only)
+                    hipLaunchKernelGGL((mp_layer_kernel<BNc, LAST, A, false, NJ, true>), dim3(grid), dim3(MP_THREADS), 0, X.st, Mn);
+            });
+        });
+    };
+    using I80 = std::integral_constant<int, 80>;
+    using I64 = std::integral_constant<int, 64>;
+    if (BN == 80) { if (last) go(I80{}, std::true_type{}); else go(I80{}, std::false_type{}); }
+    else { if (last) go(I64{}, std::true_type{}); else go(I64{}, std::false_type{}); }
+    WD_CHECK_LAUNCH("mp_layer");
+    return 0;
+}
+
+// W_o + readout (empty batches -- no molecules -- have no blocks and write nothing)
+int fused_wo_readout(const FusedCtx &X) {
+    const Dims &D0 = X.D0;
+    const PackLayout &PL = X.PL;
+    const int Hk = X.Hk, BN = X.BN;
+    Multi<WoReadoutP> M;
+    const int grid = launch_multi(X.jobs, X.n, Hk / BN, [&](WoReadoutP &R, const FusedJob &J) {
+        const WdGraph *g = J.g;
+        // (codes: the f_atoms segment is not read; a lean graph has no planes -- the A planes stand in as the
+        // segment's non-null base)
+        R.fa = g->f_atoms_blk_x6 ? (const uint8_t *)g->f_atoms_blk_x6 : (const uint8_t *)(J.ws + J.L.Ab);
+        R.kpa = g->ld_atoms; R.kcw = J.D.Fak / 32;
+        R.kca = D0.codes || J.D.atom ? 0 : R.kcw;
+        R.eo = D0.codes ? X.F(J, J.L.Eo) : (J.D.atom ? X.F(J, J.L.In3) + 2 * Hk : nullptr); R.Hk = Hk;
+        R.ldeo = J.D.atom ? 3 * Hk : Hk;
+        R.ag = (const uint8_t *)(J.ws + J.L.Ab); R.kp = Hk;
+        R.wo = (const uint8_t *)(X.pk + (BN == 80 ? PL.WoX80 : PL.WoX)); R.bias = X.W(PL.bo);
+        R.blocks = g->blocks;
+        R.w_atoms = g->w_atoms; R.mol_start = g->mol_start; R.mol_size = g->mol_size; R.xn = g->degree_of_polym;
+        R.agg = X.c->aggregation; R.norm = X.c->aggregation_norm; R.zero_vec = X.p->zero_vec;
+        R.act = X.c->activation; R.slope = X.p->prelu; R.p_drop = X.c->dropout; R.seed = X.c->seed; R.layer = J.D.T;
+        R.out = J.out; R.ncols = J.D.H; R.n_tiles = Hk / BN;
+        R.zosave = J.D.save ? X.F(J, J.L.Zo) : nullptr;
+        if (D0.V.wo_dump && J.D.T == 3)  // (tools/debug_pairs.py)
+            R.zosave = D0.lay_pairs ? X.F(J, J.L.Mp[1]) : X.F(J, J.L.Zb[1]);
+        if (D0.wo_pairs) {
+            R.apairs = (const uint8_t *)(J.ws + J.L.Ab); R.a_amax = X.slot(J, J.D.T - 1); R.a_nw = Hk / BN; R.a_g = BN;
+            R.woh = (const uint8_t *)(X.pk + PL.WoH); R.wo_amax = (const uint32_t *)(X.pk + PL.wo_amax) + 64;
+        }
+    }, M);
+    if (grid <= 0) return 0;
+    with_jobs(X.n, M, [&](const auto &Mn, auto nj) {
+        constexpr int NJ = decltype(nj)::value;
+        // one batch: single-chunk stages (55 KB, co-resident with other streams' layers); several: two
+        if (D0.wo_pairs)
+            hipLaunchKernelGGL((wo_readout_kernel<80, 1, NJ, true>), dim3(grid), dim3(512), 0, X.st, Mn);
+        else if (BN == 80)
+            hipLaunchKernelGGL((wo_readout_kernel<80, NJ == 1 ? 1 : 2, NJ>), dim3(grid), dim3(64 * WoWaves<80>::WM * WoWaves<80>::WN), 0, X.st, Mn);
+        else
+            hipLaunchKernelGGL((wo_readout_kernel<64, 1, NJ>), dim3(grid), dim3(64 * WoWaves<64>::WM * WoWaves<64>::WN), 0, X.st, Mn);
+    });
+    WD_CHECK_LAUNCH("wo_readout");
+    return 0;
+}
 
 int fused_forward(const FusedJob *jobs, int n, const WdParams *p, const WdConfig *c, const PackLayout &PL,
                   const char *pk, hipStream_t st) {
@@ -890,230 +1130,23 @@ int fused_forward(const FusedJob *jobs, int n, const WdParams *p, const WdConfig
     const Dims &D0 = jobs[0].D;
     if (D0.atom && n > 1)  // (the atom-row layer kernel is instantiated for one batch per launch only)
         return fail(WD_ERR_UNSUPPORTED, "fused forward: atom messages run one batch per launch");
-    auto W = [&](size_t off) { return (const float *)(pk + off); };
-    auto F = [](const FusedJob &J, size_t off) { return (float *)(J.ws + off); };
-    const int Hk = D0.Hk;
-    // 80-column tiles when they divide Hk (Hk = 320: 4 tiles, one workgroup per CU at the benchmark
-    // size), else 64
-    const bool bn80 = Hk % 80 == 0;
-    const int BNf = bn80 ? 80 : 64;
-    // categorical codes (compact graphs): the input layer and the f_atoms half of W_o as sums of weight
-    // columns instead of GEMMs over the one-hot rows (fused_mp.hpp embed_kernel)
-    const bool codes = fused_codes(jobs[0].g, D0);
-    for (int j = 1; j < n; ++j)
-        if (fused_codes(jobs[j].g, jobs[j].D) != codes || jobs[j].D.Hk != Hk || jobs[j].D.T != D0.T ||
-            jobs[j].D.atom != D0.atom ||
-            jobs[j].D.Fa != D0.Fa || jobs[j].D.Fb != D0.Fb || jobs[j].D.save != D0.save)
+    for (int j = 1; j < n; ++j) {
+        const Dims &D = jobs[j].D;
+        if (D.codes != D0.codes || D.Hk != D0.Hk || D.T != D0.T || D.atom != D0.atom || D.Fa != D0.Fa ||
+            D.Fb != D0.Fb || D.save != D0.save || D.pairs != D0.pairs)
             return fail(WD_ERR_UNSUPPORTED, "fused forward: batches of one launch differ in layout");
-    // h2 scale words of M_t (written by the embed for t = 0, by layer t after): [nblk][tiles of the producer]
-    auto slot = [&](const FusedJob &J, int t) { return (uint32_t *)(J.ws + J.L.amax[t & 1]); };
-    // 40-column tiles for the embed when they divide Hk: twice the workgroups of the layer tiling (two per
-    // CU at the benchmark size, 37 KB of LDS each), so one's staging overlaps the other's sums
-#ifndef WD_EMBED40
-#define WD_EMBED40 1
-#endif
-    // (the pair path: EPB-column embed tiles, one scale word per tile of M_0; measured, same box: 64-column
-    // tiles -- 320 workgroups, one round at B = 64 -- 11.29 vs 9.63 us for 32, 186.5 vs 194.0 M edges/s)
-    // The pair-operand layers (M_t as fp16 pair tiles, written by its producer and copied by LDS-DMA; DESIGN.md
-    // §4 "Pair operands") wherever the layout allows (D.pairs; gemm_variant 12 keeps the register-staged layers):
-    // round 6, one box, 190.1 vs 178.8 M edges/s three batches in flight, 121.2 vs 118.1 M one, 203.0 vs 175.0 M
-    // forward_many(4) (profiles/round6_pairs_default_ab.txt)
-    bool pairs = D0.pairs;
-    if (c->gemm_variant >= 100) pairs = D0.pairs && (c->gemm_variant / 10) % 10 == 1;  // (debug stops)
-    for (int j = 1; j < n; ++j)
-        if (jobs[j].D.pairs != D0.pairs) return fail(WD_ERR_UNSUPPORTED, "fused forward: batches of one launch differ in layout");
-    const bool bn40 = WD_EMBED40 && Hk % 40 == 0 && !pairs;
-    const int embed_tiles = Hk / (pairs ? EPB : (bn40 ? 40 : BNf));
-    if (codes) {
-        const int nt = embed_tiles;
-        Multi<EmbedP> M;
-        int grid;
-        launch_multi(jobs, n, nt, [&](EmbedP &E, const FusedJob &J) {
-            const WdGraph *g = J.g;
-            E.codes = g->atom_codes; E.src_blk = g->bond_src_blk; E.tail = g->bond_tail;
-            E.wt = W(PL.WiT); E.woat = W(PL.WoaT); E.eo = F(J, J.L.Eo); E.bias = p->b_i ? W(PL.bi) : nullptr;
-            E.blocks = g->blocks;
-            E.Fa = J.D.Fa; E.Fb = J.D.Fb; E.Hk = Hk; E.n_tiles = nt;
-            E.inp = F(J, J.L.Z[0]);
-            E.slope = p->prelu; E.amax = slot(J, 0);
-            E.m0 = pairs ? (uint8_t *)(J.ws + J.L.Mp[0]) : nullptr;
-        }, M, grid);
-        host_with_act(c->activation, [&](auto act_c) {
-            constexpr int A = decltype(act_c)::value;
-            if (pairs) {
-                if (n == 1) hipLaunchKernelGGL((embed_kernel<EPB, A, 1, true>), dim3(grid), dim3(512), 0, st, one_job(M));
-                else hipLaunchKernelGGL((embed_kernel<EPB, A, WD_MULTI, true>), dim3(grid), dim3(512), 0, st, M);
-            } else if (n == 1) {
-                const Multi<EmbedP, 1> M1 = one_job(M);
-                if (bn40) hipLaunchKernelGGL((embed_kernel<40, A, 1>), dim3(grid), dim3(512), 0, st, M1);
-                else if (bn80) hipLaunchKernelGGL((embed_kernel<80, A, 1>), dim3(grid), dim3(512), 0, st, M1);
-                else hipLaunchKernelGGL((embed_kernel<64, A, 1>), dim3(grid), dim3(512), 0, st, M1);
-            } else if (bn40) hipLaunchKernelGGL((embed_kernel<40, A>), dim3(grid), dim3(512), 0, st, M);
-            else if (bn80) hipLaunchKernelGGL((embed_kernel<80, A>), dim3(grid), dim3(512), 0, st, M);
-            else hipLaunchKernelGGL((embed_kernel<64, A>), dim3(grid), dim3(512), 0, st, M);
-        });
-        WD_CHECK_LAUNCH("embed");
-        if (c->gemm_variant >= 100 && c->gemm_variant % 10 == 1) return 0;
-    } else {
-        for (int j = 0; j < n; ++j) {
-            const FusedJob &J = jobs[j];
-            if (J.D.atom) {
-                // atom messages: per atom Fs = the sum of its in-bonds' feature rows (mpn.py:105-107, as plane
-                // tiles), then ONE GEMM [f_atoms | Fs] [[W_i, 0], [W_i, W_h[:, H:]], [W_o[:, :Fa], 0]]^T ->
-                // inp (mpn.py:93) | inp + Fs W_h[:, H:]^T (every layer's residual: the bond-feature half of
-                // W_h is the same in each layer) | f_atoms W_o[:, :Fa]^T (the f_atoms half of W_o), whose
-                // epilogue also publishes the first layer's h2 scale words per 64 x 64 tile of inp
-                const void *fs = J.g->atom_feat_sum_x6;  // (built with the graph, or gathered here)
-                int kpf = J.g->ld_bonds;
-                if (!fs) {
-                    kpf = J.D.Fbk;
-                    WD_TRY(gather8(J.g->f_bonds, J.g->ld_bonds, J.D.Fbk, J.g->bond_feat_gather, nullptr, nullptr, 0,
-                                   J.ws + J.L.Fs, J.D.Fbk, 0, J.D.R, J.D.Rp, st));
-                    fs = J.ws + J.L.Fs;
-                }
-                Epi e = epi_act(ACT_IDENTITY, nullptr, nullptr, nullptr, nullptr, F(J, J.L.In3), 3 * Hk, c, 0);
-                e.amax = slot(J, 0); e.amax_cols = Hk; e.amax_act = c->activation; e.slope = p->prelu;
-                if (!x6g_eligible(e)) return fail(WD_ERR_SHAPE, "fused forward: unaligned buffers");
-                WD_TRY(gemm_x6g(J.g->f_atoms_x6, J.g->ld_atoms, J.D.Fak, fs, kpf, J.D.Fbk, pk + PL.WiAX,
-                                J.D.Rp, 3 * Hk, e, st));
-                continue;
-            }
-            // inp only: the first layer stages M_0 = act(inp) itself
-            Epi e = epi_act(ACT_IDENTITY, nullptr, W(PL.bi), nullptr, F(J, J.L.Z[0]), nullptr, Hk, c, 0);
-            if (!x6g_eligible(e)) return fail(WD_ERR_SHAPE, "fused forward: unaligned buffers");
-            WD_TRY(gemm_x6g(J.g->f_bonds_x6, J.g->ld_bonds, J.D.Kink, nullptr, 0, 0, pk + PL.WiX, J.D.Rp, Hk, e, st));
-            host_with_act(c->activation, [&](auto act_c) {
-                hipLaunchKernelGGL(absmax_blocks_kernel<decltype(act_c)::value>, dim3(J.D.nblk), dim3(256), 0, st,
-                                   (const float *)F(J, J.L.Z[0]), Hk, Hk, J.g->blocks, p->prelu, slot(J, 0), 0);
-            });
-            WD_CHECK_LAUNCH("absmax");
-
-        }
     }
-    const int T = D0.T;
-    for (int t = 1; t < T; ++t) {
-        const bool last = t == T - 1;
-        Multi<MpLayerP> M;
-        int grid;
-        launch_multi(jobs, n, Hk / BNf, [&](MpLayerP &Q, const FusedJob &J) {
-            const WdGraph *g = J.g;
-            // Z_{t-1} in, Z_t out (the last layer: none): a training forward keeps every Z_t (L.Z), inference
-            // ping-pongs two buffers after inp
-            auto zbuf = [&](int k) { return k == 0 || J.D.save ? F(J, J.L.Z[k]) : F(J, J.L.Zb[k & 1]); };
-            const bool a3 = J.D.atom && t == 1;  // (the atom-message input GEMM's inp columns)
-            Q.zin = a3 ? F(J, J.L.In3) : zbuf(t - 1);
-            Q.ldz = a3 ? 3 * Hk : Hk;
-            Q.amax_in = slot(J, t - 1);
-            Q.amax_in_n = t > 1 ? Hk / BNf : (codes ? embed_tiles : (J.D.atom ? Hk / 64 : 1));
-            Q.amax_rt = a3 ? 64 : 0;
-            Q.p_drop_in = t - 1 == 0 ? 0.f : c->dropout;
-            Q.zout = last ? nullptr : zbuf(t);
-            Q.amax_out = last ? nullptr : slot(J, t);
-            Q.kp = Hk;
-            Q.wh = (const uint8_t *)(pk + PL.WhH); Q.wh_amax = (const uint32_t *)(pk + PL.amax) + 64;
-            Q.inp = J.D.atom ? F(J, J.L.In3) + Hk : F(J, J.L.Z[0]);
-            Q.ldr = J.D.atom ? 3 * Hk : Hk;
-            Q.bias = p->b_h ? W(PL.bh) : nullptr;
-            Q.mell_idx = g->msg_ell_idx; Q.mell_coef = g->msg_ell_coef;
-            Q.mptr = g->msg_gather.ptr; Q.midx = g->msg_gather.idx; Q.mcoef = g->msg_gather.coef;
-            Q.blocks = g->blocks;
-            Q.rev = g->b2revb; Q.src_blk = g->bond_src_blk; Q.undirected = J.D.undirected;
-            Q.act = c->activation; Q.slope = p->prelu; Q.p_drop = c->dropout; Q.seed = c->seed; Q.layer = t;
-            Q.aptr = g->atom_gather.ptr; Q.aidx = g->atom_gather.idx; Q.acoef = g->atom_gather.coef;
-            Q.aell_idx = g->atom_ell_idx; Q.aell_coef = g->atom_ell_coef;
-            Q.aplanes = (uint8_t *)(J.ws + J.L.Ab);
-            Q.n_tiles = Hk / BNf;
-            Q.zsave = J.D.save && last ? F(J, J.L.Z[t]) : nullptr;
-            Q.asave = J.D.save && last ? F(J, J.L.A) : nullptr;
-            if (pairs) {  // M_{t-1} from the pair tiles of its producer (no Z_t in inference)
-                Q.ain = (const uint8_t *)(J.ws + J.L.Mp[(t - 1) & 1]);
-                Q.ain_g = t == 1 ? EPB : BNf;
-                Q.aout = last ? nullptr : (uint8_t *)(J.ws + J.L.Mp[t & 1]);
-                Q.zin = nullptr;
-                Q.zout = nullptr;
-                // the last layer: A as pair tiles (W_o on pairs, WD_WO_PAIRS), its words in the slot this layer
-                // does not read; else bf16x3 plane tiles
-                Q.apairs = last && WD_WO_PAIRS ? (uint8_t *)(J.ws + J.L.Ab) : nullptr;
-                Q.amax_out = slot(J, t);
-            }
-        }, M, grid);
+    const FusedCtx X{jobs, n, p, c, PL, pk, st, D0, D0.Hk, D0.bn};
+    const int stop = D0.V.stop;  // (debug: the stage after which to return, its buffers left in the workspace)
+    WD_TRY(fused_input(X));
+    if (D0.codes && stop == 1) return 0;
+    for (int t = 1; t < D0.T; ++t) {
         if (t == 1) WD_TRY(record_prof(c, 0, 0, st));  // one pair around all the layers
-        // one instantiation per (tile width, last layer, activation)
-        auto go = [&](auto bn_c, auto last_c) {
-            constexpr int BN = decltype(bn_c)::value;
-            constexpr bool LAST = decltype(last_c)::value;
-            host_with_act(c->activation, [&](auto act_c) {
-                constexpr int A = decltype(act_c)::value;
-                if constexpr (BN == 80) {
-                    if (pairs) {
-                        if (n == 1)
-                            hipLaunchKernelGGL((mp_layer_kernel<BN, LAST, A, false, 1, true>), dim3(grid), dim3(MP_THREADS), 0, st, one_job(M));
-                        else
-                            hipLaunchKernelGGL((mp_layer_kernel<BN, LAST, A, false, WD_MULTI, true>), dim3(grid), dim3(MP_THREADS), 0, st, M);
-                        return;
-                    }
-                }
-                if (n == 1 && D0.atom)
-                    hipLaunchKernelGGL((mp_layer_kernel<BN, LAST, A, true, 1>), dim3(grid), dim3(MP_THREADS), 0, st, one_job(M));
-                else if (n == 1)
-                    hipLaunchKernelGGL((mp_layer_kernel<BN, LAST, A, false, 1>), dim3(grid), dim3(MP_THREADS), 0, st, one_job(M));
-                else
-                    hipLaunchKernelGGL((mp_layer_kernel<BN, LAST, A, false>), dim3(grid), dim3(MP_THREADS), 0, st, M);
-            });
-        };
-        using I80 = std::integral_constant<int, 80>;
-        using I64 = std::integral_constant<int, 64>;
-        if (bn80) { if (last) go(I80{}, std::true_type{}); else go(I80{}, std::false_type{}); }
-        else { if (last) go(I64{}, std::true_type{}); else go(I64{}, std::false_type{}); }
-        WD_CHECK_LAUNCH("mp_layer");
-        if (last) WD_TRY(record_prof(c, 0, 1, st));
-        if (c->gemm_variant >= 100 && c->gemm_variant % 10 == t + 1) return 0;
+        WD_TRY(fused_layer(X, t));
+        if (t == D0.T - 1) WD_TRY(record_prof(c, 0, 1, st));
+        if (stop == t + 1) return 0;
     }
-    // W_o + readout (empty batches -- no molecules -- have no blocks and write nothing)
-    Multi<WoReadoutP> M;
-    int grid;
-    launch_multi(jobs, n, Hk / BNf, [&](WoReadoutP &R, const FusedJob &J) {
-        const WdGraph *g = J.g;
-        // (codes: the f_atoms segment is not read; a lean graph has no planes -- the A planes stand in as the
-        // segment's non-null base)
-        R.fa = g->f_atoms_blk_x6 ? (const uint8_t *)g->f_atoms_blk_x6 : (const uint8_t *)(J.ws + J.L.Ab);
-        R.kpa = g->ld_atoms; R.kcw = J.D.Fak / 32;
-        R.kca = codes || J.D.atom ? 0 : R.kcw;
-        R.eo = codes ? F(J, J.L.Eo) : (J.D.atom ? F(J, J.L.In3) + 2 * Hk : nullptr); R.Hk = Hk;
-        R.ldeo = J.D.atom ? 3 * Hk : Hk;
-        R.ag = (const uint8_t *)(J.ws + J.L.Ab); R.kp = Hk;
-        R.wo = (const uint8_t *)(pk + (bn80 ? PL.WoX80 : PL.WoX)); R.bias = W(PL.bo);
-        R.blocks = g->blocks;
-        R.w_atoms = g->w_atoms; R.mol_start = g->mol_start; R.mol_size = g->mol_size; R.xn = g->degree_of_polym;
-        R.agg = c->aggregation; R.norm = c->aggregation_norm; R.zero_vec = p->zero_vec;
-        R.act = c->activation; R.slope = p->prelu; R.p_drop = c->dropout; R.seed = c->seed; R.layer = J.D.T;
-        R.out = J.out; R.ncols = J.D.H; R.n_tiles = Hk / BNf;
-        R.zosave = J.D.save ? F(J, J.L.Zo) : nullptr;
-        // (debug variants 1a4: the W_o pre-activation into the free second ping-pong buffer, tools/debug_pairs.py)
-        if (c->gemm_variant >= 100 && c->gemm_variant % 10 == 4 && J.D.T == 3)
-            R.zosave = pairs ? F(J, J.L.Mp[1]) : F(J, J.L.Zb[1]);
-        if (pairs && WD_WO_PAIRS) {
-            R.apairs = (const uint8_t *)(J.ws + J.L.Ab); R.a_amax = slot(J, J.D.T - 1); R.a_nw = Hk / BNf; R.a_g = BNf;
-            R.woh = (const uint8_t *)(pk + PL.WoH); R.wo_amax = (const uint32_t *)(pk + PL.wo_amax) + 64;
-        }
-    }, M, grid);
-    if (grid > 0) {
-        // one batch: single-chunk stages (55 KB, co-resident with other streams' layers); several: two
-        if (pairs && WD_WO_PAIRS && n > 1)
-            hipLaunchKernelGGL((wo_readout_kernel<80, 1, WD_MULTI, true>), dim3(grid), dim3(512), 0, st, M);
-        else if (pairs && WD_WO_PAIRS)
-            hipLaunchKernelGGL((wo_readout_kernel<80, 1, 1, true>), dim3(grid), dim3(512), 0, st, one_job(M));
-        else if (bn80 && n > 1)
-            hipLaunchKernelGGL((wo_readout_kernel<80, 2>), dim3(grid), dim3(64 * WoWaves<80>::WM * WoWaves<80>::WN), 0, st, M);
-        else if (bn80)
-            hipLaunchKernelGGL((wo_readout_kernel<80, 1, 1>), dim3(grid), dim3(64 * WoWaves<80>::WM * WoWaves<80>::WN), 0, st, one_job(M));
-        else if (n == 1)
-            hipLaunchKernelGGL((wo_readout_kernel<64, 1, 1>), dim3(grid), dim3(64 * WoWaves<64>::WM * WoWaves<64>::WN), 0, st, one_job(M));
-        else
-            hipLaunchKernelGGL((wo_readout_kernel<64, 1>), dim3(grid), dim3(64 * WoWaves<64>::WM * WoWaves<64>::WN), 0, st, M);
-        WD_CHECK_LAUNCH("wo_readout");
-    }
-    return 0;
+    return fused_wo_readout(X);
 }
 
 // the whole fused inference forward as one launch (small_fwd.hpp): one workgroup per molecule block
@@ -1121,7 +1154,6 @@ int small_forward(const WdGraph *g, const Dims &D, const WdParams *p, const WdCo
                   const char *pk, float *out, hipStream_t st) {
     if (D.nblk < 1) return 0;
     auto W = [&](size_t off) { return (const float *)(pk + off); };
-    const bool bn80 = D.Hk % 80 == 0;
     SmallFwdP S{};
     S.blocks = g->blocks; S.codes = g->atom_codes; S.src_blk = g->bond_src_blk; S.tail = g->bond_tail;
     S.rev = g->b2revb;
@@ -1130,8 +1162,8 @@ int small_forward(const WdGraph *g, const Dims &D, const WdParams *p, const WdCo
     S.w_atoms = g->w_atoms; S.mol_start = g->mol_start; S.mol_size = g->mol_size; S.xn = g->degree_of_polym;
     S.wit = W(PL.WiT); S.woat = W(PL.WoaT);
     S.bi = p->b_i ? W(PL.bi) : nullptr; S.bh = p->b_h ? W(PL.bh) : nullptr; S.bo = W(PL.bo);
-    S.wh = (const uint8_t *)(pk + PL.WhH); S.wh_amax = (const uint32_t *)(pk + PL.amax) + 64; S.whbr = fused_bn(D.Hk);
-    S.wo = (const uint8_t *)(pk + (bn80 ? PL.WoX80 : PL.WoX)); S.wobr = bn80 ? 80 : 64; S.kcw = D.Fak / 32;
+    S.wh = (const uint8_t *)(pk + PL.WhH); S.wh_amax = (const uint32_t *)(pk + PL.amax) + 64; S.whbr = D.bn;
+    S.wo = (const uint8_t *)(pk + (D.bn == 80 ? PL.WoX80 : PL.WoX)); S.wobr = D.bn; S.kcw = D.Fak / 32;
     S.Fa = D.Fa; S.Fb = D.Fb; S.T = D.T; S.undirected = D.undirected; S.agg = c->aggregation; S.norm = c->aggregation_norm;
     S.zero_vec = p->zero_vec; S.slope = p->prelu;
     S.out = out; S.ncols = D.H;
@@ -1253,10 +1285,6 @@ int wdmpnn_forward(const WdGraph *g, const WdParams *p, const WdConfig *c, void 
     auto W = [&](size_t off) { return (const float *)(pk + off); };
     const int Hk = D.Hk;
 
-    // without plane copies of its A operand a split-plane GEMM splits in the kernel (gemm_x6_kernel)
-    const bool split = !D.f32;
-    const char *pkb = pk;
-
     if (D.small) return small_forward(g, D, p, c, PL, pk, out, st);
     if (D.blocked) {
         FusedJob J{g, D, L, ws, out};
@@ -1269,9 +1297,10 @@ int wdmpnn_forward(const WdGraph *g, const WdParams *p, const WdConfig *c, void 
         const int lda = D.atom ? g->ld_atoms : g->ld_bonds;
         const Epi e = epi_act(c->activation, p->prelu, W(PL.bi), nullptr, F(L.Z[0]), F(L.M[0]), Hk, c, 0);
         if (D.x6 && g->f_bonds_x6 && x6g_eligible(e))
-            WD_TRY(gemm_x6g(g->f_bonds_x6, g->ld_bonds, D.Kink, nullptr, 0, 0, pkb + PL.WiX, D.Rp, Hk, e, st));
+            WD_TRY(gemm_x6g(g->f_bonds_x6, g->ld_bonds, D.Kink, nullptr, 0, 0, pk + PL.WiX, D.Rp, Hk, e, st));
         else
-            WD_TRY(gemm_nt(a, lda, D.Kink, nullptr, 0, 0, W(PL.Wi), D.Kink, D.Rp, Hk, e, st, split));
+            // (without plane copies of its A operand a split-plane GEMM splits in the kernel, gemm_x6_kernel)
+            WD_TRY(gemm_nt(a, lda, D.Kink, nullptr, 0, 0, W(PL.Wi), D.Kink, D.Rp, Hk, e, st, !D.V.f32));
     }
     // L1..T-1: message passing (mpn.py:100-124): X_t = gather(M_{t-1}) [| bond features], then
     // M_t = act(inp + X_t W_h^T (+ b_h))
@@ -1288,13 +1317,13 @@ int wdmpnn_forward(const WdGraph *g, const WdParams *p, const WdConfig *c, void 
             // X_t as plane tiles (+ fp32 for the weight gradient when training)
             WD_TRY(gather8(F(L.M[prev]), Hk, Hk, g->msg_gather, sym, D.save ? Xt : nullptr, D.ldx, ws + L.Xp, Hk, 0,
                            D.R, D.Rp, st));
-            WD_TRY(gemm_x6g(ws + L.Xp, Hk, Hk, nullptr, 0, 0, pkb + PL.WhX, D.Rp, Hk, e, st));
+            WD_TRY(gemm_x6g(ws + L.Xp, Hk, Hk, nullptr, 0, 0, pk + PL.WhX, D.Rp, Hk, e, st));
         } else {
             WD_TRY(gather8(F(L.M[prev]), Hk, Hk, g->msg_gather, sym, Xt, D.ldx, nullptr, 0, 0, D.R, D.Rp, st));
             if (D.atom)
                 WD_TRY(gather8(g->f_bonds, g->ld_bonds, D.Fbk, g->bond_feat_gather, nullptr, Xt + Hk, D.ldx, nullptr, 0,
                                0, D.R, D.Rp, st));
-            WD_TRY(gemm_nt(Xt, D.ldx, D.ldx, nullptr, 0, 0, W(PL.Wh), D.ldx, D.Rp, Hk, e, st, split));
+            WD_TRY(gemm_nt(Xt, D.ldx, D.ldx, nullptr, 0, 0, W(PL.Wh), D.ldx, D.Rp, Hk, e, st, !D.V.f32));
         }
         if (t == D.T - 1) WD_TRY(record_prof(c, 0, 1, st));
         cur = next;
@@ -1307,11 +1336,11 @@ int wdmpnn_forward(const WdGraph *g, const WdParams *p, const WdConfig *c, void 
         if (D.x6 && g->f_atoms_x6 && x6g_eligible(e)) {
             WD_TRY(gather8(M_last, Hk, Hk, g->atom_gather, nullptr, D.save ? F(L.A) : nullptr, Hk, ws + L.Ap, Hk, 0,
                            D.Va, D.Vap, st));
-            WD_TRY(gemm_x6g(g->f_atoms_x6, g->ld_atoms, D.Fak, ws + L.Ap, Hk, Hk, pkb + PL.WoX, D.Vap, Hk, e, st));
+            WD_TRY(gemm_x6g(g->f_atoms_x6, g->ld_atoms, D.Fak, ws + L.Ap, Hk, Hk, pk + PL.WoX, D.Vap, Hk, e, st));
         } else {
             WD_TRY(gather8(M_last, Hk, Hk, g->atom_gather, nullptr, F(L.A), Hk, nullptr, 0, 0, D.Va, D.Vap, st));
             WD_TRY(gemm_nt(g->f_atoms, g->ld_atoms, D.Fak, F(L.A), Hk, Hk, W(PL.Wo), D.Ko, D.Vap, Hk, e, st,
-                           split));
+                           !D.V.f32));
         }
     }
     const float *hfin = F(L.h);
@@ -1934,11 +1963,8 @@ static int feed_batch_workspace(const Feed *F, const WdParams *p, const WdConfig
     if (!p || !c || p->hidden <= 0 || c->depth < 2) return fail(WD_ERR_ARG, "feed forward: bad params / depth");
     const FeedBounds f = feed_bounds(F->spec.kind);
     Dims D{};
-    D.H = p->hidden; D.Hk = rup(D.H, 64); D.T = c->depth;
-    D.R = 2 * F->spec.batch * f.pairs_per_mol + 1; D.Rp = rup(D.R, 128);
-    D.Va = F->spec.batch * f.atoms_per_mol + 1; D.Vap = rup(D.Va, 128);
-    D.Fa = F->spec.atom_fdim; D.Fak = rup(D.Fa, 32); D.Fb = F->spec.bond_fdim; D.Fbk = rup(D.Fb, 32);
-    D.Hd = D.H; D.Hdk = rup(D.Hd, 64); D.Kin = D.Fb; D.Kink = D.Fbk; D.ldx = D.Hk; D.Ko = D.Fak + D.Hk; D.Kd = D.Hk;
+    fill_sizes(D, p->hidden, c->depth, F->spec.batch * f.atoms_per_mol + 1, 2 * F->spec.batch * f.pairs_per_mol + 1,
+               F->spec.atom_fdim, F->spec.bond_fdim, 0, false);
     D.x6 = true; D.blocked = true; D.nblk = F->spec.batch;  // (blocks hold whole molecules: <= batch)
     const size_t staged = fwd_layout(D, false).total;
     D.pairs = true;  // (the pair tiles too: whichever layout get_dims picks is covered)
@@ -2102,7 +2128,6 @@ int wdmpnn_adam_step_repack(const WdAdamTensor *tensors, int32_t n, const WdAdam
     char *base = (char *)packed;
     auto F = [&](size_t off) { return (void *)(base + off); };
     const int H = D.H;
-    const bool b80 = D.Hk % 80 == 0;
     uint32_t *wh_amax = (uint32_t *)(base + L.amax);
     RepackTarget rt[6] = {};
     // (pack_params' jobs, in its order: plain copy, transposes, plane tiles)
@@ -2116,7 +2141,7 @@ int wdmpnn_adam_step_repack(const WdAdamTensor *tensors, int32_t n, const WdAdam
     rt[2].out[rt[2].nout++] = ao(F(L.Wh), AO_PLAIN, D.ldx, {{0, 0, H}});
     rt[2].out[rt[2].nout++] = ao(F(L.WhT), AO_TRANSPOSE, D.Hk, {{0, 0, H}});
     rt[2].out[rt[2].nout++] = ao(F(L.WhX), AO_PLANES, D.ldx, {{0, 0, H}}, 64);
-    if (b80) rt[2].out[rt[2].nout++] = ao(F(L.WhX80), AO_PLANES, D.ldx, {{0, 0, H}}, 80);
+    if (D.bn == 80) rt[2].out[rt[2].nout++] = ao(F(L.WhX80), AO_PLANES, D.ldx, {{0, 0, H}}, 80);
     rt[3] = {p->b_h, 1, H, {}, 0, nullptr};
     rt[3].out[rt[3].nout++] = ao(F(L.bh), AO_PLAIN, D.Hk, {{0, 0, H}});
     rt[4] = {p->W_o, H, D.Fa + H, {}, 0, nullptr};
@@ -2124,7 +2149,7 @@ int wdmpnn_adam_step_repack(const WdAdamTensor *tensors, int32_t n, const WdAdam
     rt[4].out[rt[4].nout++] = ao(F(L.WoT), AO_TRANSPOSE, D.Hk, {{0, D.Fa, H}});
     rt[4].out[rt[4].nout++] = ao(F(L.WoaT), AO_TRANSPOSE, D.Hk, {{0, 0, D.Fa}});
     rt[4].out[rt[4].nout++] = ao(F(L.WoX), AO_PLANES, D.Ko, {{0, 0, D.Fa}, {D.Fak, D.Fa, H}}, 64);
-    if (b80) rt[4].out[rt[4].nout++] = ao(F(L.WoX80), AO_PLANES, D.Ko, {{0, 0, D.Fa}, {D.Fak, D.Fa, H}}, 80);
+    if (D.bn == 80) rt[4].out[rt[4].nout++] = ao(F(L.WoX80), AO_PLANES, D.Ko, {{0, 0, D.Fa}, {D.Fak, D.Fa, H}}, 80);
     rt[5] = {p->b_o, 1, H, {}, 0, nullptr};
     rt[5].out[rt[5].nout++] = ao(F(L.bo), AO_PLAIN, D.Hk, {{0, 0, H}});
     bool found[6] = {};
@@ -2137,7 +2162,7 @@ int wdmpnn_adam_step_repack(const WdAdamTensor *tensors, int32_t n, const WdAdam
     // W_h's fp16-pair tiles from the fresh plain copy, scaled by the max over adam_kernel's tile words
     const int nw = ((H + ADAM_TILE - 1) / ADAM_TILE) * ((H + ADAM_TILE - 1) / ADAM_TILE);
     hipLaunchKernelGGL(split_h2_kernel, dim3(ew_blocks((size_t)D.Hk * D.Hk / 8)), dim3(256), 0, st, (const float *)F(L.Wh),
-                       D.ldx, D.Hk, D.Hk, fused_bn(D.Hk), (uint8_t *)F(L.WhH), wh_amax + 65, nw, wh_amax + 64);
+                       D.ldx, D.Hk, D.Hk, D.bn, (uint8_t *)F(L.WhH), wh_amax + 65, nw, wh_amax + 64);
     WD_CHECK_LAUNCH("adam_step_repack h2");
     return 0;
 }

@@ -134,6 +134,24 @@ def _molgraphs(g):
 
 
 # ---------------------------------------------------------------- native feed (wdmpnn_feed_*)
+def _workspace_within_feed_bound(enc, feed, g):
+    """The bound NativeFeed.encode sizes its workspace by (wdmpnn_feed_forward_workspace_bytes with k = 1, from
+    the largest batch the feed can make) covers the forward workspace of batch ``g`` the feed handed out."""
+    import ctypes
+    from chemprop_amd import _native
+    L = _native.lib()
+    cfg = enc._config(False)
+    gs = enc._graph_struct(g.device_graph(DEV, False, get_bond_fdim()))
+    pstruct, _ = enc._packed_params(gs, cfg, tuple(enc._param_tuple()), DEV)
+    bound, need = ctypes.c_size_t(), ctypes.c_size_t()
+    _native.check(L.wdmpnn_feed_forward_workspace_bytes(feed.handle, ctypes.byref(pstruct), ctypes.byref(cfg), 1,
+                                                        ctypes.byref(bound)), 'feed workspace')
+    _native.check(L.wdmpnn_workspace_bytes(ctypes.byref(gs), ctypes.byref(pstruct), ctypes.byref(cfg),
+                                           ctypes.byref(need)), 'workspace')
+    assert 0 < need.value <= bound.value, (need.value, bound.value)
+    return True
+
+
 def test_native_feed_reproduces_the_python_stream():
     """Same seeds -> the same batches in the same order as StreamedBatches (generation, staging, upload
     and device build now on native threads): bitwise equal encoder outputs, any producer / slot count."""
@@ -143,9 +161,10 @@ def test_native_feed_reproduces_the_python_stream():
         ref = [enc(g) for g in StreamedBatches('polymer', 64, 20, seed=17, device=DEV, rank=1, lean=True)]
         for producers, slots in ((4, None), (1, 3), (7, 16)):
             got = []
-            for g in NativeFeed('polymer', 64, 20, seed=17, device=DEV, rank=1, producers=producers, slots=slots,
-                                lean=True):
+            feed = NativeFeed('polymer', 64, 20, seed=17, device=DEV, rank=1, producers=producers, slots=slots, lean=True)
+            for g in feed:
                 got.append(enc(g))
+                assert _workspace_within_feed_bound(enc, feed, g)  # (hidden 300: the pair tiles' workspace)
             torch.cuda.synchronize()
             assert len(got) == len(ref)
             assert all(torch.equal(a, b) for a, b in zip(ref, got)), (producers, slots)
@@ -165,6 +184,8 @@ def test_native_feed_encode_equals_per_batch_forward():
             edges += e
     assert n == 23 and edges > 0
     assert torch.equal(torch.cat(outs), ref)
+    with NativeFeed('qm9', 32, 23, seed=3, device=DEV, producers=3, slots=6, lean=True) as feed:
+        assert sum(_workspace_within_feed_bound(enc, feed, g) for g in feed) == 23
 
 
 def test_native_feed_training_matches_python_stream():

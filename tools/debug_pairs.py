@@ -1,7 +1,7 @@
 """Stage-by-stage check of the pair-operand forward (round 6) against the register-staged one, on one GPU.
 
-Runs the fused inference forward stopped after each stage (WdConfig.gemm_variant 1ab: a = 1 pair layers, 2
-register-staged layers; b = stage) and decodes the intermediate buffers of the encoder's workspace
+Runs the fused inference forward stopped after each stage (WdConfig.gemm_variant WD_VARIANT_DEBUG, wdmpnn.h:
+_native.variant_debug(DEBUG_PAIRS or DEBUG_STAGED layers, stage)) and decodes the intermediate buffers of the encoder's workspace
 (wdmpnn_debug_fwd_offsets): M_0 pairs vs act(inp), M_1 pairs vs act(Z_1) of the staged path, A pairs vs
 the staged path's bf16x3 A planes, then the outputs.
     python tools/debug_pairs.py [kind] [batch] [hidden]"""
@@ -36,6 +36,7 @@ L.wdmpnn_debug_fwd_offsets.argtypes = [ctypes.c_void_p] * 4
 blocks = np.array(g.molecule_blocks(), np.int64)
 Hk = -(-H // 64) * 64
 nch = Hk // 32
+PAIRS, STAGED, WO_DUMP, stop = _native.DEBUG_PAIRS, _native.DEBUG_STAGED, _native.DEBUG_WO_DUMP, _native.variant_debug
 EPB = int(os.environ.get('WD_EMBED_PAIR_BN', '32'))  # the embed's pair tile width (wdmpnn.hip EPB)
 
 
@@ -97,7 +98,7 @@ def err(a, b, mask_rows):
 
 
 relu = lambda x: np.maximum(x, 0)  # noqa: E731
-o, ws, off = run(111)
+o, ws, off = run(stop(PAIRS, 1))
 print('offsets', off)
 inp = f32(ws, off[0], (len(ws) - off[0]) // 4)
 R = lambda k: blocks[k][1]  # noqa: E731
@@ -109,10 +110,10 @@ m0 = pairs(ws, off[1], 128, w0, EPB)
 print('M0 pairs vs act(inp): rel err %.3e (block %d)' % err(m0, relu(inp_blk), R))
 print('   embed words block 0:', [hex(x) for x in w0[0]])
 
-o, ws, off = run(112)
+o, ws, off = run(stop(PAIRS, 2))
 w1 = words(ws, off[5], Hk // 80)
 m1 = pairs(ws, off[2], 128, w1, 80)
-o2, ws2, off2 = run(122)
+o2, ws2, off2 = run(stop(STAGED, 2))
 z1 = f32(ws2, off2[7], len(ws2) // 4 - off2[7] // 4)
 z1_blk = np.zeros((len(blocks), 128, Hk))
 for k, (bs, bn, *_) in enumerate(blocks):
@@ -120,10 +121,10 @@ for k, (bs, bn, *_) in enumerate(blocks):
 print('M1 pairs vs act(Z1) staged: rel err %.3e (block %d)' % err(m1, relu(z1_blk), R))
 print('   layer-1 words block 0:', [hex(x) for x in w1[0]])
 
-o, ws, off = run(113)
+o, ws, off = run(stop(PAIRS, 3))
 wa = words(ws, off[4], Hk // 80)
 a_p = pairs(ws, off[3], 64, wa, 80)
-o2, ws2, off2 = run(123)
+o2, ws2, off2 = run(stop(STAGED, 3))
 a_s = planes(ws2, off2[3], 64)
 print('A pairs vs A planes staged: rel err %.3e (block %d)' % err(a_p, a_s, lambda k: blocks[k][3]))
 
@@ -136,9 +137,9 @@ print('W_o words: folded', hex(wmax[64]), 'max of 64', hex(wmax[:64].max()), 'tr
 t = pk[off[10]:off[10] + Hk * Hk * 4].view(np.float16).reshape(Hk // 80, nch, 2, 80, 32).astype(np.float64)
 woh = (t[:, :, 0] + t[:, :, 1]).transpose(0, 2, 1, 3).reshape(Hk, Hk) / scale(np.array([wmax[64]]))[0]
 print('W_o pairs vs W_o[:, Fa:]: max abs err %.3e (max %.3e)' % (np.abs(woh[:H, :H] - wo).max(), np.abs(wo).max()))
-o, ws, off = run(114)
+o, ws, off = run(stop(PAIRS, WO_DUMP))
 zo_p = f32(ws, off[2], (len(ws) - off[2]) // 4)
-o2, ws2, off2 = run(124)
+o2, ws2, off2 = run(stop(STAGED, WO_DUMP))
 zo_s = f32(ws2, off2[7], (len(ws2) - off2[7]) // 4)
 na = g.n_atoms
 d = np.abs(zo_p[Hk:na * Hk] - zo_s[Hk:na * Hk])
@@ -178,7 +179,7 @@ for k, (bs, bn, as_, an, *_) in enumerate(blocks[:3]):
 eo_p = f32(ws, off[14], (len(ws) - off[14]) // 4)[:na * Hk]
 eo_s = f32(ws2, off2[14], (len(ws2) - off2[14]) // 4)[:na * Hk]
 print('Eo pairs path vs staged path: max abs %.3e' % np.abs(eo_p[Hk:] - eo_s[Hk:]).max())
-o, _, _ = run(110)
-o2, _, _ = run(120)
+o, _, _ = run(stop(PAIRS, 0))
+o2, _, _ = run(stop(STAGED, 0))
 n = lambda a, b: float(np.abs(a - b).max() / np.abs(b).max())  # noqa: E731
 print('outputs: pairs vs oracle %.3e, staged vs oracle %.3e, pairs vs staged %.3e' % (n(o, ref), n(o2, ref), n(o, o2)))

@@ -2,8 +2,8 @@
 
 For each configuration, prints max|out - ref64| / max|ref64| of the encoder output for
   ref32  the fp32 oracle (the reference's own arithmetic, CPU),
-  f32    the HIP path with the f32-MFMA GEMM (WdConfig.gemm_variant 9),
-  x6     the default HIP path: bf16x6 split-plane GEMMs (gemm_variant 0; molecule-blocked when the
+  f32    the HIP path with the f32-MFMA GEMM (WdConfig.gemm_variant WD_VARIANT_F32),
+  x6     the default HIP path: bf16x6 split-plane GEMMs (WD_VARIANT_DEFAULT; molecule-blocked when the
          batch allows it, operands split in the kernel in atom-message mode),
 so the split GEMM can be judged against the fp32 arithmetic it replaces."""
 import os
@@ -14,7 +14,7 @@ sys.path[:0] = [ROOT, os.path.join(ROOT, 'polymer-chemprop_amd')]
 import numpy as np  # noqa: E402
 import torch  # noqa: E402
 
-from chemprop_amd import TrainArgs, synthetic  # noqa: E402
+from chemprop_amd import TrainArgs, _native, synthetic  # noqa: E402
 from chemprop_amd.featurization import BatchMolGraph, get_atom_fdim, get_bond_fdim  # noqa: E402
 from chemprop_amd.mpn import MPNEncoder  # noqa: E402
 from chemprop_amd.nn_utils import initialize_weights  # noqa: E402
@@ -43,7 +43,7 @@ for kind, b, H, T, extra in (('polymer', 64, 300, 3, {}), ('polymer', 64, 300, 3
             refs[dt] = mpn_ref.encoder_forward(p, g, args, dtype=dt).numpy()
     enc = enc.to(dev).eval()
     res = {'ref32': nw(refs[torch.float32], refs[torch.float64])}
-    for name, v in (('f32', 9), ('x6', 0)):
+    for name, v in (('f32', _native.VARIANT_F32), ('x6', _native.VARIANT_DEFAULT)):
         enc._gemm_variant = v
         with torch.no_grad():
             res[name] = nw(enc(g).cpu().numpy(), refs[torch.float64])
