@@ -455,6 +455,64 @@ int wdmpnn_head_predict(const WdHeadPredict *h, void *stream);
  * incoming gradient in one launch. */
 int wdmpnn_scale(float *const *p, const int64_t *n, int32_t k, const float *s, void *stream);
 
+/* The FFN head in full generality (model.py:57-121 with any ffn_num_layers, active dropout, any of the six
+ * activations): L nn.Linear layers of widths F -> Hf -> ... -> Hf -> T (L == 1: F -> T),
+ *     a_0 = drop_0(x),  z_l = a_{l-1} W_l^T + b_l (l = 1 .. L),  a_l = drop_l(act(z_l)) (l = 1 .. L-1),
+ *     out = z_L,
+ * the losses of WdHead (loss_kind, n_classes, table, ld_table, inv_n: exactly as there) and every gradient in
+ * one call: dx, dW_l, db_l and, for PReLU, dslope (ONE slope shared by every activation site, as the
+ * reference's single activation module: its gradient is the sum over the sites).
+ * Dropout: drop_l(v)[row][col] = v[row][col] * m, m = 0 or 1 / (1 - p), the counter hash of
+ * (seed, layer = l, row, col) -- chemprop_amd.nn_utils.dropout_mask restates it.  Site l has the shape of
+ * Linear l+1's input; no mask is stored (the backward re-derives it); p == 0 skips the hash.
+ * 2 L - 1 launches (2 for L == 1): one GEMM per hidden layer with the activation and the mask applied as its
+ * A operand is staged, one row kernel (the last layer, the loss, dz_{L-1}), then one launch per layer
+ * L-1 .. 1 for dz_{l-1} | dW_l | db_l (the last layer's dW_L, db_L and the loss ride in the first of them).
+ * Fixed summation orders and no float atomics: bitwise repeatable.  fp32 FMA.
+ * Limits: 1 <= L <= WD_HEAD_MAX_LAYERS, F and Hf <= 4096, T <= 64 (WD_ERR_UNSUPPORTED beyond); 0 <= p < 1.
+ * scratch: caller-owned device memory of at least wdmpnn_head_stack_scratch_bytes (16-byte aligned).
+ * B == 0 is a no-op. */
+#define WD_HEAD_MAX_LAYERS 6
+typedef struct WdHeadStack {
+    const float *x; int32_t ld_x;          /* encoder output [B][ld_x], first F columns used        */
+    int32_t B, F, Hf, T, L;                /* rows, input width, hidden width, outputs, Linear layers */
+    const float *W[WD_HEAD_MAX_LAYERS];    /* W_l: [out_l][in_l] row-major (nn.Linear.weight)       */
+    const float *b[WD_HEAD_MAX_LAYERS];    /* b_l or NULL                                           */
+    const float *slope;                    /* [1]: PReLU's slope (act == WD_ACT_PRELU), else unused */
+    const float *table; int32_t ld_table;  /* as WdHead (may be pinned host memory)                 */
+    float inv_n;                           /* 1 / mask.sum()                                        */
+    int32_t act;                           /* WdActivation (any of the six)                         */
+    float p;                               /* dropout probability of every site (0: none)           */
+    uint64_t seed;                         /* the head's dropout seed                               */
+    int32_t loss_kind, n_classes;          /* as WdHead                                             */
+    void *scratch; size_t scratch_bytes;
+    float *out;                            /* [B][T]: the FFN's outputs z_L, or NULL                */
+    float *dx;                             /* [B][ld_x]: d loss / d x                               */
+    float *dW[WD_HEAD_MAX_LAYERS];         /* d loss / d W_l                                        */
+    float *db[WD_HEAD_MAX_LAYERS];         /* d loss / d b_l (NULL = skip)                          */
+    float *dslope;                         /* [1] (NULL = skip; 0 is written unless PReLU and L > 1) */
+    float *loss;                           /* [1]                                                   */
+} WdHeadStack;
+/* floats: z_l and dz_l [B][Hf] for l = 1 .. L-1, a_{L-1} [B][L == 1 ? F : Hf], dout [B][T], the rows'
+ * loss terms [B], and (L - 1) x max(B, ceil(B / 16) ceil(Hf / 16)) partial sums of dslope. */
+int wdmpnn_head_stack_scratch_bytes(int32_t B, int32_t F, int32_t Hf, int32_t T, int32_t L, size_t *bytes);
+int wdmpnn_head_stack(const WdHeadStack *h, void *stream);
+/* The same stack at prediction time (eval mode: no dropout) in L launches, with the output kinds of
+ * WdHeadPredict.  scratch: (L - 1) B Hf floats (the z_l), at least scratch_bytes of them given. */
+typedef struct WdHeadStackPredict {
+    const float *x; int32_t ld_x;
+    int32_t B, F, Hf, T, L;
+    const float *W[WD_HEAD_MAX_LAYERS];
+    const float *b[WD_HEAD_MAX_LAYERS];
+    const float *slope;
+    int32_t act;
+    void *scratch; size_t scratch_bytes;
+    float *out;                            /* [B][T]                                                */
+    int32_t out_kind;                      /* 0 identity, 1 sigmoid, 2 softmax per class group      */
+    int32_t n_classes;                     /* 1 for kinds 0 and 1, >= 2 for kind 2                  */
+} WdHeadStackPredict;
+int wdmpnn_head_stack_predict(const WdHeadStackPredict *h, void *stream);
+
 /* ------------------------------------------------------------------------------------------------
  * Native streamed batches (BASELINE.json configs[4]: millions of synthetic polymer graphs per rank,
  * never materialised).  Replaces chemprop's DataLoader + construct_molecule_batch + BatchMolGraph

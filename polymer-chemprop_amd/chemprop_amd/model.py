@@ -87,11 +87,12 @@ class MoleculeModel(nn.Module):
         emb = self.encoder(batch, features_batch, atom_descriptors_batch, atom_features_batch, bond_features_batch)
         if self.multiclass and not self.training and not torch.is_grad_enabled():
             # multiclass prediction: ffn, the reshape and the softmax as two HIP launches (train.head_predict)
-            # when the head is the two-layer one the native head runs; the torch ops below otherwise
-            from .train import _predict_head, head_predict
+            # when the head is the two-layer one the native head runs (L launches for the other FFNs of create_ffn:
+            # the stack prediction head); the torch ops below otherwise
+            from .train import _head_linears, _predict_head, head_predict
             head = _predict_head(self)
             if head is not None and emb.dim() == 2 and emb.dtype == torch.float32 and \
-                    emb.device == head[0].weight.device:
+                    emb.device == _head_linears(head)[0].weight.device:
                 out = head_predict(self, emb, head)
                 return (out, emb) if return_embeddings else out
         out = self.ffn(emb)

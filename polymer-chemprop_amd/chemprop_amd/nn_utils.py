@@ -8,6 +8,7 @@ and stay PyTorch.
 """
 from __future__ import annotations
 
+import numpy as np
 import torch
 import torch.nn as nn
 
@@ -66,6 +67,27 @@ def index_select_ND(source: torch.Tensor, index: torch.Tensor) -> torch.Tensor:
     if source.dtype != torch.float32:
         raise TypeError('index_select_ND: float32 source expected')
     return _IndexSelectND.apply(source, index.to(source.device))
+
+
+def dropout_mask(seed: int, layer: int, rows: int, cols: int, p: float) -> np.ndarray:
+    """The native dropout masks' contract (``dropout_scale`` in csrc/common.hpp, restated in numpy): float32
+    ``[rows][cols]`` of 0 or 1 / (1 - p).  Element (row, col) of dropout site ``layer`` under the 64-bit ``seed``
+    hashes ``seed ^ (GOLDEN * (layer + 1)) ^ (row << 32 | col)`` with the splitmix64 finaliser (uint64
+    arithmetic), takes the top 24 bits as a uniform u in [0, 1) and keeps the element when
+    ``u >= float32(p)``.  The head's sites: ``layer`` l masks the input of Linear l + 1 (site 0 the encoding)."""
+    p32 = np.float32(p)
+    golden = np.uint64(0x9E3779B97F4A7C15)
+    with np.errstate(over='ignore'):
+        x = np.uint64(seed & 0xFFFFFFFFFFFFFFFF) ^ (golden * np.uint64(layer + 1))
+        r = np.arange(rows, dtype=np.uint64)[:, None] << np.uint64(32)
+        x = x ^ (r | np.arange(cols, dtype=np.uint64)[None, :])
+        x = x + golden
+        x = (x ^ (x >> np.uint64(30))) * np.uint64(0xBF58476D1CE4E5B9)
+        x = (x ^ (x >> np.uint64(27))) * np.uint64(0x94D049BB133111EB)
+        x = x ^ (x >> np.uint64(31))
+    u = (x >> np.uint64(40)).astype(np.float32) * np.float32(1.0 / 16777216.0)
+    keep = np.float32(1.0) / (np.float32(1.0) - p32)
+    return np.where(u >= p32, keep, np.float32(0.0)).astype(np.float32)
 
 
 def get_activation_function(activation: str) -> nn.Module:

@@ -318,6 +318,9 @@ def batch_loss(preds: torch.Tensor, target_batch: Sequence[Sequence[Optional[flo
 # active dropout; MSELoss for regression, BCEWithLogitsLoss for classification, per-task CrossEntropyLoss for
 # multiclass) the loss and every gradient of the head come from two HIP
 # launches in the forward; the backward scales them by the loss's incoming gradient (one launch).
+# Every other FFN of create_ffn with at most 64 outputs (one or up to six Linear layers, dropout active
+# while training, PReLU with its single shared slope) runs the stack head (wdmpnn_head_stack, _StackHead):
+# 2 L - 1 launches, dropout masks from the counter hash of nn_utils.dropout_mask under one seed per step.
 # ------------------------------------------------------------------------------------------------
 def _head_act(m: nn.Module) -> Optional[int]:
     """WdActivation of an FFN activation module the fused head supports (not PReLU), else None."""
@@ -355,19 +358,104 @@ def _fusable_head(model: nn.Module, loss_func: Callable, dataset_type: str):
     st = _head_structure(model)
     if st is None:
         return None
-    l1, l2, code = st
+    l2 = st.linears[-1] if isinstance(st, _StackHead) else st[1]
     if kind == 2 and (l2.out_features % n_classes or l2.out_features != getattr(model, 'output_size', -1)):
         return None
+    if isinstance(st, _StackHead):
+        return st.with_kind(kind, n_classes)
+    l1, l2, code = st
     return l1, l2, code, kind, n_classes
 
 
+class _StackHead:
+    """An FFN the native stack head runs (``wdmpnn_head_stack``): its ``Linear`` layers, the activation code,
+    the shared PReLU slope (or None), the dropout probability active now, and the loss or output kind with its
+    classes per task (set by ``with_kind``)."""
+    __slots__ = ('linears', 'act', 'slope', 'p', 'kind', 'n_classes')
+
+    def __init__(self, linears, act, slope, p, kind=None, n_classes=1):
+        self.linears, self.act, self.slope, self.p, self.kind, self.n_classes = linears, act, slope, p, kind, n_classes
+
+    def with_kind(self, kind: int, n_classes: int) -> '_StackHead':
+        return _StackHead(self.linears, self.act, self.slope, self.p, kind, n_classes)
+
+    def params(self) -> list:
+        """W_1, b_1, ..., W_L, b_L (None for an absent bias), then the slope (or None)."""
+        out = []
+        for l in self.linears:
+            out += [l.weight, l.bias]
+        return out + [self.slope]
+
+
+HEAD_MAX_WIDTH, HEAD_MAX_OUTPUTS = 4096, 64  # (wdmpnn.h: F, Hf <= 4096, T <= 64)
+
+
+def _ffn_structure(ffn: nn.Module, training: bool) -> Optional[_StackHead]:
+    """The structure of an FFN built by ``MoleculeModel.create_ffn`` within the native head's limits, else None:
+    Dropout, Linear, then (activation, Dropout, Linear) up to ``HEAD_MAX_LAYERS`` Linear layers in all, every
+    Dropout with one probability (< 1), one activation (the same module at every site, as create_ffn builds it:
+    a PReLU must have a single slope), hidden layers of one width, widths <= 4096 and <= 64 outputs.  Devices
+    and dtypes are not looked at (``_head_structure`` does)."""
+    from . import _native
+    if not isinstance(ffn, nn.Sequential) or len(ffn) < 2 or len(ffn) % 3 != 2 or \
+            len(ffn) // 3 + 1 > _native.HEAD_MAX_LAYERS:
+        return None
+    mods = list(ffn)
+    drops, linears, acts = mods[0::3], mods[1::3], mods[2::3]
+    if any(type(d) is not nn.Dropout for d in drops) or any(type(l) is not nn.Linear for l in linears):
+        return None
+    p = drops[0].p
+    if any(d.p != p for d in drops) or not 0 <= p < 1:
+        return None
+    code, slope = _native.ACT_IDENTITY, None  # (a one-layer FFN has no activation site)
+    if acts:
+        act = acts[0]
+        if any(a is not act for a in acts):
+            return None
+        if type(act) is nn.PReLU:
+            if act.num_parameters != 1:
+                return None
+            code, slope = 2, act.weight
+        else:
+            code = _head_act(act)
+            if code is None:
+                return None
+    width = linears[0].in_features
+    hidden = linears[0].out_features
+    for i, l in enumerate(linears):
+        if l.in_features != width or l.in_features > HEAD_MAX_WIDTH:
+            return None
+        if i < len(linears) - 1 and l.out_features != hidden:
+            return None
+        width = l.out_features
+    if linears[-1].out_features > HEAD_MAX_OUTPUTS:
+        return None
+    return _StackHead(linears, code, slope, float(p) if training else 0.0)
+
+
 def _head_structure(model: nn.Module):
-    """(Linear 1, Linear 2, activation code) of a MoleculeModel whose FFN the native head kernels can run
-    (Dropout / Linear / activation / Dropout / Linear on the GPU, no dropout while training, at most 64
-    outputs), else None."""
+    """The FFN of a MoleculeModel as the native head kernels run it, else None: (Linear 1, Linear 2,
+    activation code) for the two-layer head without active dropout or PReLU (``wdmpnn_head_mse`` /
+    ``wdmpnn_head_predict``), a :class:`_StackHead` (kind unset) for every other FFN ``_ffn_structure``
+    recognises; float32 contiguous parameters on the GPU."""
     from .model import MoleculeModel
     if not isinstance(model, MoleculeModel) or type(model).forward is not MoleculeModel.forward:
         return None
+    st = _two_layer_structure(model)
+    if st is not None:
+        return st
+    st = _ffn_structure(model.ffn, model.training)
+    if st is None:
+        return None
+    for t in st.params():
+        if t is not None and (t.device.type != 'cuda' or t.dtype != torch.float32 or not t.is_contiguous()):
+            return None
+    return st
+
+
+def _two_layer_structure(model: nn.Module):
+    """(Linear 1, Linear 2, activation code) of the two-layer head (Dropout / Linear / activation / Dropout /
+    Linear on the GPU, no dropout while training, no PReLU, at most 64 outputs), else None."""
     ffn = model.ffn
     if len(ffn) != 5:
         return None
@@ -426,11 +514,97 @@ class _HeadMSE(torch.autograd.Function):
         return grads + (None, None, None, None, None)
 
 
+def _scale_all(grads, gl: torch.Tensor) -> None:
+    """Every gradient times the loss's incoming gradient: wdmpnn_scale, 8 buffers per launch."""
+    from . import _native
+    live = [g for g in grads if g is not None]
+    gl = gl.to(torch.float32).contiguous()
+    for i in range(0, len(live), 8):
+        part = live[i:i + 8]
+        ptrs = (ctypes.c_void_p * len(part))(*[g.data_ptr() for g in part])
+        ns = (ctypes.c_int64 * len(part))(*[g.numel() for g in part])
+        _native.check(_native.lib().wdmpnn_scale(ptrs, ns, len(part), gl.data_ptr(),
+                                                 _native.current_stream(gl.device)), 'scale')
+
+
+def _run_head_stack(x: torch.Tensor, head: _StackHead, tab_ptr: int, ld_table: int, inv_n: float, seed: int,
+                    grad_of: Callable):
+    """One ``wdmpnn_head_stack`` call on the encodings x [B][F] (contiguous): (loss, dx, the gradients in the
+    order of ``head.params()``, None where the parameter is None).  ``grad_of(parameter)`` gives the buffer
+    each gradient is written into."""
+    from . import _native
+    dev = x.device
+    B, F = x.shape
+    lin = head.linears
+    L, T = len(lin), lin[-1].out_features
+    Hf = lin[0].out_features if L > 1 else 0
+    nbytes = _native.head_stack_scratch_bytes(B, F, Hf, T, L)
+    scratch = torch.empty(max(nbytes // 4, 4), dtype=torch.float32, device=dev)
+    dx = torch.empty_like(x)
+    loss = torch.empty((), dtype=torch.float32, device=dev)
+    h = _native.WdHeadStack()
+    h.x, h.ld_x, h.B, h.F, h.Hf, h.T, h.L = x.data_ptr(), F, B, F, Hf, T, L
+    grads = []
+    for i, l in enumerate(lin):
+        gw = grad_of(l.weight)
+        h.W[i], h.dW[i] = l.weight.data_ptr(), gw.data_ptr()
+        grads.append(gw)
+        gb = None
+        if l.bias is not None:
+            gb = grad_of(l.bias)
+            h.b[i], h.db[i] = l.bias.data_ptr(), gb.data_ptr()
+        grads.append(gb)
+    gs = None
+    if head.slope is not None:
+        gs = grad_of(head.slope)
+        h.slope, h.dslope = head.slope.data_ptr(), gs.data_ptr()
+    grads.append(gs)
+    h.table, h.ld_table, h.inv_n, h.act = tab_ptr, ld_table, float(inv_n), head.act
+    h.p, h.seed, h.loss_kind, h.n_classes = head.p, seed, head.kind, head.n_classes
+    h.scratch, h.scratch_bytes = scratch.data_ptr(), scratch.numel() * 4
+    h.dx, h.loss = dx.data_ptr(), loss.data_ptr()
+    _native.check(_native.lib().wdmpnn_head_stack(ctypes.byref(h), _native.current_stream(dev)), 'FFN head stack + loss')
+    return loss, dx, grads
+
+
+class _HeadStack(torch.autograd.Function):
+    """The loss of a :class:`_StackHead` on x, with every gradient computed in the forward (as ``_HeadMSE``).
+    ``params`` are ``head.params()``: autograd needs them as inputs to hand their gradients out."""
+
+    @staticmethod
+    def forward(ctx, x, head, table, inv_n, seed, *params):
+        loss, dx, grads = _run_head_stack(x.contiguous(), head, table.data_ptr(), table.shape[1], inv_n, seed,
+                                          torch.empty_like)
+        ctx.grads = [dx] + grads
+        return loss
+
+    @staticmethod
+    def backward(ctx, gl):
+        grads, ctx.grads = ctx.grads, None
+        _scale_all(grads, gl)
+        return (grads[0], None, None, None, None) + tuple(grads[1:])
+
+
+def _head_seed(head) -> int:
+    """The head's dropout seed for this step: one ``_dropout_seed`` draw when its dropout is active (after the
+    encoder's draw, on the direct and the autograd path alike), else 0."""
+    if isinstance(head, _StackHead) and head.p > 0:
+        from .mpn import _dropout_seed
+        return _dropout_seed()
+    return 0
+
+
 def head_loss(emb: torch.Tensor, head, target_batch, target_weights=None, data_weights=None) -> torch.Tensor:
     """``batch_loss(model.ffn(emb), ...)`` for a head accepted by ``_fusable_head`` (regression with MSE,
     classification with BCE on logits, multiclass with one cross-entropy per task: the targets are then
-    class indices, one per task, checked on the host)."""
-    l1, l2, act, kind, n_classes = head
+    class indices, one per task, checked on the host).  A :class:`_StackHead` (deeper or one-layer FFN, active
+    dropout, PReLU) runs ``wdmpnn_head_stack``; its dropout masks follow the counter hash of
+    ``nn_utils.dropout_mask`` under one seed drawn here."""
+    stack = isinstance(head, _StackHead)
+    if stack:
+        l1, l2, kind, n_classes = head.linears[0], head.linears[-1], head.kind, head.n_classes
+    else:
+        l1, l2, act, kind, n_classes = head
     table, n_t, n_mask = _loss_table(target_batch, target_weights, data_weights, emb.device,
                                      num_classes=n_classes if kind == 2 else 0)
     if n_t * n_classes != l2.out_features:
@@ -439,6 +613,8 @@ def head_loss(emb: torch.Tensor, head, target_batch, target_weights=None, data_w
         raise ValueError(f'{table.shape[0]} target rows for encodings of shape {tuple(emb.shape)} '
                          f'(FFN input {l1.in_features})')
     inv_n = 1.0 / n_mask if n_mask else float('inf')
+    if stack:
+        return _HeadStack.apply(emb, head, table, inv_n, _head_seed(head), *head.params())
     return _HeadMSE.apply(emb, l1.weight, l1.bias, l2.weight, l2.bias, table, inv_n, act, kind, n_classes)
 
 
@@ -448,13 +624,19 @@ def _predict_head(model: nn.Module):
     st = _head_structure(model)
     if st is None:
         return None
-    l2 = st[1]
+    stack = isinstance(st, _StackHead)
+    l2 = st.linears[-1] if stack else st[1]
+    kind, c = 1 if getattr(model, 'classification', False) else 0, 1
     if getattr(model, 'multiclass', False):
-        c = getattr(model, 'num_classes', 0)
+        kind, c = 2, getattr(model, 'num_classes', 0)
         if not isinstance(c, int) or c < 2 or l2.out_features % c:
             return None
-        return st + (2, c)
-    return st + (1 if getattr(model, 'classification', False) else 0, 1)
+    return st.with_kind(kind, c) if stack else st + (kind, c)
+
+
+def _head_linears(head) -> list:
+    """The Linear layers of a head of ``_fusable_head`` / ``_predict_head``, first to last."""
+    return head.linears if isinstance(head, _StackHead) else [head[0], head[1]]
 
 
 def head_predict(model: nn.Module, emb: torch.Tensor, head=None) -> torch.Tensor:
@@ -462,23 +644,41 @@ def head_predict(model: nn.Module, emb: torch.Tensor, head=None) -> torch.Tensor
     encoder: ``ffn``, then nothing for regression, the sigmoid for classification, the softmax over each
     task's classes for multiclass) as two HIP launches (``wdmpnn_head_predict``).  ``[B][T]`` for
     regression and classification, ``[B][tasks][classes]`` for multiclass.  No autograd graph is built.
-    The model must be in eval mode with the two-layer head the fused training head accepts
-    (``NotImplementedError`` otherwise: there is no torch fallback here)."""
+    The model must be in eval mode with an FFN the native heads run: the two-layer head, or any other FFN of
+    ``create_ffn`` with at most 64 outputs as L launches (``wdmpnn_head_stack_predict``);
+    ``NotImplementedError`` otherwise: there is no torch fallback here."""
     from . import _native
     if model.training:
         raise ValueError('head_predict is the eval-mode head: call model.eval() first')
     if head is None:
         head = _predict_head(model)
     if head is None:
-        raise NotImplementedError('head_predict: the model\'s FFN is not the two-layer head (<= 64 outputs, no PReLU) '
-                                  'the native head runs')
-    l1, l2, act, kind, n_classes = head
+        raise NotImplementedError('head_predict: the model\'s FFN is not one the native head runs (Dropout / Linear / '
+                                  'activation stacks of create_ffn, <= 64 outputs, a single PReLU slope)')
+    l1 = _head_linears(head)[0]
     if emb.dim() != 2 or emb.shape[1] != l1.in_features or emb.device != l1.weight.device or \
             emb.dtype != torch.float32:
         raise ValueError(f'encodings of shape {tuple(emb.shape)} ({emb.dtype}, {emb.device}) for an FFN input of '
                          f'{l1.in_features} on {l1.weight.device}')
     x = emb.detach().contiguous()
     B, F = x.shape
+    if isinstance(head, _StackHead):
+        lin = head.linears
+        L, T = len(lin), lin[-1].out_features
+        Hf = lin[0].out_features if L > 1 else 0
+        scratch = torch.empty(max((L - 1) * B * Hf, 4), dtype=torch.float32, device=x.device)
+        out = torch.empty((B, T), dtype=torch.float32, device=x.device)
+        h = _native.WdHeadStackPredict()
+        h.x, h.ld_x, h.B, h.F, h.Hf, h.T, h.L = x.data_ptr(), F, B, F, Hf, T, L
+        for i, l in enumerate(lin):
+            h.W[i], h.b[i] = l.weight.data_ptr(), _native.ptr(l.bias)
+        h.slope, h.act = _native.ptr(head.slope), head.act
+        h.scratch, h.scratch_bytes = scratch.data_ptr(), scratch.numel() * 4
+        h.out, h.out_kind, h.n_classes = out.data_ptr(), head.kind, head.n_classes
+        _native.check(_native.lib().wdmpnn_head_stack_predict(ctypes.byref(h), _native.current_stream(x.device)),
+                      'FFN head stack (predict)')
+        return out.view(B, T // head.n_classes, head.n_classes) if head.kind == 2 else out
+    l1, l2, act, kind, n_classes = head
     Hf, T = l1.out_features, l2.out_features
     a = torch.empty((B, Hf), dtype=torch.float32, device=x.device)
     out = torch.empty((B, T), dtype=torch.float32, device=x.device)
@@ -522,10 +722,14 @@ def _direct_encoder(model: nn.Module, mol_batch, features_batch, head):
         return None
     # the direct step skips zero_grad and overwrites only the gradients it computes: any other trainable
     # parameter (a future addition to the model) would keep a stale gradient, so it must not exist
-    l1, l2 = head[:2]
-    written = {id(t) for _, t in enc._direct_names()} | {id(t) for t in (l1.weight, l1.bias, l2.weight, l2.bias)
-                                                          if t is not None}
-    if len(ids) != len(written) or not written.issuperset(ids):
+    if isinstance(head, _StackHead):
+        head_params = head.params()
+    else:
+        l1, l2 = head[:2]
+        head_params = (l1.weight, l1.bias, l2.weight, l2.bias)
+    written = {id(t) for _, t in enc._direct_names()} | {id(t) for t in head_params if t is not None}
+    # (a shared activation module sits at several places of the FFN's Sequential: its slope is met once per site)
+    if set(ids) != written:
         return None
     return enc
 
@@ -552,7 +756,11 @@ def _direct_step(model, enc, graph, head, target_batch, target_weights, data_wei
     parameters' .grad buffers.  The same launches as the autograd path minus its host gaps (the engine
     hand-off, the gradient-seed fill and the scale by 1; profiles/round3_*)."""
     from . import _native
-    l1, l2, act, kind, n_classes = head
+    stack = isinstance(head, _StackHead)
+    if stack:
+        l1, l2, kind, n_classes = head.linears[0], head.linears[-1], head.kind, head.n_classes
+    else:
+        l1, l2, act, kind, n_classes = head
     nc = n_classes if kind == 2 else 0  # (multiclass: _loss_table checks the class indices on the host)
     out, state = enc._train_forward(graph)
     # the loss table read by the head kernel straight from its pinned host buffer (no copy launch in the
@@ -571,20 +779,24 @@ def _direct_step(model, enc, graph, head, target_batch, target_weights, data_wei
                          f'(FFN input {l1.in_features})')
     inv_n = 1.0 / n_mask if n_mask else float('inf')
     dev = out.device
-    B, F = out.shape
-    Hf, T = l1.weight.shape[0], l2.weight.shape[0]
-    scratch = torch.empty(B * (2 * Hf + T + 1), dtype=torch.float32, device=dev)
-    dx = torch.empty_like(out)
-    loss = torch.empty((), dtype=torch.float32, device=dev)
-    dW1, dW2 = _grad_buffer(l1.weight), _grad_buffer(l2.weight)
-    db1 = _grad_buffer(l1.bias) if l1.bias is not None else None
-    db2 = _grad_buffer(l2.bias) if l2.bias is not None else None
-    ptr = _native.ptr
-    sp = scratch.data_ptr()
-    h = _native.WdHead(ptr(out), F, B, F, Hf, T, ptr(l1.weight), ptr(l1.bias), ptr(l2.weight), ptr(l2.bias), tab_ptr,
-                       tshape[1], float(inv_n), act, sp, sp + 4 * B * Hf, sp + 8 * B * Hf, sp + 4 * B * (2 * Hf + T),
-                       ptr(dx), ptr(dW1), ptr(db1), ptr(dW2), ptr(db2), ptr(loss), kind, n_classes)
-    _native.check(_native.lib().wdmpnn_head_mse(ctypes.byref(h), _native.current_stream(dev)), 'FFN head + loss')
+    if stack:
+        loss, dx, _ = _run_head_stack(out, head, tab_ptr, tshape[1], inv_n, _head_seed(head), _grad_buffer)
+    else:
+        B, F = out.shape
+        Hf, T = l1.weight.shape[0], l2.weight.shape[0]
+        scratch = torch.empty(B * (2 * Hf + T + 1), dtype=torch.float32, device=dev)
+        dx = torch.empty_like(out)
+        loss = torch.empty((), dtype=torch.float32, device=dev)
+        dW1, dW2 = _grad_buffer(l1.weight), _grad_buffer(l2.weight)
+        db1 = _grad_buffer(l1.bias) if l1.bias is not None else None
+        db2 = _grad_buffer(l2.bias) if l2.bias is not None else None
+        ptr = _native.ptr
+        sp = scratch.data_ptr()
+        h = _native.WdHead(ptr(out), F, B, F, Hf, T, ptr(l1.weight), ptr(l1.bias), ptr(l2.weight), ptr(l2.bias),
+                           tab_ptr, tshape[1], float(inv_n), act, sp, sp + 4 * B * Hf, sp + 8 * B * Hf,
+                           sp + 4 * B * (2 * Hf + T), ptr(dx), ptr(dW1), ptr(db1), ptr(dW2), ptr(db2), ptr(loss), kind,
+                           n_classes)
+        _native.check(_native.lib().wdmpnn_head_mse(ctypes.byref(h), _native.current_stream(dev)), 'FFN head + loss')
     if zc is not None:
         zc[1].record(torch.cuda.current_stream(dev))  # (the pinned buffer's last reader)
     if bucket is not None:  # the head's gradients are enqueued: their all-reduce overlaps the encoder backward
@@ -600,7 +812,9 @@ def train_step(model: nn.Module, mol_batch, target_batch, loss_func: Callable, o
     """One optimisation step (train.py:55-86).  With ``bucket`` the gradients are averaged over the
     data-parallel ranks (one all-reduce) before clipping and the optimizer step.  ``fused_head``: the
     default regression / classification / multiclass head + loss run as ``wdmpnn_head_mse`` (same loss and gradients within fp32
-    summation order; ``False`` = the torch ops of the reference).  ``direct``: with the fused head and a
+    summation order; ``False`` = the torch ops of the reference); FFNs with another number of layers, active
+    dropout or PReLU run as ``wdmpnn_head_stack`` (their dropout masks follow ``nn_utils.dropout_mask``, not
+    torch's generator).  ``direct``: with the fused head and a
     plain one-molecule encoder, skip the autograd engine (``_direct_step``: the same launches and results,
     bitwise, without the engine's host gaps).  The direct step keeps one packed copy of the encoder weights
     across steps (rewritten by :class:`HipAdam`); after writing an encoder parameter through ``.data`` call

@@ -789,6 +789,9 @@ __global__ __launch_bounds__(256) void adam_kernel(AdamLaunch A) {
 // loss_kind 1 swaps in BCE on the logits, loss_kind 2 (head_rows_ce_kernel) one softmax cross-entropy per
 // task over its n_classes outputs; only the row kernel's loss terms and dout differ.  The prediction head
 // (wdmpnn_head_predict) is the same H GEMM followed by head_predict_rows_kernel.
+// Every other FFN of model.py:57-121 (1 .. 6 Linear layers, active dropout, PReLU) is the head stack at the
+// end of this file (wdmpnn_head_stack): the same tile code with the activation and the dropout mask applied
+// as operands are staged, 2 L - 1 launches.
 // ------------------------------------------------------------------------------------------------
 namespace wd {
 constexpr int HEAD_MAX_F = 4096, HEAD_MAX_H = 4096, HEAD_MAX_T = 64;
@@ -827,8 +830,15 @@ struct alignas(16) SmallGemmLds {
 };
 static_assert(sizeof(SmallGemmLds<16>) <= sizeof(SmallGemmLds<32>), "head_grads_kernel shares one LDS area");
 // AK: A's k index contiguous (sak == 1, else sai == 1); BJ: B's j index contiguous (sbj == 1, else sbk == 1)
-template <int TS, bool AK, bool BJ>
-__device__ __forceinline__ void small_gemm_tile_t(const SmallGemm &G, int tile, SmallGemmLds<TS> &L) {
+// fa(A(i, k), i, k) and fb(B(k, j), k, j) are applied as the operands are staged and fc(C(i, j), i, j) as the
+// output is stored (the head stack's activation, dropout mask and backward factors; identity for the plain
+// GEMMs of the two-layer head)
+struct SgIdentity {
+    __device__ __forceinline__ float operator()(float v, int, int) const { return v; }
+};
+template <int TS, bool AK, bool BJ, class FA, class FB, class FC>
+__device__ __forceinline__ void small_gemm_tile_f(const SmallGemm &G, int tile, SmallGemmLds<TS> &L, const FA &fa,
+                                                  const FB &fb, FC &fc) {
     constexpr int R = TS / 8;
     typedef float fR __attribute__((ext_vector_type(R)));
     const int tn = (G.N + TS - 1) / TS, i0 = (tile / tn) * TS, j0 = (tile % tn) * TS;
@@ -841,9 +851,9 @@ __device__ __forceinline__ void small_gemm_tile_t(const SmallGemm &G, int tile, 
         for (int q = 0; q < PER; ++q) {
             const int e = tid + 256 * q;
             const int ia = i0 + (AK ? e / SG_KC : e % TS), ka = k0 + (AK ? e % SG_KC : e / TS);
-            ra[q] = ia < G.M && ka < G.K ? G.A[ia * G.sai + ka * G.sak] : 0.f;
+            ra[q] = ia < G.M && ka < G.K ? fa(G.A[ia * G.sai + ka * G.sak], ia, ka) : 0.f;
             const int kb = k0 + (BJ ? e / TS : e % SG_KC), jb = j0 + (BJ ? e % TS : e / SG_KC);
-            rb[q] = kb < G.K && jb < G.N ? G.B[kb * G.sbk + jb * G.sbj] : 0.f;
+            rb[q] = kb < G.K && jb < G.N ? fb(G.B[kb * G.sbk + jb * G.sbj], kb, jb) : 0.f;
         }
     };
     auto store = [&]() {
@@ -888,8 +898,13 @@ __device__ __forceinline__ void small_gemm_tile_t(const SmallGemm &G, int tile, 
     for (int q = 0; q < TS * TS / 256; ++q) {
         const int o = tid + 256 * q, i = i0 + o / TS, j = j0 + o % TS;
         const float v = ((part[o] + part[TS * TS + o]) + part[2 * TS * TS + o]) + part[3 * TS * TS + o];
-        if (i < G.M && j < G.N) G.C[i * G.ldc + j] = v + (G.bias ? G.bias[j] : 0.f);
+        if (i < G.M && j < G.N) G.C[i * G.ldc + j] = fc(v + (G.bias ? G.bias[j] : 0.f), i, j);
     }
+}
+template <int TS, bool AK, bool BJ>
+__device__ __forceinline__ void small_gemm_tile_t(const SmallGemm &G, int tile, SmallGemmLds<TS> &L) {
+    SgIdentity id;
+    small_gemm_tile_f<TS, AK, BJ>(G, tile, L, id, id, id);
 }
 template <int TS>
 __device__ __forceinline__ void small_gemm_tile(const SmallGemm &G, int tile, SmallGemmLds<TS> &L) {
@@ -1109,5 +1124,306 @@ __global__ __launch_bounds__(256) void scale_kernel(ScaleJobs J) {
     for (int i = 0; i < J.k; ++i)
         for (long long e = (long long)blockIdx.x * 256 + threadIdx.x; e < J.n[i]; e += (long long)gridDim.x * 256)
             J.p[i][e] *= s;
+}
+
+// ------------------------------------------------------------------------------------------------
+// The head stack (wdmpnn_head_stack): the FFN with L Linear layers, dropout at every site and any of the six
+// activations (one shared PReLU slope),
+//     a_0 = drop_0(x), z_l = a_{l-1} W_l^T + b_l, a_l = drop_l(act(z_l)), out = z_L,
+// the loss kinds of the two-layer head, and every gradient.  Only the pre-activations z_l are stored: a_l is
+// rebuilt from z_l (activation, then the mask from the counter hash) wherever a GEMM stages it.  Launches:
+//   head_stack_fwd_kernel, l = 1 .. L-1:  z_l, A operand a_{l-1} built as it is staged
+//   head_stack_rows_kernel:               one wave per row: a_{L-1}, out, the loss terms, dout, dz_{L-1}
+//                                         (L == 1: dx), the row's dslope term
+//   head_stack_bwd_kernel, l = L-1 .. 1:  dz_{l-1} = (dz_l W_l) drop_{l-1} act'(z_{l-1}) (l == 1: dx) with each
+//                                         tile's dslope term, dW_l = dz_l^T a_{l-1}, db_l; the launch of l = L-1
+//                                         adds dW_L, db_L and the loss, the launch of l = 1 sums dslope
+//   head_stack_last_kernel (L == 1 only): dW_1, db_1, the loss
+// 2 L - 1 launches (2 for L == 1).  Scratch (floats, wdmpnn_head_stack_scratch_bytes): z [L-1][B][Hf],
+// dz [L-1][B][Hf], a_{L-1} [B][Kin], dout [B][T], lossrow [B], spart [L-1][np]: dslope's partial sums, for site
+// s < L-1 one per 16 x 16 tile of dz_s, for site L-1 one per row; np = max(B, tiles).
+// ------------------------------------------------------------------------------------------------
+__host__ __device__ inline long long head_stack_np(int B, int Hf) {
+    const long long t = head_tiles(B, Hf, HEAD_H_TS);
+    return t > B ? t : B;
+}
+__host__ __device__ inline size_t head_stack_floats(int B, int F, int Hf, int T, int L) {
+    const size_t b = (size_t)B;
+    return (size_t)(L - 1) * (2 * b * Hf + (size_t)head_stack_np(B, Hf)) + b * (L == 1 ? F : Hf) + b * T + b;
+}
+struct StackLayout {
+    float *z, *dz, *alast, *dout, *lossrow, *spart;
+    long long np;
+};
+__host__ __device__ inline StackLayout stack_layout(const WdHeadStack &P) {
+    StackLayout S;
+    const size_t plane = (size_t)P.B * P.Hf, n = (size_t)(P.L - 1) * plane;
+    S.z = (float *)P.scratch;
+    S.dz = S.z + n;
+    S.alast = S.dz + n;
+    S.dout = S.alast + (size_t)P.B * (P.L == 1 ? P.F : P.Hf);
+    S.lossrow = S.dout + (size_t)P.B * P.T;
+    S.spart = S.lossrow + P.B;
+    S.np = head_stack_np(P.B, P.Hf);
+    return S;
+}
+
+// a_s(row, col) from the stored value (z_s, or x for site 0 with ACT_IDENTITY): act, then the site's mask
+template <int ACT>
+struct StackSite {
+    float slope, p;
+    uint64_t seed;
+    uint32_t site;
+    __device__ __forceinline__ float mask(int row, int col) const {
+        return p > 0.f ? dropout_scale(seed, site, (uint32_t)row, (uint32_t)col, p) : 1.f;
+    }
+    __device__ __forceinline__ float operator()(float z, int row, int col) const {
+        return act_fwd(ACT, z, slope) * mask(row, col);
+    }
+};
+// da_s(row, col) -> dz_s(row, col) = da drop_s act'(z_s); part collects the thread's dslope terms
+// da drop_s min(z_s, 0) (PReLU only)
+template <int ACT>
+struct StackDz {
+    StackSite<ACT> s;
+    const float *z;
+    long long ldz;
+    float part;
+    __device__ __forceinline__ float operator()(float v, int row, int col) {
+        v *= s.mask(row, col);
+        if (ACT == ACT_IDENTITY) return v;
+        const float zz = z[row * ldz + col];
+        if (ACT == ACT_PRELU) part += v * (zz > 0.f ? 0.f : zz);
+        return v * act_grad(ACT, zz, s.slope);
+    }
+};
+__device__ __forceinline__ float stack_slope(const float *slope, int act) {
+    return act == ACT_PRELU && slope ? slope[0] : 0.f;
+}
+
+__global__ __launch_bounds__(256) void head_stack_fwd_kernel(WdHeadStack P, int l) {
+    __shared__ SmallGemmLds<HEAD_H_TS> L;
+    const StackLayout S = stack_layout(P);
+    const size_t plane = (size_t)P.B * P.Hf;
+    const int K = l == 1 ? P.F : P.Hf;
+    const SmallGemm G{l == 1 ? P.x : S.z + (l - 2) * plane, l == 1 ? P.ld_x : P.Hf, 1, P.W[l - 1], 1, K, P.b[l - 1],
+                      S.z + (l - 1) * plane, P.Hf, P.B, P.Hf, K};
+    with_act(l == 1 ? (int)ACT_IDENTITY : P.act, [&](auto act_c) {
+        constexpr int ACT = decltype(act_c)::value;
+        const StackSite<ACT> site{stack_slope(P.slope, P.act), P.p, P.seed, (uint32_t)(l - 1)};
+        SgIdentity id;
+        small_gemm_tile_f<HEAD_H_TS, true, false>(G, blockIdx.x, L, site, id, id);
+    });
+}
+
+// The last layer's sums, one thread per element, rows in order: dW_L [T][Kin], db_L [T], the loss
+__device__ __forceinline__ void stack_last_sums(const WdHeadStack &P, const StackLayout &S, long long q) {
+    const int T = P.T, B = P.B, Kin = P.L == 1 ? P.F : P.Hf;
+    if (q < (long long)T * Kin) {
+        const int t = (int)(q / Kin), j = (int)(q % Kin);
+        P.dW[P.L - 1][q] = row_sum(S.dout + t, T, S.alast + j, Kin, B);
+    } else if (q < (long long)T * Kin + T) {
+        const int t = (int)(q - (long long)T * Kin);
+        const float s = row_sum(S.dout + t, T, nullptr, 0, B);
+        if (P.db[P.L - 1]) P.db[P.L - 1][t] = s;
+    } else if (q == (long long)T * Kin + T) {
+        P.loss[0] = row_sum(S.lossrow, 1, nullptr, 0, B) * P.inv_n;
+    }
+}
+__host__ __device__ inline long long stack_last_count(int F, int Hf, int T, int L) {
+    return (long long)T * (L == 1 ? F : Hf) + T + 1;
+}
+
+// One wave per row: a_{L-1} = drop_{L-1}(act(z_{L-1})) (L == 1: drop_0(x)) into S.alast, out = a_{L-1} W_L^T +
+// b_L into the wave's LDS row, the loss terms and dout as head_rows_kernel / head_rows_ce_kernel, then
+// dz_{L-1} = (dout W_L) drop_{L-1} act'(z_{L-1}) (L == 1: dx) and the row's dslope term
+__global__ __launch_bounds__(256) void head_stack_rows_kernel(WdHeadStack P) {
+    __shared__ float dsh[4][HEAD_MAX_T];
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6, row = blockIdx.x * 4 + wave;
+    if (row >= P.B) return;
+    const StackLayout S = stack_layout(P);
+    const int L = P.L, T = P.T, Kin = L == 1 ? P.F : P.Hf;
+    const int C = P.loss_kind == 2 ? P.n_classes : 1, K = T / C;
+    const float *zin = L == 1 ? P.x + (size_t)row * P.ld_x : S.z + ((size_t)(L - 2) * P.B + row) * P.Hf;
+    float *dzo = L == 1 ? P.dx + (size_t)row * P.ld_x : S.dz + ((size_t)(L - 2) * P.B + row) * P.Hf;
+    float *a = S.alast + (size_t)row * Kin;
+    const float *W = P.W[L - 1], *bias = P.b[L - 1];
+    const float *tab = P.table + (size_t)row * P.ld_table;
+    // the row's targets | weights, one per lane, loaded first (head_rows_kernel: the table may be pinned host memory)
+    const bool tlane = 2 * K <= 64;
+    const float tv = tlane && lane < 2 * K ? tab[lane] : 0.f;
+    float *ds = dsh[wave];
+    with_act(L == 1 ? (int)ACT_IDENTITY : P.act, [&](auto act_c) {
+        constexpr int ACT = decltype(act_c)::value;
+        const StackSite<ACT> site{stack_slope(P.slope, P.act), P.p, P.seed, (uint32_t)(L - 1)};
+        for (int j = lane; j < Kin; j += 64) a[j] = site(zin[j], row, j);  // (each lane reads back its own elements)
+        for (int t = 0; t < T; ++t) {
+            const float *w = W + (size_t)t * Kin;
+            float s = 0.f;
+            for (int j = lane; j < Kin; j += 64) s = fmaf(w[j], a[j], s);
+            ds[t] = wave_sum(s) + (bias ? bias[t] : 0.f);
+        }
+        if (P.out && lane < T) P.out[(size_t)row * T + lane] = ds[lane];
+        float l = 0.f;
+        for (int k = 0; k < K; ++k) {
+            const float y = tlane ? __shfl(tv, k, 64) : tab[k], w = tlane ? __shfl(tv, K + k, 64) : tab[K + k];
+            if (P.loss_kind == 2) {  // softmax cross-entropy over the task's C logits (head_rows_ce_kernel)
+                float *s = ds + k * C;
+                float m, e;
+                group_max_sum(s, C, m, e);
+                const float logsum = logf(e);
+                float sy = 0.f;
+                for (int c = 0; c < C; ++c) {
+                    const float z = s[c] - m;
+                    const bool hit = (float)c == y;
+                    sy = hit ? z : sy;
+                    s[c] = w * (expf(z - logsum) - (hit ? 1.f : 0.f)) * P.inv_n;
+                }
+                l = fmaf(w, logsum - sy, l);
+            } else {
+                const float s = ds[k];
+                if (P.loss_kind == 0) {  // MSE
+                    const float r = s - y;
+                    l = fmaf(w * r, r, l);
+                    ds[k] = 2.f * w * r * P.inv_n;
+                } else {  // BCE with logits
+                    l = fmaf(w, fmaxf(s, 0.f) - s * y + log1pf(expf(-fabsf(s))), l);
+                    ds[k] = w * (1.f / (1.f + expf(-s)) - y) * P.inv_n;
+                }
+            }
+        }
+        if (lane < T) S.dout[(size_t)row * T + lane] = ds[lane];
+        if (lane == 0) S.lossrow[row] = l;
+        float sp = 0.f;
+        for (int j = lane; j < Kin; j += 64) {
+            float g = 0.f;
+            for (int t = 0; t < T; ++t) g = fmaf(ds[t], W[(size_t)t * Kin + j], g);
+            g *= site.mask(row, j);
+            if (ACT != ACT_IDENTITY) {
+                const float z = zin[j];
+                if (ACT == ACT_PRELU) sp += g * (z > 0.f ? 0.f : z);
+                g *= act_grad(ACT, z, site.slope);
+            }
+            dzo[j] = g;
+        }
+        if (ACT == ACT_PRELU) {
+            sp = wave_sum(sp);
+            if (lane == 0) S.spart[(size_t)(L - 2) * S.np + row] = sp;
+        }
+    });
+}
+
+// dslope = the sum of every site's partial sums, one workgroup: thread t adds the partials t, t + 256, ... of
+// the sites in order, thread 0 the 256 sums in order
+__device__ __forceinline__ void stack_slope_sum(const WdHeadStack &P, const StackLayout &S, float *red) {
+    const int tid = threadIdx.x;
+    float s = 0.f;
+    if (P.act == ACT_PRELU)
+        for (int site = 1; site < P.L; ++site) {
+            const long long n = site == P.L - 1 ? P.B : head_tiles(P.B, P.Hf, HEAD_H_TS);
+            for (long long e = tid; e < n; e += 256) s += S.spart[(size_t)(site - 1) * S.np + e];
+        }
+    red[tid] = s;
+    __syncthreads();
+    if (tid == 0) {
+        float t = 0.f;
+        for (int e = 0; e < 256; ++e) t += red[e];
+        P.dslope[0] = t;
+    }
+}
+
+// Layer l < L: tiles of dz_{l-1} (l == 1: dx), then tiles of dW_l, then one thread per element of db_l and (l ==
+// L-1) of the last layer's sums, then (l == 1, dslope wanted) one workgroup for dslope
+__global__ __launch_bounds__(256) void head_stack_bwd_kernel(WdHeadStack P, int l) {
+    __shared__ SmallGemmLds<HEAD_G_TS> L;
+    __shared__ float red[256];
+    const StackLayout S = stack_layout(P);
+    const size_t plane = (size_t)P.B * P.Hf;
+    const int B = P.B, Hf = P.Hf, in = l == 1 ? P.F : Hf;
+    const float *dz = S.dz + (l - 1) * plane;
+    const float *prev = l == 1 ? P.x : S.z + (l - 2) * plane;  // site l-1's stored values
+    const long long ldp = l == 1 ? P.ld_x : Hf;
+    const SmallGemm GX{dz, Hf, 1, P.W[l - 1], in, 1, nullptr, l == 1 ? P.dx : S.dz + (l - 2) * plane, ldp, B, in, Hf};
+    const SmallGemm GW{dz, 1, Hf, prev, ldp, 1, nullptr, P.dW[l - 1], in, Hf, in, B};
+    const int n1 = head_tiles(GX.M, GX.N, HEAD_H_TS), n2 = head_tiles(GW.M, GW.N, HEAD_G_TS);
+    const int b = blockIdx.x;
+    if (b < n1 + n2) {
+        with_act(l == 1 ? (int)ACT_IDENTITY : P.act, [&](auto act_c) {
+            constexpr int ACT = decltype(act_c)::value;
+            const StackSite<ACT> site{stack_slope(P.slope, P.act), P.p, P.seed, (uint32_t)(l - 1)};
+            SgIdentity id;
+            if (b >= n1) {
+                small_gemm_tile_f<HEAD_G_TS, false, true>(GW, b - n1, L, id, site, id);
+                return;
+            }
+            StackDz<ACT> dzf{site, prev, ldp, 0.f};
+            small_gemm_tile_f<HEAD_H_TS, true, true>(GX, b, *reinterpret_cast<SmallGemmLds<HEAD_H_TS> *>(&L), id, id, dzf);
+            if (ACT == ACT_PRELU) {  // the tile's dslope term: the 256 threads' terms in thread order
+                red[threadIdx.x] = dzf.part;
+                __syncthreads();
+                if (threadIdx.x == 0) {
+                    float t = 0.f;
+                    for (int e = 0; e < 256; ++e) t += red[e];
+                    S.spart[(size_t)(l - 2) * S.np + b] = t;
+                }
+            }
+        });
+        return;
+    }
+    const long long last = l == P.L - 1 ? stack_last_count(P.F, Hf, P.T, P.L) : 0;
+    const long long tail_blocks = (Hf + last + 255) / 256;
+    if (b - n1 - n2 >= tail_blocks) {
+        stack_slope_sum(P, S, red);
+        return;
+    }
+    const long long q = (long long)(b - n1 - n2) * 256 + threadIdx.x;
+    if (q < Hf) {
+        const float s = row_sum(dz + q, Hf, nullptr, 0, B);
+        if (P.db[l - 1]) P.db[l - 1][q] = s;
+    } else if (q - Hf < last) {
+        stack_last_sums(P, S, q - Hf);
+    }
+}
+
+// L == 1: dW_1, db_1 and the loss; dslope = 0 (no activation site)
+__global__ __launch_bounds__(256) void head_stack_last_kernel(WdHeadStack P) {
+    const StackLayout S = stack_layout(P);
+    const long long q = (long long)blockIdx.x * 256 + threadIdx.x, n = stack_last_count(P.F, P.Hf, P.T, 1);
+    if (q < n) stack_last_sums(P, S, q);
+    else if (q == n && P.dslope) P.dslope[0] = 0.f;
+}
+
+// prediction, one wave per row: out = act(z_{L-1}) W_L^T + b_L (L == 1: x W_1^T + b_1), then the output
+// kinds of head_predict_rows_kernel
+__global__ __launch_bounds__(256) void head_stack_predict_rows_kernel(WdHeadStackPredict P) {
+    __shared__ float osh[4][HEAD_MAX_T];
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6, row = blockIdx.x * 4 + wave;
+    if (row >= P.B) return;
+    const int L = P.L, T = P.T, Kin = L == 1 ? P.F : P.Hf;
+    const float *zin = L == 1 ? P.x + (size_t)row * P.ld_x
+                              : (const float *)P.scratch + ((size_t)(L - 2) * P.B + row) * P.Hf;
+    const float *W = P.W[L - 1], *bias = P.b[L - 1];
+    const float slope = stack_slope(P.slope, P.act);
+    float *os = osh[wave];
+    with_act(L == 1 ? (int)ACT_IDENTITY : P.act, [&](auto act_c) {
+        constexpr int ACT = decltype(act_c)::value;
+        for (int t = 0; t < T; ++t) {
+            const float *w = W + (size_t)t * Kin;
+            float s = 0.f;
+            for (int j = lane; j < Kin; j += 64) s = fmaf(w[j], act_fwd(ACT, zin[j], slope), s);
+            os[t] = wave_sum(s) + (bias ? bias[t] : 0.f);
+        }
+    });
+    if (lane >= T) return;
+    float v = os[lane];
+    if (P.out_kind == 1) {
+        v = 1.f / (1.f + expf(-v));
+    } else if (P.out_kind == 2) {
+        const int C = P.n_classes;
+        float m, e;
+        group_max_sum(os + (lane / C) * C, C, m, e);
+        v = expf(v - m) / e;
+    }
+    P.out[(size_t)row * T + lane] = v;
 }
 }  // namespace wd

@@ -2241,4 +2241,92 @@ int wdmpnn_scale(float *const *p, const int64_t *n, int32_t k, const float *s, v
     return 0;
 }
 
+// the checks wdmpnn_head_stack and wdmpnn_head_stack_predict share (Hf is unused when L == 1)
+static int head_stack_check(int B, int F, int Hf, int T, int L, int ld_x, int act, int kind, int n_classes,
+                            const float *const *W, const float *slope) {
+    if (L < 1) return fail(WD_ERR_SHAPE, "head stack: %d layers", L);
+    if (L > WD_HEAD_MAX_LAYERS) return fail(WD_ERR_UNSUPPORTED, "head stack: %d layers (at most %d)", L, WD_HEAD_MAX_LAYERS);
+    if (act == WD_ACT_PRELU) {
+        if (L > 1 && !slope) return fail(WD_ERR_ARG, "head stack: PReLU without its slope");
+        act = WD_ACT_RELU;  // (head_check's activation test is the two-layer head's)
+    }
+    if (L == 1 && act == WD_ACT_IDENTITY) act = WD_ACT_RELU;  // (one layer: no activation site)
+    WD_TRY(head_check(B, F, L == 1 ? 1 : Hf, T, ld_x, act, kind, n_classes));
+    for (int l = 0; l < L; ++l)
+        if (!W[l]) return fail(WD_ERR_ARG, "head stack: null weight %d", l);
+    return 0;
+}
+
+int wdmpnn_head_stack_scratch_bytes(int32_t B, int32_t F, int32_t Hf, int32_t T, int32_t L, size_t *bytes) {
+    if (!bytes) return fail(WD_ERR_ARG, "null bytes");
+    if (B < 0 || F <= 0 || T <= 0 || L < 1 || L > WD_HEAD_MAX_LAYERS || (L > 1 && Hf <= 0))
+        return fail(WD_ERR_SHAPE, "head stack: bad sizes");
+    *bytes = sizeof(float) * head_stack_floats(B, F, L == 1 ? 1 : Hf, T, L);
+    return 0;
+}
+
+int wdmpnn_head_stack(const WdHeadStack *h, void *stream) {
+    WD_KERNELS_OK();
+    if (!h) return fail(WD_ERR_ARG, "null head");
+    WD_TRY(head_stack_check(h->B, h->F, h->Hf, h->T, h->L, h->ld_x, h->act, h->loss_kind, h->n_classes, h->W, h->slope));
+    if (!(h->p >= 0.f && h->p < 1.f)) return fail(WD_ERR_ARG, "head stack: dropout %g outside [0, 1)", (double)h->p);
+    if (h->ld_table < 2 * (h->T / h->n_classes)) return fail(WD_ERR_SHAPE, "head: bad sizes (ld_table)");
+    for (int l = 0; l < h->L; ++l)
+        if (!h->dW[l]) return fail(WD_ERR_ARG, "head stack: null gradient %d", l);
+    if (!h->loss || !h->scratch || (h->B && (!h->x || !h->table || !h->dx)))
+        return fail(WD_ERR_ARG, "head stack: null pointer");
+    WdHeadStack P = *h;
+    if (P.L == 1) P.Hf = 1;
+    if (h->scratch_bytes < sizeof(float) * head_stack_floats(P.B, P.F, P.Hf, P.T, P.L))
+        return fail(WD_ERR_WORKSPACE, "head stack: scratch of %zu bytes, %zu needed", h->scratch_bytes,
+                    sizeof(float) * head_stack_floats(P.B, P.F, P.Hf, P.T, P.L));
+    if (P.B == 0) return 0;
+    hipStream_t st = (hipStream_t)stream;
+    const int B = P.B, F = P.F, Hf = P.Hf, L = P.L;
+    for (int l = 1; l < L; ++l) {
+        hipLaunchKernelGGL(head_stack_fwd_kernel, dim3(head_tiles(B, Hf, HEAD_H_TS)), dim3(256), 0, st, P, l);
+        WD_CHECK_LAUNCH("head_stack_fwd");
+    }
+    hipLaunchKernelGGL(head_stack_rows_kernel, dim3((B + 3) / 4), dim3(256), 0, st, P);
+    WD_CHECK_LAUNCH("head_stack_rows");
+    if (L == 1) {
+        const long long n = stack_last_count(F, Hf, P.T, 1) + 1;
+        hipLaunchKernelGGL(head_stack_last_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, P);
+        WD_CHECK_LAUNCH("head_stack_last");
+        return 0;
+    }
+    for (int l = L - 1; l >= 1; --l) {
+        const int in = l == 1 ? F : Hf;
+        const long long last = l == L - 1 ? stack_last_count(F, Hf, P.T, L) : 0;
+        const long long blocks = head_tiles(B, in, HEAD_H_TS) + head_tiles(Hf, in, HEAD_G_TS) + (Hf + last + 255) / 256 +
+                                 (l == 1 && P.dslope ? 1 : 0);
+        hipLaunchKernelGGL(head_stack_bwd_kernel, dim3((unsigned)blocks), dim3(256), 0, st, P, l);
+        WD_CHECK_LAUNCH("head_stack_bwd");
+    }
+    return 0;
+}
+
+int wdmpnn_head_stack_predict(const WdHeadStackPredict *h, void *stream) {
+    WD_KERNELS_OK();
+    if (!h) return fail(WD_ERR_ARG, "null head");
+    WD_TRY(head_stack_check(h->B, h->F, h->Hf, h->T, h->L, h->ld_x, h->act, h->out_kind, h->n_classes, h->W, h->slope));
+    if (h->B == 0) return 0;
+    if (!h->x || !h->out || (h->L > 1 && !h->scratch)) return fail(WD_ERR_ARG, "head stack: null pointer");
+    if (h->L > 1 && h->scratch_bytes < sizeof(float) * (size_t)(h->L - 1) * h->B * h->Hf)
+        return fail(WD_ERR_WORKSPACE, "head stack: scratch of %zu bytes, %zu needed", h->scratch_bytes,
+                    sizeof(float) * (size_t)(h->L - 1) * h->B * h->Hf);
+    hipStream_t st = (hipStream_t)stream;
+    WdHeadStack v{};  // head_stack_fwd_kernel's view (no dropout; z_l at the start of the scratch)
+    v.x = h->x; v.ld_x = h->ld_x; v.B = h->B; v.F = h->F; v.Hf = h->Hf; v.T = h->T; v.L = h->L;
+    for (int l = 0; l < h->L; ++l) { v.W[l] = h->W[l]; v.b[l] = h->b[l]; }
+    v.slope = h->slope; v.act = h->act; v.scratch = h->scratch;
+    for (int l = 1; l < h->L; ++l) {
+        hipLaunchKernelGGL(head_stack_fwd_kernel, dim3(head_tiles(h->B, h->Hf, HEAD_H_TS)), dim3(256), 0, st, v, l);
+        WD_CHECK_LAUNCH("head_stack_fwd");
+    }
+    hipLaunchKernelGGL(head_stack_predict_rows_kernel, dim3((h->B + 3) / 4), dim3(256), 0, st, *h);
+    WD_CHECK_LAUNCH("head_stack_predict_rows");
+    return 0;
+}
+
 }  // extern "C"
