@@ -497,6 +497,17 @@ typedef struct WdHeadStack {
  * loss terms [B], and (L - 1) x max(B, ceil(B / 16) ceil(Hf / 16)) partial sums of dslope. */
 int wdmpnn_head_stack_scratch_bytes(int32_t B, int32_t F, int32_t Hf, int32_t T, int32_t L, size_t *bytes);
 int wdmpnn_head_stack(const WdHeadStack *h, void *stream);
+/* The same head for a partly frozen model: any subset of the gradients.  Same struct, forward, losses, dropout
+ * hash and scratch as wdmpnn_head_stack; dx, every dW[l], every db[l] and dslope may each be NULL ("not
+ * wanted"), independently.  loss is always written.  Every wanted output is bitwise what wdmpnn_head_stack
+ * writes for it (fixed summation orders: no output depends on which others are computed).  What nobody wants
+ * is not launched: the dz chain runs down to level 0 only for dx, to level 1 for PReLU's dslope, else to the
+ * first layer with a wanted dW or db; a layer's dW tiles, its db sums and the dz tiles below that level take no
+ * workgroups; a launch left with nothing is dropped, and when no launch of a layer below L remains, dW_L, db_L
+ * and the loss get a small launch of their own.  Nothing is read or written through a NULL pointer; the scratch
+ * regions of skipped levels stay unused.  Refusals: those of wdmpnn_head_stack but for its null-gradient ones
+ * (W, loss, scratch, and with B > 0 x and table, are still required).  B == 0 is a no-op. */
+int wdmpnn_head_stack_partial(const WdHeadStack *h, void *stream);
 /* The same stack at prediction time (eval mode: no dropout) in L launches, with the output kinds of
  * WdHeadPredict.  scratch: (L - 1) B Hf floats (the z_l), at least scratch_bytes of them given. */
 typedef struct WdHeadStackPredict {

@@ -44,7 +44,8 @@ EXPORTED_SYMBOLS = ('wdmpnn_abi_version', 'wdmpnn_last_error', 'wdmpnn_workspace
                     'wdmpnn_forward_many', 'wdmpnn_feed_slot_bytes', 'wdmpnn_feed_create', 'wdmpnn_feed_next',
                     'wdmpnn_feed_release', 'wdmpnn_feed_forward_workspace_bytes', 'wdmpnn_feed_forward',
                     'wdmpnn_feed_destroy', 'wdmpnn_adam_step_repack', 'wdmpnn_self_check', 'wdmpnn_head_predict',
-                    'wdmpnn_head_stack_scratch_bytes', 'wdmpnn_head_stack', 'wdmpnn_head_stack_predict')
+                    'wdmpnn_head_stack_scratch_bytes', 'wdmpnn_head_stack', 'wdmpnn_head_stack_predict',
+                    'wdmpnn_head_stack_partial')
 HEAD_MAX_LAYERS = 6  # WD_HEAD_MAX_LAYERS
 
 
@@ -203,6 +204,7 @@ def lib() -> ctypes.CDLL:
     L.wdmpnn_head_predict.argtypes = [POINTER(WdHeadPredict), c_void_p]
     L.wdmpnn_head_stack_scratch_bytes.argtypes = [c_int32, c_int32, c_int32, c_int32, c_int32, POINTER(c_size_t)]
     L.wdmpnn_head_stack.argtypes = [POINTER(WdHeadStack), c_void_p]
+    L.wdmpnn_head_stack_partial.argtypes = [POINTER(WdHeadStack), c_void_p]
     L.wdmpnn_head_stack_predict.argtypes = [POINTER(WdHeadStackPredict), c_void_p]
     L.wdmpnn_forward_many.argtypes = [c_int32, POINTER(WdGraph), POINTER(WdParams), POINTER(WdConfig),
                                       POINTER(c_void_p), POINTER(c_size_t), POINTER(c_void_p), c_void_p]
@@ -230,7 +232,8 @@ def lib() -> ctypes.CDLL:
             ('wdmpnn_forward_many', 'wdmpnn_feed_slot_bytes', 'wdmpnn_feed_create', 'wdmpnn_feed_next',
              'wdmpnn_feed_release', 'wdmpnn_feed_forward_workspace_bytes', 'wdmpnn_feed_forward',
              'wdmpnn_feed_destroy', 'wdmpnn_adam_step_repack', 'wdmpnn_head_predict',
-             'wdmpnn_head_stack_scratch_bytes', 'wdmpnn_head_stack', 'wdmpnn_head_stack_predict'):
+             'wdmpnn_head_stack_scratch_bytes', 'wdmpnn_head_stack', 'wdmpnn_head_stack_predict',
+             'wdmpnn_head_stack_partial'):
         getattr(L, fn).restype = c_int
     v = L.wdmpnn_abi_version()
     if v != ABI_VERSION:

@@ -42,6 +42,7 @@ class TrainArgs:
     checkpoint_frzn: Optional[str] = None
     freeze_first_only: bool = False
     frzn_ffn_layers: int = 0
+    frzn_encoder: bool = False           # (run_training.py:287-291's --frzn_encoder; cli.apply_freezing)
     polymer: bool = False
     # optimizer (args.py:397-407, utils.py:295-310)
     init_lr: float = 1e-4

@@ -55,7 +55,7 @@ from .graph_io import load_graphs
 from .model import MoleculeModel
 from .nn_utils import initialize_weights
 from .polymer import split_polymer_string, parse_polymer_rules
-from .train import NoamLR, build_optimizer, get_loss_func, train_step
+from .train import NoamLR, _predict_head, build_optimizer, frozen_encodings, get_loss_func, head_predict, train_step
 
 
 class StandardScaler:
@@ -126,6 +126,70 @@ def load_checkpoint(path: str, device=None):
     model = MoleculeModel(args)
     model.load_state_dict(sd)
     return model.to(args.device)
+
+
+def load_frzn_checkpoint(model, path: str, log=None) -> tuple:
+    """``--checkpoint_frzn`` (run_training.py:271-285): copy into ``model`` every tensor of the checkpoint at
+    ``path`` whose name and shape match one of the model's (``strict=False`` semantics); returns (names loaded,
+    names skipped) and reports both through ``log``.  The file is read with ``weights_only=True``; its weights
+    are under ``state_dict`` (this package's and the reference's ``save_checkpoint``, utils.py:47-73) or
+    ``model_state_dict`` (the fork's pretraining files, run_training.py:275); ``encoder.encoder.W*`` names of
+    older checkpoints are remapped as in ``load_checkpoint``.  ``ValueError`` when nothing matches.  Loading
+    freezes nothing: that is ``apply_freezing``."""
+    log = log or (lambda msg: print(msg, file=sys.stderr))
+    state = torch.load(path, map_location='cpu', weights_only=True)
+    sd = None
+    if isinstance(state, dict):
+        sd = state.get('state_dict', state.get('model_state_dict'))
+    if not isinstance(sd, dict):
+        raise ValueError(f'{path} is not a checkpoint (no state_dict or model_state_dict)')
+    sd = {re.sub(r'^encoder\.encoder\.([Wc])', r'encoder.encoder.0.\1', k): v for k, v in sd.items()}
+    own = model.state_dict()
+    loaded, skipped = [], []
+    for name, t in sd.items():
+        if not isinstance(t, torch.Tensor) or name not in own:
+            skipped.append(name)
+            log(f'checkpoint_frzn: skipped {name} (no such parameter in the model)')
+        elif tuple(own[name].shape) != tuple(t.shape):
+            skipped.append(name)
+            log(f'checkpoint_frzn: skipped {name} (shape {tuple(t.shape)}, the model has {tuple(own[name].shape)})')
+        else:
+            loaded.append(name)
+    if not loaded:
+        raise ValueError(f'{path}: no tensor matches the model by name and shape')
+    model.load_state_dict({k: sd[k] for k in loaded}, strict=False)
+    log(f'checkpoint_frzn: loaded {len(loaded)} tensors from {path}: {", ".join(loaded)}')
+    return loaded, skipped
+
+
+def apply_freezing(model, frzn_encoder: bool = False, frzn_ffn_layers: int = 0) -> None:
+    """``--frzn_encoder`` / ``--frzn_ffn_layers N``.  ``frzn_encoder`` freezes every encoder parameter
+    (run_training.py:287-291).  ``frzn_ffn_layers = N > 0`` freezes the FIRST N ``Linear`` layers of the FFN,
+    weight and bias, and implies a frozen encoder: the documented meaning (args.py:430-435) and what
+    model.py:118-121 aims at.  It is not run_training.py:302-305, whose loop freezes the LAST 2N tensors of the
+    FFN against its own help text; and unlike model.py's ``parameters()[0:2N]`` slice it counts Linear layers,
+    so a PReLU slope or a bias-free layer does not shift the cut.  ``N >= `` the FFN's Linear layers is a
+    ``ValueError`` (nothing would train).  With neither flag every parameter trains (run_training.py:277-285)."""
+    if frzn_ffn_layers < 0:
+        raise ValueError('--frzn_ffn_layers must not be negative')
+    linears = [m for m in model.ffn if isinstance(m, torch.nn.Linear)]
+    if frzn_ffn_layers >= len(linears) and frzn_ffn_layers > 0:
+        raise ValueError(f'--frzn_ffn_layers {frzn_ffn_layers}: the FFN has {len(linears)} Linear layers, and at '
+                         'least one must stay trainable')
+    if frzn_encoder or frzn_ffn_layers > 0:
+        for p in model.encoder.parameters():
+            p.requires_grad = False
+    for lin in linears[:frzn_ffn_layers]:
+        for p in lin.parameters():
+            p.requires_grad = False
+
+
+def subsample_train(n_train: int, frac: float, seed: int) -> List[int]:
+    """``--train_frac`` (run_training.py:132-137): the positions kept of a training split of ``n_train`` rows,
+    ``default_rng(seed).choice(n_train, int(n_train * frac), replace=False)``."""
+    if not 0 < frac <= 1:
+        raise ValueError('--train_frac must be in (0, 1]')
+    return np.random.default_rng(seed).choice(n_train, int(n_train * frac), replace=False).tolist()
 
 
 def load_scalers(path: str):
@@ -202,12 +266,18 @@ def evaluate_predictions(preds, targets, num_tasks: int, metrics: List[str], dat
     return out
 
 
-def predict(model, graphs, idx, batch_size: int, scaler: Optional[StandardScaler]) -> List[List[float]]:
-    """predict.py:10-68: eval, no_grad, batches in order, inverse scaling."""
+def predict(model, graphs, idx, batch_size: int, scaler: Optional[StandardScaler],
+            encodings: Optional[torch.Tensor] = None) -> List[List[float]]:
+    """predict.py:10-68: eval, no_grad, batches in order, inverse scaling.  ``encodings``: the rows of ``idx``
+    from ``frozen_encodings`` (a frozen encoder's outputs, computed once per run): the native prediction head
+    on them in place of the model's forward."""
     model.eval()
     preds = []
     with torch.no_grad():
         for s in range(0, len(idx), batch_size):
+            if encodings is not None:
+                preds.extend(head_predict(model, encodings[s:s + batch_size]).cpu().numpy().tolist())
+                continue
             g = BatchMolGraph([graphs[i] for i in idx[s:s + batch_size]])
             preds.extend(model([g]).cpu().numpy().tolist())
     if scaler is not None and preds:
@@ -281,6 +351,17 @@ def parse_args(argv=None) -> argparse.Namespace:
     ap.add_argument('--bias', action='store_true')
     ap.add_argument('--undirected', action='store_true')
     ap.add_argument('--gpu', type=int, default=0)
+    ap.add_argument('--weight_decay', type=float, default=0.0)
+    ap.add_argument('--optimizer', default='adam', choices=['adam', 'adamw'])
+    ap.add_argument('--checkpoint_frzn', default=None,
+                    help='pretrained checkpoint: every tensor that matches by name and shape is loaded')
+    ap.add_argument('--frzn_encoder', action='store_true', help='freeze every encoder parameter')
+    ap.add_argument('--frzn_ffn_layers', type=int, default=0,
+                    help='freeze the first N Linear layers of the FFN (implies --frzn_encoder)')
+    ap.add_argument('--train_frac', type=float, default=1.0,
+                    help='train on this fraction of the training split (drawn by --seed)')
+    ap.add_argument('--no_encoding_cache', action='store_true',
+                    help='run the frozen encoder every step instead of computing its encodings once')
     return ap.parse_args(argv)
 
 
@@ -311,9 +392,13 @@ def run_training(a: argparse.Namespace) -> Dict[str, list]:
                      aggregation=a.aggregation, aggregation_norm=a.aggregation_norm, bias=a.bias,
                      undirected=a.undirected, ffn_num_layers=a.ffn_num_layers,
                      ffn_hidden_size=a.ffn_hidden_size or a.hidden_size, dataset_type=a.dataset_type,
-                     num_tasks=num_tasks, multiclass_num_classes=a.multiclass_num_classes, device=device)
+                     num_tasks=num_tasks, multiclass_num_classes=a.multiclass_num_classes, device=device,
+                     frzn_encoder=bool(a.frzn_encoder or a.frzn_ffn_layers > 0), frzn_ffn_layers=a.frzn_ffn_layers,
+                     init_lr=a.init_lr, optimizer=a.optimizer, weight_decay=a.weight_decay)
     torch.manual_seed(a.pytorch_seed)
     train_idx, val_idx, test_idx = random_split(len(smiles), a.split_sizes, a.seed)
+    if a.train_frac != 1.0:  # run_training.py:132-137; the scaler below is fitted on the subsample
+        train_idx = [train_idx[k] for k in subsample_train(len(train_idx), a.train_frac, a.seed)]
     scaler = None
     train_targets = [targets[i] for i in train_idx]
     if a.dataset_type == 'regression':
@@ -323,8 +408,17 @@ def run_training(a: argparse.Namespace) -> Dict[str, list]:
                          for r in train_targets]
     model = MoleculeModel(args)
     initialize_weights(model)
+    if a.checkpoint_frzn is not None:
+        load_frzn_checkpoint(model, a.checkpoint_frzn)
+    apply_freezing(model, a.frzn_encoder, a.frzn_ffn_layers)
     model = model.to(device)
-    optimizer = build_optimizer(model, a.init_lr)
+    optimizer = build_optimizer(model, args)
+    # a frozen encoder without dropout gives every molecule the same encoding at every step: computed once per
+    # split, the steps and the per-epoch scores then run the head alone (train.frozen_encodings)
+    enc_cache = None
+    if args.frzn_encoder and a.dropout == 0 and not a.no_encoding_cache and _predict_head(model.eval()) is not None:
+        enc_cache = {name: frozen_encodings(model, [graphs[i] for i in idx], a.batch_size)
+                     for name, idx in (('train', train_idx), ('val', val_idx), ('test', test_idx))}
     scheduler = NoamLR(optimizer, warmup_epochs=[a.warmup_epochs], total_epochs=[a.epochs],
                        steps_per_epoch=len(train_idx) // a.batch_size, init_lr=[a.init_lr], max_lr=[a.max_lr],
                        final_lr=[a.final_lr])
@@ -342,13 +436,20 @@ def run_training(a: argparse.Namespace) -> Dict[str, list]:
             losses = []
             for s in range(0, len(order), a.batch_size):
                 pos = order[s:s + a.batch_size]
-                g = BatchMolGraph([graphs[train_idx[p]] for p in pos])
-                loss = train_step(model, [g], [train_targets[p] for p in pos], loss_func, optimizer, scheduler,
-                                  a.dataset_type, grad_clip=a.grad_clip)
+                if enc_cache is not None:
+                    rows = enc_cache['train'][torch.as_tensor(pos, device=device)]
+                    loss = train_step(model, None, [train_targets[p] for p in pos], loss_func, optimizer, scheduler,
+                                      a.dataset_type, grad_clip=a.grad_clip, encodings=rows)
+                else:
+                    g = BatchMolGraph([graphs[train_idx[p]] for p in pos])
+                    loss = train_step(model, [g], [train_targets[p] for p in pos], loss_func, optimizer, scheduler,
+                                      a.dataset_type, grad_clip=a.grad_clip)
                 losses.append(float(loss))
-            val_scores = evaluate_predictions(predict(model, graphs, val_idx, a.batch_size, scaler),
+            val_scores = evaluate_predictions(predict(model, graphs, val_idx, a.batch_size, scaler,
+                                                      enc_cache and enc_cache['val']),
                                               [targets[i] for i in val_idx], num_tasks, metrics, a.dataset_type)
-            tr_scores = evaluate_predictions(predict(model, graphs, train_idx, a.batch_size, scaler),
+            tr_scores = evaluate_predictions(predict(model, graphs, train_idx, a.batch_size, scaler,
+                                                     enc_cache and enc_cache['train']),
                                              [targets[i] for i in train_idx], num_tasks, metrics, a.dataset_type)
             w.writerow([epoch, float(np.mean(losses)) if losses else float('nan')] +
                        [float(np.nanmean(tr_scores[m])) if tr_scores[m] else float('nan') for m in metrics] +
@@ -361,7 +462,7 @@ def run_training(a: argparse.Namespace) -> Dict[str, list]:
     ckpt = torch.load(os.path.join(a.save_dir, 'best_model.pt'), map_location=device, weights_only=True)
     model.load_state_dict(ckpt['state_dict'])
     test_targets = [targets[i] for i in test_idx]
-    test_preds = predict(model, graphs, test_idx, a.batch_size, scaler)
+    test_preds = predict(model, graphs, test_idx, a.batch_size, scaler, enc_cache and enc_cache['test'])
     scores = evaluate_predictions(test_preds, test_targets, num_tasks, metrics, a.dataset_type)
     with open(os.path.join(a.save_dir, 'test_scores.json'), 'w') as f:
         json.dump(scores, f, indent=4, sort_keys=True)

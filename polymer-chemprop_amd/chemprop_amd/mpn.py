@@ -328,6 +328,22 @@ class MPNEncoder(nn.Module):
         out, ws, ws_bytes = _forward_call(gs, cfg, pstruct, self.hidden_size, device, pre_launch=pack)
         return out, (gs, cfg, pstruct, ws, ws_bytes, packed, dg)
 
+    def _frozen_forward(self, mol_graph):
+        """The forward of a frozen encoder inside a training step (``train.train_step``'s direct path for partly
+        frozen models): the inference call of :meth:`forward` (``save_for_backward = 0``, the same device graph,
+        config and launches as the autograd path takes when no parameter requires grad; the encoder's dropout,
+        when active, draws its seed here as there), on the cached weight pack, which for frozen parameters
+        outlives optimizer steps (:meth:`_packed_params`)."""
+        base = self._param_tuple()
+        device = base[0].device
+        dg = mol_graph.device_graph(device, self.atom_messages, self.bond_fdim, not self.bias)
+        dg.use_on(torch.cuda.current_stream(device))
+        gs = self._graph_struct(dg)
+        params = [_f32(t) for t in base[:6]] + [None, None, _f32(base[8])]
+        cfg = self._config(False)
+        pstruct, _ = self._packed_params(gs, cfg, params, device, cache=True)
+        return _forward_call(gs, cfg, pstruct, self.hidden_size, device)[0]
+
     def _train_pack_for(self, gs, cfg, params, device):
         """The direct training step's packed weights: one persistent buffer, rewritten by the optimizer's
         own pass when it is a :class:`train.HipAdam` step through ``wdmpnn_adam_step_repack`` (which then
@@ -523,9 +539,15 @@ class MPNEncoder(nn.Module):
         (parameter pointer, version counter, optimizer-step generation): fused optimizers update the
         weights without bumping version counters, so every ``Optimizer.step`` also bumps
         ``_OPT_STEPS``.  A training forward through autograd repacks and leaves no cache behind (the direct
-        step keeps its own persistent pack, :meth:`_train_pack_for`).  ``sid``: the raw
-        id of the current stream (the inference path's cheaper alternative to ``stream``)."""
-        key = (tuple((t.data_ptr(), t._version, id(t)) if t is not None else None for t in params), _OPT_STEPS[0],
+        step keeps its own persistent pack, :meth:`_train_pack_for`).  A frozen encoder (no parameter requires
+        grad) has no gradient for an optimizer to apply, so its key leaves the optimizer-step count out: one pack
+        serves every step of a fine-tuning run (parameter identity and version, ``load_state_dict`` and
+        :meth:`invalidate_packed_params` still drop it, and so does unfreezing: the count is back in the key).
+        ``sid``: the raw id of the current stream (the inference path's cheaper alternative to ``stream``)."""
+        # (the first test alone settles a trainable encoder: this runs once per inference forward)
+        frozen = not params[0].requires_grad and not any(t is not None and t.requires_grad for t in params)
+        key = (tuple((t.data_ptr(), t._version, id(t)) if t is not None else None for t in params),
+               -1 if frozen else _OPT_STEPS[0],
                self._parameters['cached_zero_vector'].data_ptr(), gs.atom_fdim, gs.bond_fdim, gs.desc_dim,
                gs.atom_messages, device, cfg.gemm_variant) if cache else None  # (it decides what the pack holds)
         cached = self._pack_cache if cache else None

@@ -528,10 +528,12 @@ def _scale_all(grads, gl: torch.Tensor) -> None:
 
 
 def _run_head_stack(x: torch.Tensor, head: _StackHead, tab_ptr: int, ld_table: int, inv_n: float, seed: int,
-                    grad_of: Callable):
+                    grad_of: Callable, want_dx: bool = True):
     """One ``wdmpnn_head_stack`` call on the encodings x [B][F] (contiguous): (loss, dx, the gradients in the
     order of ``head.params()``, None where the parameter is None).  ``grad_of(parameter)`` gives the buffer
-    each gradient is written into."""
+    each gradient is written into, or None for a gradient nobody wants (a frozen parameter); ``want_dx``:
+    whether d loss / d x is wanted (else dx is None).  With anything left out the call is
+    ``wdmpnn_head_stack_partial``: the same outputs, bitwise, and no launch or workgroup for the rest."""
     from . import _native
     dev = x.device
     B, F = x.shape
@@ -540,30 +542,36 @@ def _run_head_stack(x: torch.Tensor, head: _StackHead, tab_ptr: int, ld_table: i
     Hf = lin[0].out_features if L > 1 else 0
     nbytes = _native.head_stack_scratch_bytes(B, F, Hf, T, L)
     scratch = torch.empty(max(nbytes // 4, 4), dtype=torch.float32, device=dev)
-    dx = torch.empty_like(x)
+    dx = torch.empty_like(x) if want_dx else None
     loss = torch.empty((), dtype=torch.float32, device=dev)
     h = _native.WdHeadStack()
     h.x, h.ld_x, h.B, h.F, h.Hf, h.T, h.L = x.data_ptr(), F, B, F, Hf, T, L
     grads = []
+    partial = not want_dx
+    ptr = _native.ptr
     for i, l in enumerate(lin):
         gw = grad_of(l.weight)
-        h.W[i], h.dW[i] = l.weight.data_ptr(), gw.data_ptr()
+        h.W[i], h.dW[i] = l.weight.data_ptr(), ptr(gw)
         grads.append(gw)
+        partial = partial or gw is None
         gb = None
         if l.bias is not None:
             gb = grad_of(l.bias)
-            h.b[i], h.db[i] = l.bias.data_ptr(), gb.data_ptr()
+            h.b[i], h.db[i] = l.bias.data_ptr(), ptr(gb)
+            partial = partial or gb is None
         grads.append(gb)
     gs = None
     if head.slope is not None:
         gs = grad_of(head.slope)
-        h.slope, h.dslope = head.slope.data_ptr(), gs.data_ptr()
+        h.slope, h.dslope = head.slope.data_ptr(), ptr(gs)
+        partial = partial or gs is None
     grads.append(gs)
     h.table, h.ld_table, h.inv_n, h.act = tab_ptr, ld_table, float(inv_n), head.act
     h.p, h.seed, h.loss_kind, h.n_classes = head.p, seed, head.kind, head.n_classes
     h.scratch, h.scratch_bytes = scratch.data_ptr(), scratch.numel() * 4
-    h.dx, h.loss = dx.data_ptr(), loss.data_ptr()
-    _native.check(_native.lib().wdmpnn_head_stack(ctypes.byref(h), _native.current_stream(dev)), 'FFN head stack + loss')
+    h.dx, h.loss = ptr(dx), loss.data_ptr()
+    entry = _native.lib().wdmpnn_head_stack_partial if partial else _native.lib().wdmpnn_head_stack
+    _native.check(entry(ctypes.byref(h), _native.current_stream(dev)), 'FFN head stack + loss')
     return loss, dx, grads
 
 
@@ -573,8 +581,11 @@ class _HeadStack(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, x, head, table, inv_n, seed, *params):
+        # only the gradients autograd will ask for (a frozen parameter, a frozen encoder's output: none)
+        need = ctx.needs_input_grad
+        wanted = {id(t) for t, n in zip(params, need[5:]) if t is not None and n}
         loss, dx, grads = _run_head_stack(x.contiguous(), head, table.data_ptr(), table.shape[1], inv_n, seed,
-                                          torch.empty_like)
+                                          lambda t: torch.empty_like(t) if id(t) in wanted else None, need[0])
         ctx.grads = [dx] + grads
         return loss
 
@@ -749,12 +760,113 @@ def _all_trainable(mod: nn.Module, skip, ids: list) -> bool:
     return True
 
 
-def _direct_step(model, enc, graph, head, target_batch, target_weights, data_weights, bucket=None) -> torch.Tensor:
+def _collect_parameters(mod: nn.Module, skip, out: dict) -> None:
+    """id -> parameter of ``mod`` and its submodules (but ``skip``), from the raw module dicts (``_all_trainable``)."""
+    for p in mod._parameters.values():
+        if p is not None and p is not skip:
+            out[id(p)] = p
+    for m in mod._modules.values():
+        if m is not None:
+            _collect_parameters(m, skip, out)
+
+
+class _FrozenPlan:
+    """A partly frozen model the direct step runs (``_frozen_plan``): the encoder, whether all of it is frozen,
+    the FFN as a :class:`_StackHead` (kind set) and the frozen parameters (their ``.grad`` is set to None)."""
+    __slots__ = ('enc', 'enc_frozen', 'head', 'frozen')
+
+    def __init__(self, enc, enc_frozen, head, frozen):
+        self.enc, self.enc_frozen, self.head, self.frozen = enc, enc_frozen, head, frozen
+
+    def grad_of(self, p: torch.Tensor) -> Optional[torch.Tensor]:
+        return _grad_buffer(p) if p.requires_grad else None
+
+
+def _frozen_plan(model: nn.Module, mol_batch, features_batch, head, cached: bool = False) -> Optional[_FrozenPlan]:
+    """The plan of a direct step on a model with frozen parameters, else None.  The conditions of
+    ``_direct_encoder`` on the model, the encoder and the batch (``cached``: the step runs from cached encodings
+    and has no batch), with these in place of "every parameter trainable": every parameter belongs to the
+    encoder or to an FFN ``_ffn_structure`` recognises (the two-layer head runs as a stack head here: the one
+    entry point that leaves gradients out), the encoder's parameters are all frozen or all trainable, and at
+    least one parameter is frozen (any subset of the FFN's weights, biases and slope may be).  ``head`` is
+    ``_fusable_head``'s answer: it gives the loss kind.  A partly frozen encoder (``freeze_first_only``) is not
+    a plan: such a model keeps the autograd path."""
+    from .model import MoleculeModel
+    from .mpn import MPNEncoder
+    if head is None or not isinstance(model, MoleculeModel) or type(model).forward is not MoleculeModel.forward:
+        return None
+    mpn = model.encoder
+    if features_batch is not None or mpn.features_only or mpn.use_input_features or mpn.atom_descriptors or \
+            len(mpn.encoder) != 1:
+        return None
+    if not cached and (not isinstance(mol_batch, (list, tuple)) or len(mol_batch) != 1 or
+                       type(mol_batch[0]).__name__ != 'BatchMolGraph'):
+        return None
+    enc = mpn.encoder[0]
+    if type(enc) is not MPNEncoder or enc.depth < 2 or enc.atom_messages or hasattr(enc, 'atom_descriptors_layer'):
+        return None
+    if isinstance(head, _StackHead):
+        st = head
+    else:
+        st = _ffn_structure(model.ffn, model.training)
+        if st is None:
+            return None
+        st = st.with_kind(head[3], head[4])
+    head_params = [t for t in st.params() if t is not None]  # (devices and dtypes: checked by _fusable_head)
+    enc_params = [t for _, t in enc._direct_names()]
+    known = {id(t) for t in enc_params} | {id(t) for t in head_params}
+    every = {}
+    _collect_parameters(model, enc.cached_zero_vector, every)
+    if set(every) != known:
+        return None
+    n_train = sum(t.requires_grad for t in enc_params)
+    if n_train not in (0, len(enc_params)):
+        return None
+    frozen = [t for t in every.values() if not t.requires_grad]
+    if not frozen:
+        return None
+    return _FrozenPlan(enc, n_train == 0, st, frozen)
+
+
+def frozen_encodings(model: nn.Module, graphs: Sequence, batch_size: int) -> torch.Tensor:
+    """The encodings ``[len(graphs)][F]`` of a list of ``MolGraph`` under the frozen encoder of ``model``, in
+    batches of ``batch_size`` through ``MPNEncoder.forward_many``: with a frozen encoder and no encoder dropout a
+    molecule's encoding is the same at every step, so a fine-tuning run computes it once and passes the rows of
+    each batch to ``train_step(encodings=...)`` / ``head_predict``.  ``ValueError`` when any encoder parameter
+    requires grad or the encoder's dropout would be active in training mode (``dropout > 0``)."""
+    from .featurization import BatchMolGraph
+    mpn = model.encoder
+    if mpn.features_only or len(mpn.encoder) != 1:
+        raise ValueError('frozen_encodings: one message-passing encoder expected')
+    enc = mpn.encoder[0]
+    if any(p.requires_grad for p in enc.parameters()):
+        raise ValueError('frozen_encodings: the encoder has trainable parameters (its encodings change every step)')
+    if enc.dropout > 0:
+        raise ValueError(f'frozen_encodings: encoder dropout {enc.dropout} would be active while training '
+                         '(the encodings differ from step to step)')
+    dev = enc.W_i.weight.device
+    if not len(graphs):
+        return torch.empty((0, enc.hidden_size), dtype=torch.float32, device=dev)
+    batches = [BatchMolGraph(list(graphs[s:s + batch_size])) for s in range(0, len(graphs), batch_size)]
+    outs = []
+    with torch.no_grad():
+        for s in range(0, len(batches), 8):  # (forward_many launches once per 8 batches; their workspaces are live together)
+            outs += enc.forward_many(batches[s:s + 8])
+    return torch.cat(outs, dim=0)
+
+
+def _direct_step(model, enc, graph, head, target_batch, target_weights, data_weights, bucket=None,
+                 plan: _FrozenPlan = None, encodings: torch.Tensor = None) -> torch.Tensor:
     """Forward, loss and every gradient of a fused-head step without the autograd engine: the encoder's
     training forward, wdmpnn_head_mse (loss, d loss / d encoding, the head's gradients) and the encoder's
     backward on that gradient (the incoming gradient of the loss is 1), each written straight into the
     parameters' .grad buffers.  The same launches as the autograd path minus its host gaps (the engine
-    hand-off, the gradient-seed fill and the scale by 1; profiles/round3_*)."""
+    hand-off, the gradient-seed fill and the scale by 1; profiles/round3_*).
+    With ``plan`` (a partly frozen model, ``_frozen_plan``) the head leaves out the frozen parameters' gradients
+    (``wdmpnn_head_stack_partial``) and sets their ``.grad`` to None; a frozen encoder runs its inference
+    forward on a pack that outlives optimizer steps (``MPNEncoder._frozen_forward``), the head computes no dx and
+    there is no encoder backward.  ``encodings`` (frozen encoder only): this batch's rows of
+    ``frozen_encodings`` in place of the forward."""
     from . import _native
     stack = isinstance(head, _StackHead)
     if stack:
@@ -762,7 +874,13 @@ def _direct_step(model, enc, graph, head, target_batch, target_weights, data_wei
     else:
         l1, l2, act, kind, n_classes = head
     nc = n_classes if kind == 2 else 0  # (multiclass: _loss_table checks the class indices on the host)
-    out, state = enc._train_forward(graph)
+    enc_frozen = plan is not None and plan.enc_frozen
+    if encodings is not None:
+        out = encodings
+    elif enc_frozen:
+        out = enc._frozen_forward(graph)
+    else:
+        out, state = enc._train_forward(graph)
     # the loss table read by the head kernel straight from its pinned host buffer (no copy launch in the
     # step: the copy kernel and its gap were ~10 us, profiles/round4_train_kernel_trace_v1.txt)
     zc, n_t, n_mask, tshape = _loss_table(target_batch, target_weights, data_weights, out.device, zero_copy=True,
@@ -780,7 +898,8 @@ def _direct_step(model, enc, graph, head, target_batch, target_weights, data_wei
     inv_n = 1.0 / n_mask if n_mask else float('inf')
     dev = out.device
     if stack:
-        loss, dx, _ = _run_head_stack(out, head, tab_ptr, tshape[1], inv_n, _head_seed(head), _grad_buffer)
+        loss, dx, _ = _run_head_stack(out, head, tab_ptr, tshape[1], inv_n, _head_seed(head),
+                                      _grad_buffer if plan is None else plan.grad_of, not enc_frozen)
     else:
         B, F = out.shape
         Hf, T = l1.weight.shape[0], l2.weight.shape[0]
@@ -801,14 +920,19 @@ def _direct_step(model, enc, graph, head, target_batch, target_weights, data_wei
         zc[1].record(torch.cuda.current_stream(dev))  # (the pinned buffer's last reader)
     if bucket is not None:  # the head's gradients are enqueued: their all-reduce overlaps the encoder backward
         bucket.start_early()
-    enc._train_backward(state, dx, {n: _grad_buffer(p) for n, p in enc._direct_names()})
+    if plan is not None:
+        for p in plan.frozen:  # (as zero_grad(set_to_none=True) on the autograd path: the optimizer skips them)
+            p.grad = None
+    if not enc_frozen:
+        enc._train_backward(state, dx, {n: _grad_buffer(p) for n, p in enc._direct_names()})
     return loss
 
 
 def train_step(model: nn.Module, mol_batch, target_batch, loss_func: Callable, optimizer: Optimizer,
                scheduler: _LRScheduler = None, dataset_type: str = 'regression', features_batch=None,
                target_weights=None, data_weights=None, grad_clip: float = None,
-               bucket: GradBucket = None, fused_head: bool = True, direct: bool = True) -> torch.Tensor:
+               bucket: GradBucket = None, fused_head: bool = True, direct: bool = True,
+               encodings: torch.Tensor = None) -> torch.Tensor:
     """One optimisation step (train.py:55-86).  With ``bucket`` the gradients are averaged over the
     data-parallel ranks (one all-reduce) before clipping and the optimizer step.  ``fused_head``: the
     default regression / classification / multiclass head + loss run as ``wdmpnn_head_mse`` (same loss and gradients within fp32
@@ -818,12 +942,42 @@ def train_step(model: nn.Module, mol_batch, target_batch, loss_func: Callable, o
     plain one-molecule encoder, skip the autograd engine (``_direct_step``: the same launches and results,
     bitwise, without the engine's host gaps).  The direct step keeps one packed copy of the encoder weights
     across steps (rewritten by :class:`HipAdam`); after writing an encoder parameter through ``.data`` call
-    ``MPNEncoder.invalidate_packed_params()`` (reassigned parameters and ``load_state_dict`` are detected)."""
+    ``MPNEncoder.invalidate_packed_params()`` (reassigned parameters and ``load_state_dict`` are detected).
+
+    Partly frozen models (fine-tuning: ``requires_grad = False`` on all of the encoder and / or on any of the
+    FFN's weights, biases and slope; ``_frozen_plan``) take the direct step too: the head computes only the
+    wanted gradients (``wdmpnn_head_stack_partial``, on the autograd path as well), a frozen encoder runs its
+    inference forward on a weight pack kept across optimizer steps with no backward, and the frozen
+    parameters' ``.grad`` is None after the step.  ``encodings``: this batch's rows of ``frozen_encodings``
+    (frozen encoder without dropout): the step is then the head and the optimizer alone, with the same result,
+    bitwise; ``mol_batch`` is not read."""
     if not model.training:  # (module.train() walks every submodule: the reference sets it once per epoch)
         model.train()
     head = _fusable_head(model, loss_func, dataset_type) if fused_head else None
-    enc = _direct_encoder(model, mol_batch, features_batch, head) if head is not None and direct else None
-    if enc is not None:
+    enc = _direct_encoder(model, mol_batch, features_batch, head) if head is not None and direct and \
+        encodings is None else None
+    plan = None
+    if enc is None and head is not None and bucket is None:
+        plan = _frozen_plan(model, mol_batch, features_batch, head, cached=encodings is not None)
+        if plan is not None:
+            head = plan.head  # (the stack head on either path: the same head arithmetic with and without autograd)
+    if encodings is not None:
+        if plan is None or not plan.enc_frozen or plan.enc.dropout > 0 or not direct:
+            raise ValueError('train_step(encodings=...) needs the direct step of a model with a frozen encoder without '
+                             'dropout and an FFN the native head runs')
+        l1 = plan.head.linears[0]
+        if encodings.dim() != 2 or encodings.shape[1] != l1.in_features or encodings.dtype != torch.float32 or \
+                encodings.device != l1.weight.device:
+            raise ValueError(f'encodings of shape {tuple(encodings.shape)} ({encodings.dtype}, {encodings.device}) for '
+                             f'an FFN input of {l1.in_features} on {l1.weight.device}')
+        encodings = encodings.detach().contiguous()
+    if plan is not None and not direct:
+        plan = None
+    if plan is not None:
+        enc = plan.enc if not plan.enc_frozen else None  # (HipAdam rewrites a trainable encoder's pack)
+        loss = _direct_step(model, plan.enc, None if encodings is not None else mol_batch[0], head, target_batch,
+                            target_weights, data_weights, None, plan, encodings)
+    elif enc is not None:
         # every trainable parameter's gradient is overwritten: no zeroing, no autograd
         if bucket is not None:
             bucket.attach()

@@ -1138,8 +1138,11 @@ __global__ __launch_bounds__(256) void scale_kernel(ScaleJobs J) {
 //   head_stack_bwd_kernel, l = L-1 .. 1:  dz_{l-1} = (dz_l W_l) drop_{l-1} act'(z_{l-1}) (l == 1: dx) with each
 //                                         tile's dslope term, dW_l = dz_l^T a_{l-1}, db_l; the launch of l = L-1
 //                                         adds dW_L, db_L and the loss, the launch of l = 1 sums dslope
-//   head_stack_last_kernel (L == 1 only): dW_1, db_1, the loss
-// 2 L - 1 launches (2 for L == 1).  Scratch (floats, wdmpnn_head_stack_scratch_bytes): z [L-1][B][Hf],
+//   head_stack_last_kernel (L == 1, or no backward launch left): dW_L, db_L, the loss
+// 2 L - 1 launches (2 for L == 1).  wdmpnn_head_stack_partial runs the same kernels for any subset of the
+// gradients (StackWant): the dz chain stops at the lowest level something needs, ranges nobody wants take no
+// workgroups, and head_stack_last_kernel carries the last layer's sums when no backward launch remains.
+// Scratch (floats, wdmpnn_head_stack_scratch_bytes): z [L-1][B][Hf],
 // dz [L-1][B][Hf], a_{L-1} [B][Kin], dout [B][T], lossrow [B], spart [L-1][np]: dslope's partial sums, for site
 // s < L-1 one per 16 x 16 tile of dz_s, for site L-1 one per row; np = max(B, tiles).
 // ------------------------------------------------------------------------------------------------
@@ -1216,28 +1219,41 @@ __global__ __launch_bounds__(256) void head_stack_fwd_kernel(WdHeadStack P, int 
     });
 }
 
-// The last layer's sums, one thread per element, rows in order: dW_L [T][Kin], db_L [T], the loss
+// What one call wants of the backward (wdmpnn_head_stack: everything but NULL biases and a NULL dslope;
+// wdmpnn_head_stack_partial: any subset).  By value with every launch; the kernels index their workgroups
+// and threads over the wanted ranges only.
+struct StackWant {
+    int dz;     // the row kernel: dz_{L-1} (L == 1: dx); launch l: the tiles of dz_{l-1} (l == 1: dx)
+    int dw;     // launch l: the tiles of dW_l
+    int db;     // launch l: db_l
+    int last;   // launch l carries the last layer's sums (the loss, and dW_L / db_L where wanted)
+    int slope;  // launch l ends with the workgroup that sums dslope
+};
+
+// The last layer's sums, one thread per element, rows in order: dW_L [T][Kin] and db_L [T] where wanted, the loss
+__host__ __device__ inline long long stack_last_count(const WdHeadStack &P) {
+    const long long T = P.T, Kin = P.L == 1 ? P.F : P.Hf;
+    return (P.dW[P.L - 1] ? T * Kin : 0) + (P.db[P.L - 1] ? T : 0) + 1;
+}
 __device__ __forceinline__ void stack_last_sums(const WdHeadStack &P, const StackLayout &S, long long q) {
     const int T = P.T, B = P.B, Kin = P.L == 1 ? P.F : P.Hf;
-    if (q < (long long)T * Kin) {
+    const long long nw = P.dW[P.L - 1] ? (long long)T * Kin : 0, nb = P.db[P.L - 1] ? T : 0;
+    if (q < nw) {
         const int t = (int)(q / Kin), j = (int)(q % Kin);
         P.dW[P.L - 1][q] = row_sum(S.dout + t, T, S.alast + j, Kin, B);
-    } else if (q < (long long)T * Kin + T) {
-        const int t = (int)(q - (long long)T * Kin);
-        const float s = row_sum(S.dout + t, T, nullptr, 0, B);
-        if (P.db[P.L - 1]) P.db[P.L - 1][t] = s;
-    } else if (q == (long long)T * Kin + T) {
+    } else if (q < nw + nb) {
+        const int t = (int)(q - nw);
+        P.db[P.L - 1][t] = row_sum(S.dout + t, T, nullptr, 0, B);
+    } else if (q == nw + nb) {
         P.loss[0] = row_sum(S.lossrow, 1, nullptr, 0, B) * P.inv_n;
     }
-}
-__host__ __device__ inline long long stack_last_count(int F, int Hf, int T, int L) {
-    return (long long)T * (L == 1 ? F : Hf) + T + 1;
 }
 
 // One wave per row: a_{L-1} = drop_{L-1}(act(z_{L-1})) (L == 1: drop_0(x)) into S.alast, out = a_{L-1} W_L^T +
 // b_L into the wave's LDS row, the loss terms and dout as head_rows_kernel / head_rows_ce_kernel, then
-// dz_{L-1} = (dout W_L) drop_{L-1} act'(z_{L-1}) (L == 1: dx) and the row's dslope term
-__global__ __launch_bounds__(256) void head_stack_rows_kernel(WdHeadStack P) {
+// dz_{L-1} = (dout W_L) drop_{L-1} act'(z_{L-1}) (L == 1: dx) and the row's dslope term (want_dz; without it
+// neither is computed or written, and P.dx may be NULL)
+__global__ __launch_bounds__(256) void head_stack_rows_kernel(WdHeadStack P, int want_dz) {
     __shared__ float dsh[4][HEAD_MAX_T];
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6, row = blockIdx.x * 4 + wave;
     if (row >= P.B) return;
@@ -1245,7 +1261,8 @@ __global__ __launch_bounds__(256) void head_stack_rows_kernel(WdHeadStack P) {
     const int L = P.L, T = P.T, Kin = L == 1 ? P.F : P.Hf;
     const int C = P.loss_kind == 2 ? P.n_classes : 1, K = T / C;
     const float *zin = L == 1 ? P.x + (size_t)row * P.ld_x : S.z + ((size_t)(L - 2) * P.B + row) * P.Hf;
-    float *dzo = L == 1 ? P.dx + (size_t)row * P.ld_x : S.dz + ((size_t)(L - 2) * P.B + row) * P.Hf;
+    float *dzo = !want_dz ? nullptr
+                 : L == 1 ? P.dx + (size_t)row * P.ld_x : S.dz + ((size_t)(L - 2) * P.B + row) * P.Hf;
     float *a = S.alast + (size_t)row * Kin;
     const float *W = P.W[L - 1], *bias = P.b[L - 1];
     const float *tab = P.table + (size_t)row * P.ld_table;
@@ -1294,6 +1311,7 @@ __global__ __launch_bounds__(256) void head_stack_rows_kernel(WdHeadStack P) {
         }
         if (lane < T) S.dout[(size_t)row * T + lane] = ds[lane];
         if (lane == 0) S.lossrow[row] = l;
+        if (!want_dz) return;
         float sp = 0.f;
         for (int j = lane; j < Kin; j += 64) {
             float g = 0.f;
@@ -1332,9 +1350,18 @@ __device__ __forceinline__ void stack_slope_sum(const WdHeadStack &P, const Stac
     }
 }
 
-// Layer l < L: tiles of dz_{l-1} (l == 1: dx), then tiles of dW_l, then one thread per element of db_l and (l ==
-// L-1) of the last layer's sums, then (l == 1, dslope wanted) one workgroup for dslope
-__global__ __launch_bounds__(256) void head_stack_bwd_kernel(WdHeadStack P, int l) {
+// Layer l < L, the ranges that Q wants, in this order: tiles of dz_{l-1} (l == 1: dx), tiles of dW_l, one thread
+// per element of db_l and of the last layer's sums, one workgroup for dslope.  A range that is not wanted takes
+// no workgroups: the grid is stack_bwd_blocks, and blockIdx is read against the same counts.
+__host__ __device__ inline long long stack_bwd_tail_blocks(const WdHeadStack &P, const StackWant &Q) {
+    return ((Q.db ? P.Hf : 0) + (Q.last ? stack_last_count(P) : 0) + 255) / 256;
+}
+__host__ __device__ inline long long stack_bwd_blocks(const WdHeadStack &P, int l, const StackWant &Q) {
+    const int in = l == 1 ? P.F : P.Hf;
+    return (Q.dz ? head_tiles(P.B, in, HEAD_H_TS) : 0) + (Q.dw ? head_tiles(P.Hf, in, HEAD_G_TS) : 0) +
+           stack_bwd_tail_blocks(P, Q) + (Q.slope ? 1 : 0);
+}
+__global__ __launch_bounds__(256) void head_stack_bwd_kernel(WdHeadStack P, int l, StackWant Q) {
     __shared__ SmallGemmLds<HEAD_G_TS> L;
     __shared__ float red[256];
     const StackLayout S = stack_layout(P);
@@ -1345,7 +1372,7 @@ __global__ __launch_bounds__(256) void head_stack_bwd_kernel(WdHeadStack P, int 
     const long long ldp = l == 1 ? P.ld_x : Hf;
     const SmallGemm GX{dz, Hf, 1, P.W[l - 1], in, 1, nullptr, l == 1 ? P.dx : S.dz + (l - 2) * plane, ldp, B, in, Hf};
     const SmallGemm GW{dz, 1, Hf, prev, ldp, 1, nullptr, P.dW[l - 1], in, Hf, in, B};
-    const int n1 = head_tiles(GX.M, GX.N, HEAD_H_TS), n2 = head_tiles(GW.M, GW.N, HEAD_G_TS);
+    const int n1 = Q.dz ? head_tiles(GX.M, GX.N, HEAD_H_TS) : 0, n2 = Q.dw ? head_tiles(GW.M, GW.N, HEAD_G_TS) : 0;
     const int b = blockIdx.x;
     if (b < n1 + n2) {
         with_act(l == 1 ? (int)ACT_IDENTITY : P.act, [&](auto act_c) {
@@ -1370,25 +1397,24 @@ __global__ __launch_bounds__(256) void head_stack_bwd_kernel(WdHeadStack P, int 
         });
         return;
     }
-    const long long last = l == P.L - 1 ? stack_last_count(P.F, Hf, P.T, P.L) : 0;
-    const long long tail_blocks = (Hf + last + 255) / 256;
-    if (b - n1 - n2 >= tail_blocks) {
-        stack_slope_sum(P, S, red);
+    if (b - n1 - n2 >= stack_bwd_tail_blocks(P, Q)) {
+        if (Q.slope) stack_slope_sum(P, S, red);
         return;
     }
+    const long long ndb = Q.db ? Hf : 0, last = Q.last ? stack_last_count(P) : 0;
     const long long q = (long long)(b - n1 - n2) * 256 + threadIdx.x;
-    if (q < Hf) {
-        const float s = row_sum(dz + q, Hf, nullptr, 0, B);
-        if (P.db[l - 1]) P.db[l - 1][q] = s;
-    } else if (q - Hf < last) {
-        stack_last_sums(P, S, q - Hf);
+    if (q < ndb) {
+        P.db[l - 1][q] = row_sum(dz + q, Hf, nullptr, 0, B);
+    } else if (q - ndb < last) {
+        stack_last_sums(P, S, q - ndb);
     }
 }
 
-// L == 1: dW_1, db_1 and the loss; dslope = 0 (no activation site)
+// The last layer's sums in a launch of their own, when no head_stack_bwd_kernel launch carries them (L == 1, or
+// nothing below the last layer wanted): dW_L, db_L and the loss; L == 1: dslope = 0 (no activation site)
 __global__ __launch_bounds__(256) void head_stack_last_kernel(WdHeadStack P) {
     const StackLayout S = stack_layout(P);
-    const long long q = (long long)blockIdx.x * 256 + threadIdx.x, n = stack_last_count(P.F, P.Hf, P.T, 1);
+    const long long q = (long long)blockIdx.x * 256 + threadIdx.x, n = stack_last_count(P);
     if (q < n) stack_last_sums(P, S, q);
     else if (q == n && P.dslope) P.dslope[0] = 0.f;
 }

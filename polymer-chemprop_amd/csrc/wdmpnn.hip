@@ -2265,15 +2265,12 @@ int wdmpnn_head_stack_scratch_bytes(int32_t B, int32_t F, int32_t Hf, int32_t T,
     return 0;
 }
 
-int wdmpnn_head_stack(const WdHeadStack *h, void *stream) {
-    WD_KERNELS_OK();
-    if (!h) return fail(WD_ERR_ARG, "null head");
-    WD_TRY(head_stack_check(h->B, h->F, h->Hf, h->T, h->L, h->ld_x, h->act, h->loss_kind, h->n_classes, h->W, h->slope));
+// wdmpnn_head_stack and wdmpnn_head_stack_partial after their own pointer checks: the shared checks, then the
+// launches for what the gradient pointers of *h want (NULL = not wanted)
+static int head_stack_run(const WdHeadStack *h, void *stream) {
     if (!(h->p >= 0.f && h->p < 1.f)) return fail(WD_ERR_ARG, "head stack: dropout %g outside [0, 1)", (double)h->p);
     if (h->ld_table < 2 * (h->T / h->n_classes)) return fail(WD_ERR_SHAPE, "head: bad sizes (ld_table)");
-    for (int l = 0; l < h->L; ++l)
-        if (!h->dW[l]) return fail(WD_ERR_ARG, "head stack: null gradient %d", l);
-    if (!h->loss || !h->scratch || (h->B && (!h->x || !h->table || !h->dx)))
+    if (!h->loss || !h->scratch || (h->B && (!h->x || !h->table)))
         return fail(WD_ERR_ARG, "head stack: null pointer");
     WdHeadStack P = *h;
     if (P.L == 1) P.Hf = 1;
@@ -2282,28 +2279,56 @@ int wdmpnn_head_stack(const WdHeadStack *h, void *stream) {
                     sizeof(float) * head_stack_floats(P.B, P.F, P.Hf, P.T, P.L));
     if (P.B == 0) return 0;
     hipStream_t st = (hipStream_t)stream;
-    const int B = P.B, F = P.F, Hf = P.Hf, L = P.L;
+    const int B = P.B, Hf = P.Hf, L = P.L;
+    // the lowest level m whose dz something needs (dz_0 = dx): 0 for dx, 1 for PReLU's dslope (every site has a
+    // term), else the first layer with a wanted dW or db; L when only the loss is left
+    int m = L;
+    for (int l = L; l >= 1; --l)
+        if (P.dW[l - 1] || P.db[l - 1]) m = l;
+    if (P.dslope && P.act == WD_ACT_PRELU && L > 1) m = 1;
+    if (P.dx) m = 0;
     for (int l = 1; l < L; ++l) {
         hipLaunchKernelGGL(head_stack_fwd_kernel, dim3(head_tiles(B, Hf, HEAD_H_TS)), dim3(256), 0, st, P, l);
         WD_CHECK_LAUNCH("head_stack_fwd");
     }
-    hipLaunchKernelGGL(head_stack_rows_kernel, dim3((B + 3) / 4), dim3(256), 0, st, P);
+    hipLaunchKernelGGL(head_stack_rows_kernel, dim3((B + 3) / 4), dim3(256), 0, st, P, m <= L - 1 ? 1 : 0);
     WD_CHECK_LAUNCH("head_stack_rows");
-    if (L == 1) {
-        const long long n = stack_last_count(F, Hf, P.T, 1) + 1;
-        hipLaunchKernelGGL(head_stack_last_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, P);
-        WD_CHECK_LAUNCH("head_stack_last");
-        return 0;
-    }
+    bool last_done = false;  // (the last layer's sums ride in the first backward launch there is)
     for (int l = L - 1; l >= 1; --l) {
-        const int in = l == 1 ? F : Hf;
-        const long long last = l == L - 1 ? stack_last_count(F, Hf, P.T, L) : 0;
-        const long long blocks = head_tiles(B, in, HEAD_H_TS) + head_tiles(Hf, in, HEAD_G_TS) + (Hf + last + 255) / 256 +
-                                 (l == 1 && P.dslope ? 1 : 0);
-        hipLaunchKernelGGL(head_stack_bwd_kernel, dim3((unsigned)blocks), dim3(256), 0, st, P, l);
+        StackWant Q{};
+        Q.dz = m <= l - 1;
+        Q.dw = P.dW[l - 1] != nullptr;
+        Q.db = P.db[l - 1] != nullptr;
+        Q.slope = l == 1 && P.dslope;
+        if (!(Q.dz || Q.dw || Q.db || Q.slope)) continue;
+        Q.last = !last_done;
+        last_done = true;
+        hipLaunchKernelGGL(head_stack_bwd_kernel, dim3((unsigned)stack_bwd_blocks(P, l, Q)), dim3(256), 0, st, P, l, Q);
         WD_CHECK_LAUNCH("head_stack_bwd");
     }
+    if (!last_done) {
+        const long long n = stack_last_count(P) + 1;
+        hipLaunchKernelGGL(head_stack_last_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, P);
+        WD_CHECK_LAUNCH("head_stack_last");
+    }
     return 0;
+}
+
+int wdmpnn_head_stack(const WdHeadStack *h, void *stream) {
+    WD_KERNELS_OK();
+    if (!h) return fail(WD_ERR_ARG, "null head");
+    WD_TRY(head_stack_check(h->B, h->F, h->Hf, h->T, h->L, h->ld_x, h->act, h->loss_kind, h->n_classes, h->W, h->slope));
+    for (int l = 0; l < h->L; ++l)
+        if (!h->dW[l]) return fail(WD_ERR_ARG, "head stack: null gradient %d", l);
+    if (h->B && !h->dx) return fail(WD_ERR_ARG, "head stack: null pointer");
+    return head_stack_run(h, stream);
+}
+
+int wdmpnn_head_stack_partial(const WdHeadStack *h, void *stream) {
+    WD_KERNELS_OK();
+    if (!h) return fail(WD_ERR_ARG, "null head");
+    WD_TRY(head_stack_check(h->B, h->F, h->Hf, h->T, h->L, h->ld_x, h->act, h->loss_kind, h->n_classes, h->W, h->slope));
+    return head_stack_run(h, stream);
 }
 
 int wdmpnn_head_stack_predict(const WdHeadStackPredict *h, void *stream) {
