@@ -221,6 +221,12 @@ struct H2Prod {
 // give 4 tiles for Hk = 320 and so exactly one workgroup per CU at the benchmark size (64 blocks x 4 =
 // 256): a grid of 1.25 workgroups per CU left a quarter of the CUs with twice the bytes to stream.
 constexpr int MP_THREADS = 512;
+// pair layers: the epilogue lists' loads issued before the loaders' copy loop and held in registers (1) or
+// issued after it (0).  Measured: "all waves past the GEMM" 0.5 -> 0.16 us per layer alone, the headline the
+// same (218.6 vs 218.9 M edges/s, DESIGN.md "Measured dead ends") -- not kept
+#ifndef WD_PRE_EARLY
+#define WD_PRE_EARLY 0
+#endif
 
 // mp_layer epilogue: the gather G applied to the P = M_{t-1} W_h^T tile in LDS in the reference's two
 // steps (mpn.py:110-120), then bias, residual and the fp32 stores of Z_t (with the maximum of
@@ -280,25 +286,39 @@ struct MpEpilogue {
     // reads its units' rows from LDS after the barrier (take_pre) -- no memory latency after the GEMM.
     static constexpr int PRE_ELL = BLK_ATOMS * (int)sizeof(EllRow);
     static constexpr int PRE_BYTES = PRE_ELL * (ATOM && LAST ? 2 : 1) + (ATOM ? 0 : BM * 8);
-    __device__ __forceinline__ void fill_pre(const MpLayerP &P, const BlockRow &B, uint8_t *pre) {
+    // one staging thread's share of the lists: loaded into registers (plain loads, nothing computed on what
+    // they return), then stored into the `pre` area
+    struct Pre {
+        EllRow e, f;  // (f: ATOM && LAST only)
+        int2 q;
+    };
+    __device__ __forceinline__ void load_pre(const MpLayerP &P, const BlockRow &B, Pre &R) {
         const int t = threadIdx.x - MP_THREADS / 2;  // (staging threads 0 .. 255)
+        R.e = ell_zero();
+        if (t < B.an) R.e = ATOM ? ell_load(P.mell_idx, P.mell_coef, (size_t)B.as + t)
+                                 : ell_load(P.aell_idx, P.aell_coef, (size_t)B.as + t);
+        if constexpr (ATOM && LAST) {
+            R.f = ell_zero();
+            if (t < B.an) R.f = ell_load(P.aell_idx, P.aell_coef, (size_t)B.as + t);
+        }
+        if constexpr (!ATOM) {
+            R.q = make_int2(0, 0);
+            if (t < B.bn) R.q = make_int2(P.rev[B.bs + t], (int)P.src_blk[B.bs + t]);
+        }
+    }
+    __device__ __forceinline__ void store_pre(const Pre &R, uint8_t *pre) {
+        const int t = threadIdx.x - MP_THREADS / 2;
         if (t < BLK_ATOMS) {
-            EllRow e = ell_zero();
-            if (t < B.an) e = ATOM ? ell_load(P.mell_idx, P.mell_coef, (size_t)B.as + t)
-                                   : ell_load(P.aell_idx, P.aell_coef, (size_t)B.as + t);
-            reinterpret_cast<EllRow *>(pre)[t] = e;
-            if constexpr (ATOM && LAST) {
-                EllRow f = ell_zero();
-                if (t < B.an) f = ell_load(P.aell_idx, P.aell_coef, (size_t)B.as + t);
-                reinterpret_cast<EllRow *>(pre + PRE_ELL)[t] = f;
-            }
+            reinterpret_cast<EllRow *>(pre)[t] = R.e;
+            if constexpr (ATOM && LAST) reinterpret_cast<EllRow *>(pre + PRE_ELL)[t] = R.f;
         }
         if constexpr (!ATOM)
-            if (t < BM) {
-                int2 q = make_int2(0, 0);
-                if (t < B.bn) q = make_int2(P.rev[B.bs + t], (int)P.src_blk[B.bs + t]);
-                reinterpret_cast<int2 *>(pre + PRE_ELL)[t] = q;
-            }
+            if (t < BM) reinterpret_cast<int2 *>(pre + PRE_ELL)[t] = R.q;
+    }
+    __device__ __forceinline__ void fill_pre(const MpLayerP &P, const BlockRow &B, uint8_t *pre) {
+        Pre R;
+        load_pre(P, B, R);
+        store_pre(R, pre);
     }
     __device__ __forceinline__ void take_pre(const BlockRow &B, const uint8_t *pre) {
         const int tid = threadIdx.x;
@@ -549,10 +569,10 @@ __global__ __launch_bounds__(MP_THREADS, 4) void mp_layer_kernel(const Multi<MpL
     wd_stamp(0 + 8 * LAST);
     const MpLayerP &P = multi_pick(MP, xcd_tile(blockIdx.x, gridDim.x), tile);
     const int blk = tile / P.n_tiles, nt = tile % P.n_tiles, n0 = nt * BN;
-    const BlockRow B = load_block(P.blocks, blk);
+    // (PAIRS: the block row is loaded inside the main loop, by each role where it needs it)
+    BlockRow B = PAIRS ? BlockRow{} : load_block(P.blocks, blk);
     Epi_ E;
     float *Pt = reinterpret_cast<float *>(lds);
-    const int rs = ATOM ? B.as : B.bs, rn = ATOM ? B.an : B.bn;  // the block's message rows
     if constexpr (PAIRS) {
         static_assert(!ATOM, "pair operands: bond messages");
         // the epilogue's gather lists and ids, staged by the loader waves while the consumers multiply the
@@ -560,16 +580,34 @@ __global__ __launch_bounds__(MP_THREADS, 4) void mp_layer_kernel(const Multi<MpL
         // the atom sums the epilogue writes
         static_assert(EPI_BYTES + Epi_::PRE_BYTES <= STG_BYTES, "epilogue lists beside the P tile");
         uint8_t *pre = lds + STG_BYTES - Epi_::PRE_BYTES;
-        const uint32_t wv = lane_word(P.amax_in + (size_t)blk * P.amax_in_n, P.amax_in_n);
-        const uint32_t whm = *P.wh_amax;
+        auto rows = [&]() {
+            B = load_block(P.blocks, blk);
+            return B.bn;
+        };
+        // (W_h's word too: only the consumers' epilogue step needs it, and a dependent load ahead of the role
+        // branch stood between the loaders and their first copies)
+        uint32_t whm = 0;
+        auto words = [&]() {
+            whm = *P.wh_amax;
+            return lane_word(P.amax_in + (size_t)blk * P.amax_in_n, P.amax_in_n);
+        };
         wd_stamp(1 + 8 * LAST);
         floatx4 acc[BM / 64][BN / 16];
         int se;
         constexpr int CH = 2 * BM * 64;
+        // the epilogue's lists: loaded by the loaders after their last copy (WD_PRE_EARLY: before their loop)
+        struct PreHook {
+            Epi_ &E; const MpLayerP &P; const BlockRow &B; uint8_t *pre;
+            typename Epi_::Pre R;
+            __device__ __forceinline__ void issue() { if (WD_PRE_EARLY) E.load_pre(P, B, R); }
+            __device__ __forceinline__ void finish() {
+                if (!WD_PRE_EARLY) E.load_pre(P, B, R);
+                E.store_pre(R, pre);
+            }
+        } hook{E, P, B, pre, {}};
         h2_mainloop_pairs<BM, BN>(P.ain + (size_t)blk * (P.kp >> 5) * CH, P.wh + (size_t)nt * (P.kp >> 5) * (2 * BN * 64),
-                                  P.kp >> 5, rn, wv, P.ain_g, lds, acc, se);
+                                  P.kp >> 5, rows, words, P.ain_g, lds, acc, se, hook);
         wd_stamp(2 + 8 * LAST);
-        if (threadIdx.x >= MP_THREADS / 2) E.fill_pre(P, B, pre);
         __syncthreads();
         E.take_pre(B, pre);
         wd_stamp(3 + 8 * LAST);
@@ -586,6 +624,7 @@ __global__ __launch_bounds__(MP_THREADS, 4) void mp_layer_kernel(const Multi<MpL
             if (LAST && P.asave) st4(P.asave + n0 + 4 * threadIdx.x, f4zero());
         }
     } else {
+    const int rs = ATOM ? B.as : B.bs, rn = ATOM ? B.an : B.bn;  // the block's message rows
     // the block's scale words of M_{t-1} (<= 64, one per lane) and W_h's: loaded before the GEMM's first
     // loads, reduced by the producers before their first stage and by the consumers after the GEMM
     int w0 = blk * P.amax_in_n, wn = P.amax_in_n;
@@ -880,7 +919,8 @@ __global__ __launch_bounds__(PAIRS ? 512 : 64 * WoWaves<BN>::WM * WoWaves<BN>::W
     int tile;
     const WoReadoutP &P = multi_pick(MP, xcd_tile(blockIdx.x, gridDim.x), tile);
     const int blk = tile / P.n_tiles, nt = tile % P.n_tiles, n0 = nt * BN;
-    const BlockRow B = load_block(P.blocks, blk);
+    // (PAIRS: the block row is loaded inside the main loop, by each role where it needs it)
+    BlockRow B = PAIRS ? BlockRow{} : load_block(P.blocks, blk);
     const int tid = threadIdx.x;
     X6Operands O{};
     O.a0 = P.fa; O.nkc0 = P.kpa >> 5; O.kc0 = P.kca;
@@ -894,7 +934,7 @@ __global__ __launch_bounds__(PAIRS ? 512 : 64 * WoWaves<BN>::WM * WoWaves<BN>::W
     // (thread a < an: w_atoms[as + a]) and its molecules' scope / Xn (thread i < nm)
     constexpr int C4 = BN / 4;
     static_assert((PAIRS || NT % C4 == 0) && BM <= NT, "one bias group per thread, one atom weight per thread");
-    const int nm = min(B.mh - B.ml, BLK_MOLS);  // (the packer never exceeds BLK_MOLS)
+    int nm = min(B.mh - B.ml, BLK_MOLS);  // (the packer never exceeds BLK_MOLS)
     if (P.zosave && blk == 0 && tid < BN / 4) st4(P.zosave + n0 + 4 * tid, f4zero());  // pad atom row 0
     float4 bb = f4zero();
     float watom = 0.f, mxn = 0.f;
@@ -920,16 +960,27 @@ __global__ __launch_bounds__(PAIRS ? 512 : 64 * WoWaves<BN>::WM * WoWaves<BN>::W
     float *H = reinterpret_cast<float *>(lds);
     floatx4 acc[BM / WM / 16][BN / WN / 16];
     if constexpr (PAIRS) {
-        prefetch(0);  // (registers across the GEMM: 16 rows per MFMA wave leave room)
-        const uint32_t wv = threadIdx.x < 256 ? lane_word(P.a_amax + (size_t)blk * P.a_nw, P.a_nw) : 0u;
+        // the block row and the prefetch that needs it (registers across the GEMM: 16 rows per MFMA wave leave
+        // room), per role
+        auto rows = [&]() {
+            B = load_block(P.blocks, blk);
+            nm = min(B.mh - B.ml, BLK_MOLS);
+            prefetch(0);
+            return B.an;
+        };
+        uint32_t wom = 0;  // (W_o's word: loaded by the consumers before their loop, not after it)
+        auto words = [&]() {
+            wom = *P.wo_amax;
+            return lane_word(P.a_amax + (size_t)blk * P.a_nw, P.a_nw);
+        };
         int se;
         h2_mainloop_pairs<BM, BN>(P.apairs + (size_t)blk * (P.kp >> 5) * (2 * BM * 64),
-                                  P.woh + (size_t)nt * (P.kp >> 5) * (2 * BN * 64), P.kp >> 5, B.an, wv, P.a_g, lds,
+                                  P.woh + (size_t)nt * (P.kp >> 5) * (2 * BN * 64), P.kp >> 5, rows, words, P.a_g, lds,
                                   acc, se);
         __syncthreads();
         if (threadIdx.x < 256)
             x6_acc_to_lds_scaled<BM, BN, 4, 1>(acc, H, se >= 0 ? __uint_as_float((uint32_t)(254 - se) << 23) : 1.f,
-                                               h2_inv_scale(*P.wo_amax));
+                                               h2_inv_scale(wom));
     } else {
         x6_mainloop<BM, BN, WM, WN, WS, CPS>(O, lds, acc, prefetch);
         __syncthreads();

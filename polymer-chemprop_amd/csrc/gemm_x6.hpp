@@ -1045,10 +1045,41 @@ constexpr int h2p_lds_bytes() { return H2P_STAGES * h2p_stage_bytes<BM, BN>(); }
 #ifndef WD_H2P_FRAG
 #define WD_H2P_FRAG 0
 #endif
-template <int BM, int BN, int FRAG = WD_H2P_FRAG>
-__device__ __forceinline__ void h2_mainloop_pairs(const uint8_t *a_src, const uint8_t *b_src, int nchunks, int a_rows,
-                                                  uint32_t wv, int G, uint8_t *lds, floatx4 (&acc)[BM / 64][BN / 16],
-                                                  int &se_out) {
+// rows(): the block's live rows (a_rows), words(): this lane's scale word (lane_word) -- functors, because both
+// are dependent loads (kernel arguments -> block row / words, the words a loop of loads and waits) that the two
+// roles need at different times: the consumers call both before their loop; the loaders call rows() alone, so
+// their first copies wait for the kernel arguments and the block row and for nothing else (with every thread
+// loading the words ahead of the role branch, the first copies left 0.7 us later: tools/stamps_layer.py
+// "params", profiles/prologue_stamps_*.txt).  The role branch is on a readfirstlane'd wave index: a scalar
+// branch, so what rows() loads stays in scalar registers past the join.
+//
+// EARLY (WD_H2P_EARLY, measured, not kept: DESIGN.md "Measured dead ends"): the loaders' first NS - 1 chunks
+// copy ALL of A's 16-row groups and are issued BEFORE rows() -- neither source address needs the block row, it
+// only says which groups to skip.  Rows past the block's last live group are stale bytes of the pair buffer
+// (inside it: the buffers hold BM rows for every block, fwd_layout's Mp / Ab), land in LDS rows no consumer
+// reads (`na`) and are never multiplied (tests/test_early_copies_gpu.py runs on a 0xFF-filled workspace).
+//
+// LoaderHook: what the caller's loader waves do around their copy loop -- issue(): right after the first
+// copies (plain loads into registers of the hook, landing behind the loop); finish(): after the last copy
+// has landed and every consumer is past chunk nchunks - 2 (LDS stores into the tail of ring stage NS - 1)
+#ifndef WD_H2P_EARLY
+#define WD_H2P_EARLY 0
+#endif
+// (the scalar role branch; 0: the branch on tid >> 6, divergent to the compiler -- measured, four alternating
+// headline runs on one box: 210.1-214.5 M edges/s against 216.1-218.3 with it and 207.2-212.1 for the parent,
+// profiles/prologue_parts_ab.txt)
+#ifndef WD_H2P_UNIFORM
+#define WD_H2P_UNIFORM 1
+#endif
+struct NoLoaderHook {
+    __device__ void issue() {}
+    __device__ void finish() {}
+};
+template <int BM, int BN, int FRAG = WD_H2P_FRAG, typename Rows, typename Words, typename LoaderHook = NoLoaderHook>
+__device__ __forceinline__ void h2_mainloop_pairs(const uint8_t *a_src, const uint8_t *b_src, int nchunks, Rows &&rows,
+                                                  Words &&words, int G, uint8_t *lds, floatx4 (&acc)[BM / 64][BN / 16],
+                                                  int &se_out, LoaderHook &&lhook = LoaderHook()) {
+    constexpr bool EARLY = WD_H2P_EARLY;
     // (acc[BM / 64]: a consumer wave's BM / 4 rows as 16-row tiles; the layout x6_acc_to_lds<BM, BN, 4, 1> reads)
     static_assert(BM == 128 || BM == 64, "four consumer waves of BM / 4 rows");
     constexpr int RW = BM / 4, TM = RW / 16, TN = BN / 16;  // rows per consumer wave, its 16-row tiles
@@ -1056,7 +1087,8 @@ __device__ __forceinline__ void h2_mainloop_pairs(const uint8_t *a_src, const ui
     constexpr int AP = 2 * BM / 16, APW = AP / 4;        // A: 16 pieces of 1 KB per chunk, 4 per loader wave
     constexpr int BP = 2 * BN / 16, BPW = (BP + 3) / 4;  // B: 10 pieces, <= 3 per loader wave
     static_assert(AP % 4 == 0, "A pieces split evenly over the loader waves");
-    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, w4 = wave & 3, g = lane >> 4, i16 = lane & 15;
+    const int tid = threadIdx.x, lane = tid & 63, wave = WD_H2P_UNIFORM ? __builtin_amdgcn_readfirstlane(tid >> 6) : tid >> 6, w4 = wave & 3;
+    const int g = lane >> 4, i16 = lane & 15;
     // chunk kc in stage (kc + roff) % NS, so that the LAST chunk lands in stage 0: the caller may use the
     // tail of stage NS - 1 while the consumers multiply that chunk (mp_layer_kernel's epilogue lists)
     const int roff = (NS - (nchunks - 1) % NS) % NS;
@@ -1068,26 +1100,20 @@ __device__ __forceinline__ void h2_mainloop_pairs(const uint8_t *a_src, const ui
         // this wave's pieces: source offsets in a chunk block (the DMA writes LDS lane-linearly, so the bank
         // swizzle of x6_slot is applied on the source side) and whether each is copied
         int src[APW + BPW], dst[APW + BPW];
-        bool on[APW + BPW];
-        int mine = 0;
 #pragma unroll
         for (int j = 0; j < APW; ++j) {
             const int c = 4 * j + w4, q = 64 * c + lane, p = q / (BM * 4), r = (q >> 2) % BM, sl = q & 3;
             src[j] = p * APL + r * 64 + 16 * (sl ^ ((r >> 1) & 3));
             dst[j] = 1024 * c;
-            on[j] = 16 * (c % (BM / 16)) < a_rows;  // 16-row groups past the block's rows: not copied
-            mine += on[j];
         }
 #pragma unroll
         for (int j = 0; j < BPW; ++j) {
             const int c = 4 * j + w4, q = 64 * c + lane, p = (q / (BN * 4)) % 2, r = (q >> 2) % BN, sl = q & 3;
             src[APW + j] = p * BPL + r * 64 + 16 * (sl ^ ((r >> 1) & 3));
             dst[APW + j] = 2 * APL + 1024 * c;
-            on[APW + j] = BP % 4 == 0 || c < BP;
-            mine += on[APW + j];
         }
-        mine = __builtin_amdgcn_readfirstlane(mine);  // (wave-uniform: a scalar wait below)
-        auto issue = [&](int kc) {
+        // copy j of chunk kc (all: every A group, else the live ones)
+        auto issue = [&](int kc, const bool (&on)[APW + BPW]) {
             uint8_t *st = lds + ((kc + roff) % NS) * STAGE;
             const uint8_t *ablk = a_src + (size_t)kc * (2 * APL), *bblk = b_src + (size_t)kc * (2 * BPL);
 #pragma unroll
@@ -1097,11 +1123,48 @@ __device__ __forceinline__ void h2_mainloop_pairs(const uint8_t *a_src, const ui
             for (int j = 0; j < BPW; ++j)
                 if (on[APW + j]) glds16_untracked(bblk + src[APW + j], st + dst[APW + j]);
         };
+        bool all[APW + BPW], on[APW + BPW];
 #pragma unroll
-        for (int c = 0; c < NS - 1; ++c)
-            if (c < nchunks) issue(c);
+        for (int j = 0; j < APW; ++j) all[j] = true;
+#pragma unroll
+        for (int j = 0; j < BPW; ++j) all[APW + j] = BP % 4 == 0 || 4 * j + w4 < BP;
+        if constexpr (EARLY) {
+            // before rows(): the copies are asm statements that clobber memory, so the block row's load stays
+            // behind them and nothing here waits for it
+#pragma unroll
+            for (int c = 0; c < NS - 1; ++c)
+                if (c < nchunks) issue(c, all);
+            __builtin_amdgcn_sched_barrier(0);
+        }
+        const int a_rows = rows();
+        int mine = 0;
+#pragma unroll
+        for (int j = 0; j < APW; ++j) {
+            on[j] = 16 * ((4 * j + w4) % (BM / 16)) < a_rows;  // 16-row groups past the block's rows: not copied
+            mine += on[j];
+        }
+#pragma unroll
+        for (int j = 0; j < BPW; ++j) {
+            on[APW + j] = all[APW + j];
+            mine += on[APW + j];
+        }
+        mine = __builtin_amdgcn_readfirstlane(mine);  // (wave-uniform: a scalar wait below)
+        if constexpr (!EARLY) {
+#pragma unroll
+            for (int c = 0; c < NS - 1; ++c)
+                if (c < nchunks) issue(c, on);
+        }
+        lhook.issue();
         // the loop instantiated per copy count (its steady-state wait a constant: a wait on a runtime count
-        // is a scalar branch search per chunk, ~300 cycles of the chunk period in tools/ring_probe.hip)
+        // is a scalar branch search per chunk, ~300 cycles of the chunk period in tools/ring_probe.hip).
+        // The waits count this wave's outstanding loads from the youngest back, and loads return in issue
+        // order.  Before chunk kc's wait the wave has issued chunks 0 .. min(kc + NS - 2, nchunks - 1), every
+        // one of >= M copies (EARLY: the first NS - 1 chunks carry all of A's groups, M' >= M; the rest
+        // exactly M), then at most once the hook's loads (younger than the first chunks, older than the rest).
+        // "At most n * M outstanding" with n = the number of chunks younger than kc therefore leaves
+        // outstanding only copies among the youngest n * M <= the younger chunks' own: chunk kc, and all
+        // before it, landed.  Larger first chunks and the hook's loads only make a wait cover more than it
+        // needs (at kc = 0: most of chunk 1, issued back to back with chunk 0), never less.
         dispatch_upto<APW + BPW>(mine, [&](auto m_c) {
             constexpr int M = decltype(m_c)::value;
             for (int kc = 0; kc < nchunks; ++kc) {
@@ -1112,14 +1175,17 @@ __device__ __forceinline__ void h2_mainloop_pairs(const uint8_t *a_src, const ui
                 else wait_vmcnt((nchunks - 1 - kc) * M);
                 if (WD_STAMPS && wave == 4) wd_lstamp(kc, 5);
                 __builtin_amdgcn_s_barrier();
-                if (kc + NS - 1 < nchunks) issue(kc + NS - 1);
+                if (kc + NS - 1 < nchunks) issue(kc + NS - 1, on);
             }
         });
         __builtin_amdgcn_s_waitcnt(0x0070);  // (vmcnt(0): every copy of this wave landed)
+        lhook.finish();
         se_out = -1;
         return;
     }
     // ---- consumers
+    const int a_rows = rows();
+    const uint32_t wv = words();
     int ao[TM], bo[TN];
 #pragma unroll
     for (int a = 0; a < TM; ++a) ao[a] = x6_slot(RW * w4 + 16 * a + i16, g);
