@@ -129,13 +129,10 @@ struct Feed {
         try {
             std::vector<GraphBuildP> P;
             std::vector<WdGraph> G;
-#ifndef WD_FEED_GROUP
-#define WD_FEED_GROUP 1
-#endif
             // a group of grp batches per build launch while the consumer has two or more built batches in
             // hand (waking for every staged batch gave launches of one batch): streamed leg 146.2-155.9
-            // against 142.0-149.3 M edges/s, same box, three rounds (WD_FEED_GROUP=0: the old wake-up)
-            const int64_t grp = WD_FEED_GROUP ? std::min<int64_t>(WD_MULTI, std::max<int64_t>(1, R / 2)) : 1;
+            // against 142.0-149.3 M edges/s for a wake-up per batch, same box, three rounds
+            const int64_t grp = std::min<int64_t>(WD_MULTI, std::max<int64_t>(1, R / 2));
             for (int64_t i = 0; i < spec.n_batches;) {
                 int64_t n = 0;
                 {

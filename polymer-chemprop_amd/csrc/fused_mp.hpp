@@ -210,23 +210,11 @@ struct H2Prod {
     }
 };
 
-// cache policy of the Z_t row stores: default write-back.  Write-through, as the planes use, measured
-// slower on the first polymer layer (17.46 us against 16.50, same box)
-#ifndef WD_ZWT
-#define WD_ZWT 0
-#endif
-
 // The fused layer kernel runs 512 threads, warp-specialised: 4 MFMA waves of 32 rows x all BN columns and
 // their 4 staging partners (gemm_x6.hpp h2_mainloop_ws); the epilogue runs on all 512.  80-column tiles
 // give 4 tiles for Hk = 320 and so exactly one workgroup per CU at the benchmark size (64 blocks x 4 =
 // 256): a grid of 1.25 workgroups per CU left a quarter of the CUs with twice the bytes to stream.
 constexpr int MP_THREADS = 512;
-// pair layers: the epilogue lists' loads issued before the loaders' copy loop and held in registers (1) or
-// issued after it (0).  Measured: "all waves past the GEMM" 0.5 -> 0.16 us per layer alone, the headline the
-// same (218.6 vs 218.9 M edges/s, DESIGN.md "Measured dead ends") -- not kept
-#ifndef WD_PRE_EARLY
-#define WD_PRE_EARLY 0
-#endif
 
 // mp_layer epilogue: the gather G applied to the P = M_{t-1} W_h^T tile in LDS in the reference's two
 // steps (mpn.py:110-120), then bias, residual and the fp32 stores of Z_t (with the maximum of
@@ -251,39 +239,11 @@ struct MpEpilogue {
     int32_t rv[ATOM ? 1 : UPT];
     uint32_t sa[ATOM ? 1 : UPT];
 
-    // during the GEMM: the gather rows of this thread's atom units (unit v = tid + NT i: atom v / UPR) and,
-    // in bond mode, the source / reverse ids of its bond units (unit v: row v / UPR) -- loads only, no
-    // arithmetic on what they return (that would wait for them inside the GEMM)
-    __device__ __forceinline__ void prefetch(const MpLayerP &P, const BlockRow &B) {
-        const int tid = threadIdx.x;
-#pragma unroll
-        for (int i = 0; i < AUPT; ++i) {
-            const int v = tid + NT * i;
-            const bool ok = v < AUNITS && v / UPR < B.an;
-            aell[i] = ell_zero();
-            if (ok) aell[i] = ATOM ? ell_load(P.mell_idx, P.mell_coef, (size_t)B.as + v / UPR)
-                                   : ell_load(P.aell_idx, P.aell_coef, (size_t)B.as + v / UPR);
-            if constexpr (ATOM && LAST) {
-                gell[i] = ell_zero();
-                if (ok) gell[i] = ell_load(P.aell_idx, P.aell_coef, (size_t)B.as + v / UPR);
-            }
-        }
-        if constexpr (!ATOM)
-#pragma unroll
-            for (int i = 0; i < UPT; ++i) {
-                const int v = tid + NT * i, lr = v / UPR;
-                rv[i] = 0;
-                sa[i] = 0;
-                if (v < UNITS && lr < B.bn) {
-                    rv[i] = P.rev[B.bs + lr];
-                    sa[i] = P.src_blk[B.bs + lr];
-                }
-            }
-    }
-
-    // The same lists handed over through LDS (WD_EPI_PRE): the staging waves, done one chunk before the MFMA
-    // waves, load them for the whole block while the last chunk is multiplied (fill_pre), and every thread
-    // reads its units' rows from LDS after the barrier (take_pre) -- no memory latency after the GEMM.
+    // The gather rows of the block's atoms (unit v = tid + NT i: atom v / UPR) and, in bond mode, the source /
+    // reverse ids of its bond rows (unit v: row v / UPR), handed over through LDS: the staging waves, done one
+    // chunk before the MFMA waves, load them for the whole block while the last chunk is multiplied (fill_pre),
+    // and every thread reads its units' rows from LDS after the barrier (take_pre) -- no memory latency after
+    // the GEMM.
     static constexpr int PRE_ELL = BLK_ATOMS * (int)sizeof(EllRow);
     static constexpr int PRE_BYTES = PRE_ELL * (ATOM && LAST ? 2 : 1) + (ATOM ? 0 : BM * 8);
     // one staging thread's share of the lists: loaded into registers (plain loads, nothing computed on what
@@ -447,12 +407,14 @@ struct MpEpilogue {
                 const float b8[8] = {b0.x, b0.y, b0.z, b0.w, b1.x, b1.y, b1.z, b1.w};
 #pragma unroll
                 for (int q = 0; q < 8; ++q) z[q] = r8[q] + (z[q] + b8[q]);  // mpn.py:122-123
-                if (zr) {  // (16-byte buffer stores)
+                // (16-byte buffer stores, default write-back policy: write-through, as the planes use, measured
+                // slower on the first polymer layer -- 17.46 us against 16.50, same box)
+                if (zr) {
                     const int o = (lr * P.kp + n0 + c) * 4;
                     __builtin_amdgcn_raw_buffer_store_b128(u32x4{__float_as_uint(z[0]), __float_as_uint(z[1]),
-                                                                 __float_as_uint(z[2]), __float_as_uint(z[3])}, zrs, o, 0, WD_ZWT);
+                                                                 __float_as_uint(z[2]), __float_as_uint(z[3])}, zrs, o, 0, 0);
                     __builtin_amdgcn_raw_buffer_store_b128(u32x4{__float_as_uint(z[4]), __float_as_uint(z[5]),
-                                                                 __float_as_uint(z[6]), __float_as_uint(z[7])}, zrs, o + 16, 0, WD_ZWT);
+                                                                 __float_as_uint(z[6]), __float_as_uint(z[7])}, zrs, o + 16, 0, 0);
                 }
 #pragma unroll
                 for (int q = 0; q < 8; ++q) z[q] = act_fwd(ACT, z[q], slope);
@@ -563,7 +525,7 @@ __global__ __launch_bounds__(MP_THREADS, 4) void mp_layer_kernel(const Multi<MpL
     constexpr int EPI_BYTES = Epi_::LDS_FLOATS * 4;  // P tile + the atom sums
     constexpr int STG_BYTES = PAIRS ? h2p_lds_bytes<BM, BN>() : h2_lds_bytes<BM, BN>();
     constexpr int LDS_BYTES = EPI_BYTES > STG_BYTES ? EPI_BYTES : STG_BYTES;
-    static_assert(LDS_BYTES <= (PAIRS && H2P_STAGES > 3 ? 160 : 80) * 1024, "two workgroups per CU");
+    static_assert(LDS_BYTES <= 80 * 1024, "two workgroups per CU");
     __shared__ __attribute__((aligned(16))) uint8_t lds[LDS_BYTES];
     int tile;
     wd_stamp(0 + 8 * LAST);
@@ -573,6 +535,10 @@ __global__ __launch_bounds__(MP_THREADS, 4) void mp_layer_kernel(const Multi<MpL
     BlockRow B = PAIRS ? BlockRow{} : load_block(P.blocks, blk);
     Epi_ E;
     float *Pt = reinterpret_cast<float *>(lds);
+    // Two GEMM front ends.  After either, both run the same steps -- the lists into E, the scaled tile into Pt,
+    // the epilogue, the pad rows -- written out twice: shared through a function, a lambda or common code after
+    // the branch, they compile to the same instructions with other register numbers in the register-staged
+    // kernels, and these kernels are compared byte for byte with their predecessors.
     if constexpr (PAIRS) {
         static_assert(!ATOM, "pair operands: bond messages");
         // the epilogue's gather lists and ids, staged by the loader waves while the consumers multiply the
@@ -595,13 +561,14 @@ __global__ __launch_bounds__(MP_THREADS, 4) void mp_layer_kernel(const Multi<MpL
         floatx4 acc[BM / 64][BN / 16];
         int se;
         constexpr int CH = 2 * BM * 64;
-        // the epilogue's lists: loaded by the loaders after their last copy (WD_PRE_EARLY: before their loop)
+        // the lists: loaded by the loaders after their last copy (before their loop, held in registers:
+        // "all waves past the GEMM" 0.5 -> 0.16 us per layer alone, the headline the same -- 218.6 vs 218.9 M
+        // edges/s, DESIGN.md "Measured dead ends" -- not kept)
         struct PreHook {
             Epi_ &E; const MpLayerP &P; const BlockRow &B; uint8_t *pre;
             typename Epi_::Pre R;
-            __device__ __forceinline__ void issue() { if (WD_PRE_EARLY) E.load_pre(P, B, R); }
             __device__ __forceinline__ void finish() {
-                if (!WD_PRE_EARLY) E.load_pre(P, B, R);
+                E.load_pre(P, B, R);
                 E.store_pre(R, pre);
             }
         } hook{E, P, B, pre, {}};
@@ -613,7 +580,7 @@ __global__ __launch_bounds__(MP_THREADS, 4) void mp_layer_kernel(const Multi<MpL
         wd_stamp(3 + 8 * LAST);
         if (threadIdx.x < 256) {  // (the consumer waves hold the tile)
             const float ia = se >= 0 ? __uint_as_float((uint32_t)(254 - se) << 23) : 1.f;
-            x6_acc_to_lds_scaled<BM, BN, 4, 1>(acc, Pt, ia, h2_inv_scale(whm));
+            x6_acc_to_lds<BM, BN, 4, 1, true>(acc, Pt, ia, h2_inv_scale(whm));
         }
         __syncthreads();
         E.template run<ACT>(P, B, blk, n0, Pt);
@@ -624,52 +591,45 @@ __global__ __launch_bounds__(MP_THREADS, 4) void mp_layer_kernel(const Multi<MpL
             if (LAST && P.asave) st4(P.asave + n0 + 4 * threadIdx.x, f4zero());
         }
     } else {
-    const int rs = ATOM ? B.as : B.bs, rn = ATOM ? B.an : B.bn;  // the block's message rows
-    // the block's scale words of M_{t-1} (<= 64, one per lane) and W_h's: loaded before the GEMM's first
-    // loads, reduced by the producers before their first stage and by the consumers after the GEMM
-    int w0 = blk * P.amax_in_n, wn = P.amax_in_n;
-    if (P.amax_rt > 0) {  // (the row tiles of the block's rows)
-        const int t0 = rs / P.amax_rt, t1 = (rs + max(rn, 1) - 1) / P.amax_rt;
-        w0 = t0 * P.amax_in_n;
-        wn = (t1 - t0 + 1) * P.amax_in_n;
-    }
-    const uint32_t wv = lane_word(P.amax_in + w0, wn);
-    const uint32_t whm = *P.wh_amax;
-    H2Prod<BM, ACT> ap(P, rs, rn, wv);
-    wd_stamp(1 + 8 * LAST);
-    floatx4 acc[BM / 64][BN / 16];
-    h2_mainloop_ws<BM, BN>(P.wh + (size_t)nt * (P.kp >> 5) * (2 * BN * 64), P.kp >> 5, rn, lds, acc, ap);
-    // the epilogue's gather lists and ids: not during the GEMM (live across the GEMM loop they pushed the
-    // consumers' accumulators and fragments past 128 VGPRs); the staging waves load them into LDS while the
-    // MFMA waves finish the last chunk
-    wd_stamp(2 + 8 * LAST);
-#ifndef WD_EPI_PRE
-#define WD_EPI_PRE 1
-#endif
-    __shared__ __attribute__((aligned(16))) uint8_t pre[WD_EPI_PRE ? Epi_::PRE_BYTES : 16];
-    static_assert(LDS_BYTES + (WD_EPI_PRE ? Epi_::PRE_BYTES : 0) + 64 <= 80 * 1024, "two workgroups per CU");
-    if (WD_EPI_PRE) {
+        const int rs = ATOM ? B.as : B.bs, rn = ATOM ? B.an : B.bn;  // the block's message rows
+        // the block's scale words of M_{t-1} (<= 64, one per lane) and W_h's: loaded before the GEMM's first
+        // loads, reduced by the producers before their first stage and by the consumers after the GEMM
+        int w0 = blk * P.amax_in_n, wn = P.amax_in_n;
+        if (P.amax_rt > 0) {  // (the row tiles of the block's rows)
+            const int t0 = rs / P.amax_rt, t1 = (rs + max(rn, 1) - 1) / P.amax_rt;
+            w0 = t0 * P.amax_in_n;
+            wn = (t1 - t0 + 1) * P.amax_in_n;
+        }
+        const uint32_t wv = lane_word(P.amax_in + w0, wn);
+        const uint32_t whm = *P.wh_amax;
+        H2Prod<BM, ACT> ap(P, rs, rn, wv);
+        wd_stamp(1 + 8 * LAST);
+        floatx4 acc[BM / 64][BN / 16];
+        h2_mainloop_ws<BM, BN>(P.wh + (size_t)nt * (P.kp >> 5) * (2 * BN * 64), P.kp >> 5, rn, lds, acc, ap);
+        // the epilogue's gather lists and ids: not during the GEMM (live across the GEMM loop they pushed the
+        // consumers' accumulators and fragments past 128 VGPRs); the staging waves load them into LDS while the
+        // MFMA waves finish the last chunk
+        wd_stamp(2 + 8 * LAST);
+        __shared__ __attribute__((aligned(16))) uint8_t pre[Epi_::PRE_BYTES];
+        static_assert(LDS_BYTES + Epi_::PRE_BYTES + 64 <= 80 * 1024, "two workgroups per CU");
         if (threadIdx.x >= MP_THREADS / 2) E.fill_pre(P, B, pre);
-    } else {
-        E.prefetch(P, B);
+        __syncthreads();
+        E.take_pre(B, pre);
+        wd_stamp(3 + 8 * LAST);
+        const float ia = h2_inv_scale(wave_max_u32(wv));  // (the producers' scale)
+        const float iw = h2_inv_scale(whm);
+        if (threadIdx.x < 256) x6_acc_to_lds<BM, BN, 4, 1, true>(acc, Pt, ia, iw);  // (the consumer waves hold the tile)
+        __syncthreads();
+        E.template run<ACT>(P, B, blk, n0, Pt);
+        wd_stamp(6 + 8 * LAST);
+        // the pad row 0 (bond and atom) belongs to no block: its Z rows are written as zeros (the backward
+        // multiplies them by its zero gradients, where an uninitialised NaN would poison them)
+        if (blk == 0 && threadIdx.x < BN / 4) {
+            float *zr = LAST ? P.zsave : P.zout;
+            if (zr) st4(zr + n0 + 4 * threadIdx.x, f4zero());
+            if (LAST && P.asave) st4(P.asave + n0 + 4 * threadIdx.x, f4zero());
+        }
     }
-    __syncthreads();
-    if (WD_EPI_PRE) E.take_pre(B, pre);
-    wd_stamp(3 + 8 * LAST);
-    const float ia = h2_inv_scale(wave_max_u32(wv));  // (the producers' scale)
-    const float iw = h2_inv_scale(whm);
-    if (threadIdx.x < 256) x6_acc_to_lds_scaled<BM, BN, 4, 1>(acc, Pt, ia, iw);  // (the consumer waves hold the tile)
-    __syncthreads();
-    E.template run<ACT>(P, B, blk, n0, Pt);
-    wd_stamp(6 + 8 * LAST);
-    // the pad row 0 (bond and atom) belongs to no block: its Z rows are written as zeros (the backward
-    // multiplies them by its zero gradients, where an uninitialised NaN would poison them)
-    if (blk == 0 && threadIdx.x < BN / 4) {
-        float *zr = LAST ? P.zsave : P.zout;
-        if (zr) st4(zr + n0 + 4 * threadIdx.x, f4zero());
-        if (LAST && P.asave) st4(P.asave + n0 + 4 * threadIdx.x, f4zero());
-    }
-    }  // (register-staged path)
 }
 
 // ------------------------------------------------------------------------------------------------
@@ -719,14 +679,8 @@ __device__ __forceinline__ float4 code_sum(const WdAtomCode &cd, const float *T,
     return s;
 }
 
-// (EO_LAST measured, same box: embed 10.00 vs 10.25 us, the bench's single stream 119.2 vs 125.2 M, headline
-// 202.7 vs 204.8 M -- not kept)
-#ifndef WD_EMBED_EO_LAST
-#define WD_EMBED_EO_LAST 0
-#endif
 template <int BN, int ACT, int NJ = WD_MULTI, bool PAIRS = false>
 __global__ __launch_bounds__(512) void embed_kernel(const Multi<EmbedP, NJ> MP) {
-    constexpr bool EO_LAST = WD_EMBED_EO_LAST;
     static_assert(!PAIRS || BN % 16 == 0, "pair groups of whole 16-column halves");
     constexpr int NT = 512, LDC = BN + 4, C4 = BN / 4, U8 = BN / 8, MAXK = 160, PER = (MAXK * C4 + NT - 1) / NT;
     constexpr int BU = (BLK_BONDS * U8 + NT - 1) / NT;  // bond units (8 columns of a row) per thread
@@ -768,8 +722,10 @@ __global__ __launch_bounds__(512) void embed_kernel(const Multi<EmbedP, NJ> MP) 
     }
     if (tid < B.an) reinterpret_cast<u32x4 *>(code)[tid] = cd;
     if (tid >= NT - C4) st4(bb + 4 * (tid - (NT - C4)), bq);
-    // (EO_LAST: the W_i tile and the layers' operand first, the f_atoms half of W_o -- for wo_readout, two
-    // launches later -- while the M_0 stores drain)
+    // The f_atoms half of W_o first.  (Last, while the M_0 stores drain, measured, same box: embed 10.00 vs 10.25
+    // us, the bench's single stream 119.2 vs 125.2 M, headline 202.7 vs 204.8 M -- not kept.)  A lambda called
+    // once, not straight-line code: written inline, the compiler shares the store addresses with the W_i tile's
+    // below and waits for every load before the first W_o store instead of before the last.
     auto eo_half = [&]() {
 #pragma unroll
         for (int q = 0; q < PER; ++q) {
@@ -783,10 +739,8 @@ __global__ __launch_bounds__(512) void embed_kernel(const Multi<EmbedP, NJ> MP) 
             st4(P.eo + (size_t)(B.as + la) * P.Hk + n0 + c, code_sum<BN>(code[la], wt, P.Fa, c));
         }
     };
-    if constexpr (!EO_LAST) {
-        eo_half();
-        __syncthreads();  // every read of the W_o tile done
-    }
+    eo_half();
+    __syncthreads();  // every read of the W_o tile done
     wd_estamp(2);
 #pragma unroll
     for (int q = 0; q < PER; ++q) {
@@ -857,10 +811,6 @@ __global__ __launch_bounds__(512) void embed_kernel(const Multi<EmbedP, NJ> MP) 
     } else {
         publish_max(mx, P.amax + (size_t)blk * P.n_tiles + nt, red);
     }
-    if constexpr (EO_LAST) {
-        __syncthreads();  // every read of the W_i tile done (the bond units' tail sums)
-        eo_half();
-    }
 }
 
 constexpr int WO_MAXK = 160;  // f_atoms / f_bonds columns embed_kernel stages (Fa, Fb <= 160)
@@ -908,13 +858,11 @@ __global__ __launch_bounds__(PAIRS ? 512 : 64 * WoWaves<BN>::WM * WoWaves<BN>::W
     // (PAIRS: WM x WN = 4 x 1 MFMA waves, and four more copying A: NT = 512)
     constexpr int BM = BLK_ATOMS, LDC = BN + 4, WM = PAIRS ? 4 : WoWaves<BN>::WM, WN = PAIRS ? 1 : WoWaves<BN>::WN;
     constexpr int NT = PAIRS ? 512 : 64 * WM * WN;
-    // (deeper single-chunk pipelines, with the mainloop hook's loads ordered ahead of the partial vmcnt
-    // waits, measured slower: three / four stages 15.1 / 14.8 us here, 12.8 / 11.8 against 9.7 us on
-    // QM9-shaped batches)
-    constexpr int WS = 2;  // LDS stages
+    // (two LDS stages; deeper single-chunk pipelines measured slower: three / four stages 15.1 / 14.8 us here,
+    // 12.8 / 11.8 against 9.7 us on QM9-shaped batches)
     constexpr int EPI_BYTES = (BM * LDC + BM + 3 * BLK_MOLS + BN) * 4;  // (+ the bias columns: PAIRS)
     constexpr int LDS_BYTES = PAIRS ? (h2p_lds_bytes<BM, BN>() > EPI_BYTES ? h2p_lds_bytes<BM, BN>() : EPI_BYTES)
-                                    : WS * CPS * x6_stage_bytes<BM, BN>();
+                                    : 2 * CPS * x6_stage_bytes<BM, BN>();
     __shared__ __attribute__((aligned(16))) uint8_t lds[LDS_BYTES];
     int tile;
     const WoReadoutP &P = multi_pick(MP, xcd_tile(blockIdx.x, gridDim.x), tile);
@@ -979,10 +927,10 @@ __global__ __launch_bounds__(PAIRS ? 512 : 64 * WoWaves<BN>::WM * WoWaves<BN>::W
                                   acc, se);
         __syncthreads();
         if (threadIdx.x < 256)
-            x6_acc_to_lds_scaled<BM, BN, 4, 1>(acc, H, se >= 0 ? __uint_as_float((uint32_t)(254 - se) << 23) : 1.f,
-                                               h2_inv_scale(wom));
+            x6_acc_to_lds<BM, BN, 4, 1, true>(acc, H, se >= 0 ? __uint_as_float((uint32_t)(254 - se) << 23) : 1.f,
+                                              h2_inv_scale(wom));
     } else {
-        x6_mainloop<BM, BN, WM, WN, WS, CPS>(O, lds, acc, prefetch);
+        x6_mainloop<BM, BN, WM, WN, CPS>(O, lds, acc, prefetch);
         __syncthreads();
         x6_acc_to_lds<BM, BN, WM, WN>(acc, H);
     }

@@ -282,14 +282,14 @@ struct TnX6Params {
 // a runtime switch over all of them in the staging path bloated the kernel past the instruction cache),
 // -1 when no operand is SEG_ACT.  BEXT: the bias sums come from P.bias_src (a compile-time switch: a runtime
 // branch around those loads left the compiler's vmcnt waits unable to skip the prefetched chunk's loads)
-#ifndef WD_TN_DEPTH
-#define WD_TN_DEPTH 2
-#endif
+// WD_TN_H2 (and WD_TN_NOMAX below) stay: they belong to the H2 kernels' max pass, a path the host no longer
+// takes (gemm_tn launches H2 only with both word arrays).  Deleting it was built and measured: the seven
+// <..., true, true> kernels shrink by 10-20 KB and gemm_tn_x6_kernel<0, true, true> runs 29.9 against 29.2 us, the
+// training step 0.3384 against 0.3371 ms, seven alternating runs (profiles/retire_switches_ab.txt) -- not kept.
 #ifndef WD_TN_H2
 #define WD_TN_H2 0
 #endif
 constexpr bool TN_H2 = WD_TN_H2;
-constexpr int TN_DEPTH = WD_TN_DEPTH;
 // H2: the operands as fp16 hi/lo pairs (planes.hpp split_h2) instead of bf16x3 planes -- two planes per
 // operand, three f16 products (hh hl lh) instead of six.  fp16 needs a scale: each of the tile's 128
 // operand columns gets its own power-of-two scale from its max |value| over this split's rows (a max pass
@@ -517,9 +517,9 @@ __global__ __launch_bounds__(256) void gemm_tn_x6_kernel(TnX6Params P) {
         }
     }
     if (nchunks > 0) {
-        // TN_DEPTH chunks in flight in registers: at step kc chunk kc is in LDS, kc+1 .. kc+D-1 are loading
+        // D chunks in flight in registers: at step kc chunk kc is in LDS, kc+1 .. kc+D-1 are loading
         // (or landed) in the ring, and kc+D is issued into the set chunk kc left
-        constexpr int D = TN_DEPTH;
+        constexpr int D = 2;
         Regs R[D];
 #pragma unroll
         for (int i = 0; i < D; ++i) load_chunk(R[i], min(i, nchunks - 1));
@@ -624,38 +624,19 @@ struct X6Operands {
 template <int BM, int BN>
 constexpr int x6_stage_bytes() { return 3 * BM * 64 + 3 * BN * 64; }
 
-// s_waitcnt vmcnt(n) for a wave-uniform runtime n (the counter field is an immediate)
-__device__ __forceinline__ void wait_vmcnt(int n) {
-    switch (n) {
-    case 0: asm volatile("s_waitcnt vmcnt(0)" ::: "memory"); break;
-    case 1: asm volatile("s_waitcnt vmcnt(1)" ::: "memory"); break;
-    case 2: asm volatile("s_waitcnt vmcnt(2)" ::: "memory"); break;
-    case 3: asm volatile("s_waitcnt vmcnt(3)" ::: "memory"); break;
-    case 4: asm volatile("s_waitcnt vmcnt(4)" ::: "memory"); break;
-    case 5: asm volatile("s_waitcnt vmcnt(5)" ::: "memory"); break;
-    case 6: asm volatile("s_waitcnt vmcnt(6)" ::: "memory"); break;
-    case 7: asm volatile("s_waitcnt vmcnt(7)" ::: "memory"); break;
-    case 8: asm volatile("s_waitcnt vmcnt(8)" ::: "memory"); break;
-    case 9: asm volatile("s_waitcnt vmcnt(9)" ::: "memory"); break;
-    case 10: asm volatile("s_waitcnt vmcnt(10)" ::: "memory"); break;
-    case 11: asm volatile("s_waitcnt vmcnt(11)" ::: "memory"); break;
-    case 12: asm volatile("s_waitcnt vmcnt(12)" ::: "memory"); break;
-    case 13: asm volatile("s_waitcnt vmcnt(13)" ::: "memory"); break;
-    case 14: asm volatile("s_waitcnt vmcnt(14)" ::: "memory"); break;
-    case 15: asm volatile("s_waitcnt vmcnt(15)" ::: "memory"); break;
-    case 16: asm volatile("s_waitcnt vmcnt(16)" ::: "memory"); break;
-    case 17: asm volatile("s_waitcnt vmcnt(17)" ::: "memory"); break;
-    case 18: asm volatile("s_waitcnt vmcnt(18)" ::: "memory"); break;
-    case 19: asm volatile("s_waitcnt vmcnt(19)" ::: "memory"); break;
-    case 20: asm volatile("s_waitcnt vmcnt(20)" ::: "memory"); break;
-    case 21: asm volatile("s_waitcnt vmcnt(21)" ::: "memory"); break;
-    default: asm volatile("s_waitcnt vmcnt(0)" ::: "memory"); break;
-    }
+// Source byte of lane `lane`'s 16 bytes of 1 KB DMA piece c, in a chunk block of NPL planes of ROWS rows x
+// 64 B.  The DMA writes LDS lane-linearly (image unit q = 64 c + lane = (plane, row, slot)), so the bank
+// swizzle of x6_slot goes on the source side.  (% NPL: where the pieces do not split evenly over the waves,
+// the indices past the last piece -- copies predicated off -- wrap to an offset inside the block.)
+template <int ROWS, int NPL>
+__device__ __forceinline__ int dma_piece_src(int c, int lane) {
+    const int q = 64 * c + lane, p = (q / (ROWS * 4)) % NPL, r = (q >> 2) % ROWS, sl = q & 3;
+    return p * (ROWS * 64) + r * 64 + 16 * (sl ^ ((r >> 1) & 3));
 }
 
 // acc[TM][TN] (+)= A(rb rows) · B(col tile)ᵀ for a BM x BN tile (BN = 64 or 80), waves WM x WN, wave
-// tile (BM / WM) x (BN / WN), S LDS stages (S - 1 chunks in flight behind the one multiplied) of CPS
-// chunks each.  Uses lds[0 .. S * CPS * x6_stage_bytes<BM, BN>()); on return every DMA has landed and
+// tile (BM / WM) x (BN / WN), two LDS stages (one chunk or super-chunk in flight behind the one multiplied)
+// of CPS chunks each.  Uses lds[0 .. 2 * CPS * x6_stage_bytes<BM, BN>()); on return every DMA has landed and
 // all waves are past their last LDS read (the caller may reuse the LDS after one __syncthreads()).
 struct NoHook { __device__ void operator()(int) const {} };
 
@@ -683,10 +664,7 @@ __device__ __forceinline__ void dispatch_upto(int n, F &&f) {
 // there land behind the first chunk's MFMAs instead of delaying the first chunk's wait); hook(1): once
 // more one chunk later (or right after hook(0) with a single chunk), when hook(0)'s loads have landed --
 // for loads whose addresses depend on them
-
-// BPIPE: B fragments one column tile at a time, the next one in flight (two sets of 3 registers x 4
-// instead of TN sets): fewer VGPRs for kernels that must co-reside two per CU
-template <int BM, int BN, int WM, int WN, int S = 2, int CPS = 1, bool BPIPE = false, typename Hook = NoHook>
+template <int BM, int BN, int WM, int WN, int CPS = 1, typename Hook = NoHook>
 __device__ __forceinline__ void x6_mainloop(const X6Operands &O, uint8_t *lds,
                                             floatx4 (&acc)[BM / WM / 16][BN / WN / 16], const Hook &hook = Hook()) {
     constexpr int NW = WM * WN, TM = BM / WM / 16, TN = BN / WN / 16;
@@ -697,19 +675,12 @@ __device__ __forceinline__ void x6_mainloop(const X6Operands &O, uint8_t *lds,
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
     const int wi = wave / WN, wj = wave % WN, g = lane >> 4, i16 = lane & 15;
 
-    // piece c of wave w = c * NW + w (interleaved, so that uneven counts fall on the last pieces);
-    // lane l -> image unit q = 64 c + l = (plane, row, slot) -> source byte in the chunk block
+    // piece c of wave w = c * NW + w (interleaved, so that uneven counts fall on the last pieces)
     int asrc[APW], bsrc[BPW];
 #pragma unroll
-    for (int j = 0; j < APW; ++j) {
-        const int q = 64 * (j * NW + wave) + lane, p = (q / (BM * 4)) % 3, r = (q >> 2) % BM, sl = q & 3;
-        asrc[j] = p * APL + r * 64 + 16 * (sl ^ ((r >> 1) & 3));
-    }
+    for (int j = 0; j < APW; ++j) asrc[j] = dma_piece_src<BM, 3>(j * NW + wave, lane);
 #pragma unroll
-    for (int j = 0; j < BPW; ++j) {
-        const int q = 64 * (j * NW + wave) + lane, p = (q / (BN * 4)) % 3, r = (q >> 2) % BN, sl = q & 3;
-        bsrc[j] = p * BPL + r * 64 + 16 * (sl ^ ((r >> 1) & 3));
-    }
+    for (int j = 0; j < BPW; ++j) bsrc[j] = dma_piece_src<BN, 3>(j * NW + wave, lane);
     const int nchunks = O.kc0 + O.kc1;
     auto issue = [&](int kc, int stage) {
         const bool s1 = kc >= O.kc0;
@@ -739,27 +710,6 @@ __device__ __forceinline__ void x6_mainloop(const X6Operands &O, uint8_t *lds,
         constexpr int NA = decltype(na_c)::value;
         // plane products hh, hm, mh, hl, lh, mm
         constexpr int PA[6] = {0, 0, 1, 0, 2, 1}, PB[6] = {0, 1, 0, 2, 0, 1};
-        if constexpr (BPIPE) {
-            bf16x8 af[TM][3], bq[2][3];
-#pragma unroll
-            for (int p = 0; p < 3; ++p) {
-#pragma unroll
-                for (int a = 0; a < NA; ++a) af[a][p] = *reinterpret_cast<const bf16x8 *>(st + p * APL + ao[a]);
-                bq[0][p] = *reinterpret_cast<const bf16x8 *>(st + p * BPL + bo[0]);
-            }
-#pragma unroll
-            for (int b = 0; b < TN; ++b) {
-                if (b + 1 < TN)
-#pragma unroll
-                    for (int p = 0; p < 3; ++p) bq[(b + 1) & 1][p] = *reinterpret_cast<const bf16x8 *>(st + p * BPL + bo[b + 1]);
-#pragma unroll
-                for (int t = 0; t < 6; ++t)
-#pragma unroll
-                    for (int a = 0; a < NA; ++a)
-                        acc[a][b] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(af[a][PA[t]], bq[b & 1][PB[t]], acc[a][b], 0, 0, 0);
-            }
-            return;
-        }
         bf16x8 af[TM][3], bfr[TN][3];
 #pragma unroll
         for (int p = 0; p < 3; ++p) {
@@ -781,19 +731,9 @@ __device__ __forceinline__ void x6_mainloop(const X6Operands &O, uint8_t *lds,
     for (int a = 0; a < TM; ++a)
 #pragma unroll
         for (int b = 0; b < TN; ++b) acc[a][b] = floatx4{0.f, 0.f, 0.f, 0.f};
-    // this wave's DMA instructions per chunk (the same for every chunk)
-    int mine = 0;
-#pragma unroll
-    for (int j = 0; j < APW; ++j) {
-        const int c = j * NW + wave;
-        mine += (AP % NW == 0 || c < AP) && 16 * (c % (BM / 16)) < O.a_rows;
-    }
-#pragma unroll
-    for (int j = 0; j < BPW; ++j) mine += BP % NW == 0 || j * NW + wave < BP;
     if constexpr (CPS > 1) {
-        // CPS chunks per stage (two stages): one barrier per CPS chunks; stage s holds the chunk images
-        // of super-chunk s back to back
-        static_assert(S == 2, "multi-chunk stages use two stages");
+        // CPS chunks per stage: one barrier per CPS chunks; stage s holds the chunk images of super-chunk s
+        // back to back
         const int nsc = (nchunks + CPS - 1) / CPS;
         auto issue_sc = [&](int sc, int stage) {
 #pragma unroll
@@ -813,31 +753,62 @@ __device__ __forceinline__ void x6_mainloop(const X6Operands &O, uint8_t *lds,
                 if (sc * CPS + q < nchunks) compute(lds + ((sc & 1) * CPS + q) * STAGE);
         }
     } else {
+        constexpr int AHEAD = 1;  // chunks in flight behind the one multiplied
 #pragma unroll
-        for (int c = 0; c < S - 1; ++c)
+        for (int c = 0; c < AHEAD; ++c)
             if (c < nchunks) issue(c, c);
         for (int kc = 0; kc < nchunks; ++kc) {
-            // chunk kc landed for this wave (younger chunks kc+1 .. kc+S-2 may stay in flight), then for
-            // every wave; every wave is done reading stage (kc + S - 1) % S (= the one read at kc - 1)
-            if constexpr (S == 2) asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-            else wait_vmcnt(min(S - 2, nchunks - 1 - kc) * mine);
+            // chunk kc landed for this wave, then for every wave; every wave is done reading the other
+            // stage (the one read at kc - 1)
+            asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
             asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
             __builtin_amdgcn_s_barrier();
-            // S > 2: the hook's loads go out before the DMA of chunk S - 1, so that the partial
-            // vmcnt waits above (which count only DMA instructions) find them among the older ones
-            if constexpr (S > 2) {
-                if (kc == 0) hook(0);
-                if (kc == 1 || (kc == 0 && nchunks == 1)) hook(1);
-            }
-            if (kc + S - 1 < nchunks) issue(kc + S - 1, (kc + S - 1) % S);
-            if constexpr (S == 2) {
-                if (kc == 0) hook(0);
-                if (kc == 1 || (kc == 0 && nchunks == 1)) hook(1);
-            }
-            compute(lds + (kc % S) * STAGE);
+            if (kc + AHEAD < nchunks) issue(kc + AHEAD, (kc + AHEAD) % 2);
+            if (kc == 0) hook(0);
+            if (kc == 1 || (kc == 0 && nchunks == 1)) hook(1);
+            compute(lds + (kc % 2) * STAGE);
         }
     }
     asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
+}
+
+// One 32-column chunk of an fp16-pair GEMM for one consumer wave: acc[a][b] += A tile a · (B tile b)ᵀ for the
+// wave's first NA 16-row tiles and all TN column tiles, three v_mfma_f32_16x16x32_f16 per tile (hi hi, hi lo,
+// lo hi).  sa / sb: the stage's A / B images (hi plane, then lo plane APL / BPL bytes on), ao / bo: this lane's
+// fragment offsets in a plane (x6_slot).  SCALE_A: every A fragment is multiplied by fl first (v_pk_mul_f16).
+template <int NA, bool SCALE_A, int APL, int BPL, int TM, int TN>
+__device__ __forceinline__ void h2_chunk_product(const uint8_t *sa, const uint8_t *sb, const int (&ao)[TM],
+                                                 const int (&bo)[TN], floatx4 (&acc)[TM][TN], _Float16 fl) {
+    f16x8 af[TM][2], bq[2][2];
+#pragma unroll
+    for (int p = 0; p < 2; ++p) {
+#pragma unroll
+        for (int a = 0; a < NA; ++a) {
+            af[a][p] = *reinterpret_cast<const f16x8 *>(sa + p * APL + ao[a]);
+            if constexpr (SCALE_A) af[a][p] = af[a][p] * fl;
+        }
+        bq[0][p] = *reinterpret_cast<const f16x8 *>(sb + p * BPL + bo[0]);
+    }
+    // column tile b: hi hi, the next tile's fragment reads, hi lo and lo hi -- pinned in that order (left to
+    // itself the scheduler issued each tile's reads just before their use, and its LDS wait then also covered
+    // the reads issued after them)
+#pragma unroll
+    for (int b = 0; b < TN; ++b) {
+#pragma unroll
+        for (int a = 0; a < NA; ++a)
+            acc[a][b] = __builtin_amdgcn_mfma_f32_16x16x32_f16(af[a][0], bq[b & 1][0], acc[a][b], 0, 0, 0);
+        __builtin_amdgcn_sched_barrier(0);
+        if (b + 1 < TN)
+#pragma unroll
+            for (int p = 0; p < 2; ++p) bq[(b + 1) & 1][p] = *reinterpret_cast<const f16x8 *>(sb + p * BPL + bo[b + 1]);
+        __builtin_amdgcn_sched_barrier(0);
+#pragma unroll
+        for (int a = 0; a < NA; ++a) {
+            acc[a][b] = __builtin_amdgcn_mfma_f32_16x16x32_f16(af[a][0], bq[b & 1][1], acc[a][b], 0, 0, 0);
+            acc[a][b] = __builtin_amdgcn_mfma_f32_16x16x32_f16(af[a][1], bq[b & 1][0], acc[a][b], 0, 0, 0);
+        }
+        __builtin_amdgcn_sched_barrier(0);
+    }
 }
 
 // ---------------------------------------------------------------------------------------------
@@ -865,10 +836,7 @@ __device__ __forceinline__ void x6_mainloop(const X6Operands &O, uint8_t *lds,
 // producers store A H2_A_STAGES - 1 chunks ahead (H2_A_STAGES A stages).  (Measured, same box: three A
 // stages +1.3 us per launch, B two chunks ahead +0.4 us, all of a chunk's fragments read before its first
 // MFMA +0.4 us, 3 / 4 / 6 register sets in flight 16.6 / 17.5 / 22.4 us: tools/prof_libs.sh variants.)
-#ifndef WD_H2_B_AHEAD
-#define WD_H2_B_AHEAD 1
-#endif
-constexpr int H2_B_AHEAD = WD_H2_B_AHEAD, H2_A_STAGES = 2;
+constexpr int H2_B_AHEAD = 1, H2_A_STAGES = 2;
 template <int BM, int BN>
 constexpr int h2_lds_bytes() { return H2_A_STAGES * (2 * BM * 64) + (H2_B_AHEAD + 1) * (2 * BN * 64); }
 
@@ -922,14 +890,10 @@ __device__ __forceinline__ void h2_mainloop_ws(const uint8_t *bsrc_base, int nch
         __builtin_amdgcn_s_waitcnt(0xc07f);
         return;
     }
-    // ---- consumers: B piece c = 4 j + w4 of the chunk block; lane l -> image unit q = 64 c + l, whose
-    // source carries the bank swizzle (the DMA writes LDS lane-linearly)
+    // ---- consumers: B piece c = 4 j + w4 of the chunk block
     int bsrc[BPW];
 #pragma unroll
-    for (int j = 0; j < BPW; ++j) {
-        const int q = 64 * (4 * j + w4) + lane, p = (q / (BN * 4)) % 2, r = (q >> 2) % BN, sl = q & 3;
-        bsrc[j] = p * BPL + r * 64 + 16 * (sl ^ ((r >> 1) & 3));
-    }
+    for (int j = 0; j < BPW; ++j) bsrc[j] = dma_piece_src<BN, 2>(4 * j + w4, lane);
     auto issue_b = [&](int kc) {
         const uint8_t *bblk = bsrc_base + (size_t)kc * (2 * BPL);
         uint8_t *st = lds + NA * ASTAGE + (kc % NB) * BSTAGE;
@@ -943,60 +907,29 @@ __device__ __forceinline__ void h2_mainloop_ws(const uint8_t *bsrc_base, int nch
 #pragma unroll
     for (int b = 0; b < TN; ++b) bo[b] = x6_slot(16 * b + i16, g);
     const int na = min(TM, max(0, (a_rows - 32 * w4 + 15) >> 4));
-    auto compute_n = [&](const uint8_t *st, const uint8_t *sb, auto na_c) {
-        constexpr int NA = decltype(na_c)::value;
-        f16x8 af[TM][2], bq[2][2];
-#pragma unroll
-        for (int p = 0; p < 2; ++p) {
-#pragma unroll
-            for (int a = 0; a < NA; ++a) af[a][p] = *reinterpret_cast<const f16x8 *>(st + p * APL + ao[a]);
-            bq[0][p] = *reinterpret_cast<const f16x8 *>(sb + p * BPL + bo[0]);
-        }
-        // column tile b: hi hi, the next tile's fragment reads, hi lo and lo hi -- pinned in that order (left
-        // to itself the scheduler issued each tile's reads just before their use, and its LDS wait then also
-        // covered the reads issued after them)
-#pragma unroll
-        for (int b = 0; b < TN; ++b) {
-#pragma unroll
-            for (int a = 0; a < NA; ++a)
-                acc[a][b] = __builtin_amdgcn_mfma_f32_16x16x32_f16(af[a][0], bq[b & 1][0], acc[a][b], 0, 0, 0);
-            __builtin_amdgcn_sched_barrier(0);
-            if (b + 1 < TN)
-#pragma unroll
-                for (int p = 0; p < 2; ++p) bq[(b + 1) & 1][p] = *reinterpret_cast<const f16x8 *>(sb + p * BPL + bo[b + 1]);
-            __builtin_amdgcn_sched_barrier(0);
-#pragma unroll
-            for (int a = 0; a < NA; ++a) {
-                acc[a][b] = __builtin_amdgcn_mfma_f32_16x16x32_f16(af[a][0], bq[b & 1][1], acc[a][b], 0, 0, 0);
-                acc[a][b] = __builtin_amdgcn_mfma_f32_16x16x32_f16(af[a][1], bq[b & 1][0], acc[a][b], 0, 0, 0);
-            }
-            __builtin_amdgcn_sched_barrier(0);
-        }
-    };
 #pragma unroll
     for (int a = 0; a < TM; ++a)
 #pragma unroll
         for (int b = 0; b < TN; ++b) acc[a][b] = floatx4{0.f, 0.f, 0.f, 0.f};
-    // this wave's copies per chunk (uniform)
-    int mine = 0;
-#pragma unroll
-    for (int j = 0; j < BPW; ++j) mine += BP % 4 == 0 || 4 * j + w4 < BP;
 #pragma unroll
     for (int c = 0; c < H2_B_AHEAD; ++c)
         if (c < nchunks) issue_b(c);
     for (int kc = 0; kc < nchunks; ++kc) {
-        // chunk kc's B landed for this wave (the H2_B_AHEAD - 1 younger chunks may stay in flight), this
-        // wave's fragment reads done; then for every wave: A chunk kc staged, B stage (kc + H2_B_AHEAD) % NB
-        // read by all (at kc - 1)
+        // chunk kc's B landed for this wave (one chunk ahead: nothing younger is in flight), this wave's
+        // fragment reads done; then for every wave: A chunk kc staged, B stage (kc + H2_B_AHEAD) % NB read by
+        // all (at kc - 1)
+        static_assert(H2_B_AHEAD == 1, "the wait below leaves no younger chunk in flight");
         if (WD_STAMPS && wave == 0) wd_lstamp(kc, 0);
-        wait_vmcnt(min(H2_B_AHEAD - 1, nchunks - 1 - kc) * mine);
+        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
         asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
         if (WD_STAMPS && wave == 0) wd_lstamp(kc, 1);
         __builtin_amdgcn_s_barrier();
         if (WD_STAMPS && wave == 0) wd_lstamp(kc, 2);
         if (kc + H2_B_AHEAD < nchunks) issue_b(kc + H2_B_AHEAD);
         const uint8_t *st = lds + (kc % NA) * ASTAGE, *sb = lds + NA * ASTAGE + (kc % NB) * BSTAGE;
-        dispatch_upto<TM>(na, [&](auto c) { compute_n(st, sb, c); });
+        dispatch_upto<TM>(na, [&](auto na_c) {
+            h2_chunk_product<decltype(na_c)::value, false, APL, BPL>(st, sb, ao, bo, acc, (_Float16)1);
+        });
         if (WD_STAMPS && wave == 0) {
             asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
             wd_lstamp(kc, 3);
@@ -1029,22 +962,14 @@ __device__ __forceinline__ void h2_mainloop_ws(const uint8_t *bsrc_base, int nch
 // Words: lane l of every consumer wave holds word l of the block (nw <= 64, lane_word), group of column
 // c = c / G; nchunks <= 64.
 // ---------------------------------------------------------------------------------------------
-// (2 chunks in flight + the one multiplied; WD_H2P_STAGES 4: 104 KB of LDS, one layer workgroup per CU, measured)
-#ifndef WD_H2P_STAGES
-#define WD_H2P_STAGES 3
-#endif
-constexpr int H2P_STAGES = WD_H2P_STAGES;
+// (2 chunks in flight + the one multiplied; 4 stages: 104 KB of LDS, one layer workgroup per CU, measured --
+// DESIGN.md "Measured dead ends")
+constexpr int H2P_STAGES = 3;
 template <int BM, int BN>
 constexpr int h2p_stage_bytes() { return 2 * BM * 64 + 2 * BN * 64; }
 template <int BM, int BN>
 constexpr int h2p_lds_bytes() { return H2P_STAGES * h2p_stage_bytes<BM, BN>(); }
 
-// FRAG (fragment schedule; tools/ring_probe.hip measures the variants): 0: each column tile's next B
-// fragments read after its first MFMAs; 1: read before them; 2: every B fragment of the chunk read before
-// the first MFMA
-#ifndef WD_H2P_FRAG
-#define WD_H2P_FRAG 0
-#endif
 // rows(): the block's live rows (a_rows), words(): this lane's scale word (lane_word) -- functors, because both
 // are dependent loads (kernel arguments -> block row / words, the words a loop of loads and waits) that the two
 // roles need at different times: the consumers call both before their loop; the loaders call rows() alone, so
@@ -1053,33 +978,24 @@ constexpr int h2p_lds_bytes() { return H2P_STAGES * h2p_stage_bytes<BM, BN>(); }
 // "params", profiles/prologue_stamps_*.txt).  The role branch is on a readfirstlane'd wave index: a scalar
 // branch, so what rows() loads stays in scalar registers past the join.
 //
-// EARLY (WD_H2P_EARLY, measured, not kept: DESIGN.md "Measured dead ends"): the loaders' first NS - 1 chunks
-// copy ALL of A's 16-row groups and are issued BEFORE rows() -- neither source address needs the block row, it
-// only says which groups to skip.  Rows past the block's last live group are stale bytes of the pair buffer
-// (inside it: the buffers hold BM rows for every block, fwd_layout's Mp / Ab), land in LDS rows no consumer
-// reads (`na`) and are never multiplied (tests/test_early_copies_gpu.py runs on a 0xFF-filled workspace).
+// (Measured, not kept: the loaders' first copies issued before rows(), for all of A's 16-row groups: DESIGN.md
+// "Measured dead ends".  16-row groups past the block's rows are not copied; whatever their LDS rows hold is
+// never multiplied -- `na` -- which tests/test_early_copies_gpu.py checks on a 0xFF-filled workspace.)
 //
-// LoaderHook: what the caller's loader waves do around their copy loop -- issue(): right after the first
-// copies (plain loads into registers of the hook, landing behind the loop); finish(): after the last copy
-// has landed and every consumer is past chunk nchunks - 2 (LDS stores into the tail of ring stage NS - 1)
-#ifndef WD_H2P_EARLY
-#define WD_H2P_EARLY 0
-#endif
-// (the scalar role branch; 0: the branch on tid >> 6, divergent to the compiler -- measured, four alternating
-// headline runs on one box: 210.1-214.5 M edges/s against 216.1-218.3 with it and 207.2-212.1 for the parent,
-// profiles/prologue_parts_ab.txt)
-#ifndef WD_H2P_UNIFORM
-#define WD_H2P_UNIFORM 1
-#endif
+// (The scalar role branch against the branch on tid >> 6, divergent to the compiler -- measured, four
+// alternating headline runs on one box: 216.1-218.3 M edges/s against 210.1-214.5, and 207.2-212.1 for the
+// parent, profiles/prologue_parts_ab.txt.)
+//
+// LoaderHook: what the caller's loader waves do after their copy loop -- finish(): after the last copy has
+// landed and every consumer is past chunk nchunks - 2 (loads, then LDS stores into the tail of ring stage
+// NS - 1)
 struct NoLoaderHook {
-    __device__ void issue() {}
     __device__ void finish() {}
 };
-template <int BM, int BN, int FRAG = WD_H2P_FRAG, typename Rows, typename Words, typename LoaderHook = NoLoaderHook>
+template <int BM, int BN, typename Rows, typename Words, typename LoaderHook = NoLoaderHook>
 __device__ __forceinline__ void h2_mainloop_pairs(const uint8_t *a_src, const uint8_t *b_src, int nchunks, Rows &&rows,
                                                   Words &&words, int G, uint8_t *lds, floatx4 (&acc)[BM / 64][BN / 16],
                                                   int &se_out, LoaderHook &&lhook = LoaderHook()) {
-    constexpr bool EARLY = WD_H2P_EARLY;
     // (acc[BM / 64]: a consumer wave's BM / 4 rows as 16-row tiles; the layout x6_acc_to_lds<BM, BN, 4, 1> reads)
     static_assert(BM == 128 || BM == 64, "four consumer waves of BM / 4 rows");
     constexpr int RW = BM / 4, TM = RW / 16, TN = BN / 16;  // rows per consumer wave, its 16-row tiles
@@ -1087,7 +1003,7 @@ __device__ __forceinline__ void h2_mainloop_pairs(const uint8_t *a_src, const ui
     constexpr int AP = 2 * BM / 16, APW = AP / 4;        // A: 16 pieces of 1 KB per chunk, 4 per loader wave
     constexpr int BP = 2 * BN / 16, BPW = (BP + 3) / 4;  // B: 10 pieces, <= 3 per loader wave
     static_assert(AP % 4 == 0, "A pieces split evenly over the loader waves");
-    const int tid = threadIdx.x, lane = tid & 63, wave = WD_H2P_UNIFORM ? __builtin_amdgcn_readfirstlane(tid >> 6) : tid >> 6, w4 = wave & 3;
+    const int tid = threadIdx.x, lane = tid & 63, wave = __builtin_amdgcn_readfirstlane(tid >> 6), w4 = wave & 3;
     const int g = lane >> 4, i16 = lane & 15;
     // chunk kc in stage (kc + roff) % NS, so that the LAST chunk lands in stage 0: the caller may use the
     // tail of stage NS - 1 while the consumers multiply that chunk (mp_layer_kernel's epilogue lists)
@@ -1097,23 +1013,37 @@ __device__ __forceinline__ void h2_mainloop_pairs(const uint8_t *a_src, const ui
 #pragma unroll
         for (int b = 0; b < TN; ++b) acc[a][b] = floatx4{0.f, 0.f, 0.f, 0.f};
     if (wave >= 4) {  // ---- loaders
-        // this wave's pieces: source offsets in a chunk block (the DMA writes LDS lane-linearly, so the bank
-        // swizzle of x6_slot is applied on the source side) and whether each is copied
+        // this wave's pieces (A piece 4 j + w4, then B piece 4 j + w4): source offsets in a chunk block, LDS
+        // offsets in a stage, and whether each is copied.  (A's offsets are dma_piece_src<BM, 2> written out:
+        // through the helper the 128-row layer kernels' address arithmetic compiles differently.)
         int src[APW + BPW], dst[APW + BPW];
 #pragma unroll
         for (int j = 0; j < APW; ++j) {
-            const int c = 4 * j + w4, q = 64 * c + lane, p = q / (BM * 4), r = (q >> 2) % BM, sl = q & 3;
+            const int c = 4 * j + w4;
+            const int q = 64 * c + lane, p = q / (BM * 4), r = (q >> 2) % BM, sl = q & 3;
             src[j] = p * APL + r * 64 + 16 * (sl ^ ((r >> 1) & 3));
             dst[j] = 1024 * c;
         }
 #pragma unroll
         for (int j = 0; j < BPW; ++j) {
-            const int c = 4 * j + w4, q = 64 * c + lane, p = (q / (BN * 4)) % 2, r = (q >> 2) % BN, sl = q & 3;
-            src[APW + j] = p * BPL + r * 64 + 16 * (sl ^ ((r >> 1) & 3));
+            const int c = 4 * j + w4;
+            src[APW + j] = dma_piece_src<BN, 2>(c, lane);
             dst[APW + j] = 2 * APL + 1024 * c;
         }
-        // copy j of chunk kc (all: every A group, else the live ones)
-        auto issue = [&](int kc, const bool (&on)[APW + BPW]) {
+        bool on[APW + BPW];
+#pragma unroll
+        for (int j = 0; j < BPW; ++j) on[APW + j] = BP % 4 == 0 || 4 * j + w4 < BP;
+        const int a_rows = rows();
+        int mine = 0;
+#pragma unroll
+        for (int j = 0; j < APW; ++j) {
+            on[j] = 16 * ((4 * j + w4) % (BM / 16)) < a_rows;  // 16-row groups past the block's rows: not copied
+            mine += on[j];
+        }
+#pragma unroll
+        for (int j = 0; j < BPW; ++j) mine += on[APW + j];
+        mine = __builtin_amdgcn_readfirstlane(mine);  // (wave-uniform: a scalar wait below)
+        auto issue = [&](int kc) {
             uint8_t *st = lds + ((kc + roff) % NS) * STAGE;
             const uint8_t *ablk = a_src + (size_t)kc * (2 * APL), *bblk = b_src + (size_t)kc * (2 * BPL);
 #pragma unroll
@@ -1123,59 +1053,28 @@ __device__ __forceinline__ void h2_mainloop_pairs(const uint8_t *a_src, const ui
             for (int j = 0; j < BPW; ++j)
                 if (on[APW + j]) glds16_untracked(bblk + src[APW + j], st + dst[APW + j]);
         };
-        bool all[APW + BPW], on[APW + BPW];
 #pragma unroll
-        for (int j = 0; j < APW; ++j) all[j] = true;
-#pragma unroll
-        for (int j = 0; j < BPW; ++j) all[APW + j] = BP % 4 == 0 || 4 * j + w4 < BP;
-        if constexpr (EARLY) {
-            // before rows(): the copies are asm statements that clobber memory, so the block row's load stays
-            // behind them and nothing here waits for it
-#pragma unroll
-            for (int c = 0; c < NS - 1; ++c)
-                if (c < nchunks) issue(c, all);
-            __builtin_amdgcn_sched_barrier(0);
-        }
-        const int a_rows = rows();
-        int mine = 0;
-#pragma unroll
-        for (int j = 0; j < APW; ++j) {
-            on[j] = 16 * ((4 * j + w4) % (BM / 16)) < a_rows;  // 16-row groups past the block's rows: not copied
-            mine += on[j];
-        }
-#pragma unroll
-        for (int j = 0; j < BPW; ++j) {
-            on[APW + j] = all[APW + j];
-            mine += on[APW + j];
-        }
-        mine = __builtin_amdgcn_readfirstlane(mine);  // (wave-uniform: a scalar wait below)
-        if constexpr (!EARLY) {
-#pragma unroll
-            for (int c = 0; c < NS - 1; ++c)
-                if (c < nchunks) issue(c, on);
-        }
-        lhook.issue();
+        for (int c = 0; c < NS - 1; ++c)
+            if (c < nchunks) issue(c);
         // the loop instantiated per copy count (its steady-state wait a constant: a wait on a runtime count
-        // is a scalar branch search per chunk, ~300 cycles of the chunk period in tools/ring_probe.hip).
+        // is a scalar branch search per chunk, ~300 cycles of the chunk period in tools/ring_probe.hip; the
+        // last chunk, with nothing younger in flight, waits for zero).
         // The waits count this wave's outstanding loads from the youngest back, and loads return in issue
         // order.  Before chunk kc's wait the wave has issued chunks 0 .. min(kc + NS - 2, nchunks - 1), every
-        // one of >= M copies (EARLY: the first NS - 1 chunks carry all of A's groups, M' >= M; the rest
-        // exactly M), then at most once the hook's loads (younger than the first chunks, older than the rest).
-        // "At most n * M outstanding" with n = the number of chunks younger than kc therefore leaves
-        // outstanding only copies among the youngest n * M <= the younger chunks' own: chunk kc, and all
-        // before it, landed.  Larger first chunks and the hook's loads only make a wait cover more than it
-        // needs (at kc = 0: most of chunk 1, issued back to back with chunk 0), never less.
+        // one of exactly M copies and nothing else, so "at most n * M outstanding" with n = the number of
+        // chunks younger than kc means that chunk kc, and all before it, landed.
         dispatch_upto<APW + BPW>(mine, [&](auto m_c) {
             constexpr int M = decltype(m_c)::value;
             for (int kc = 0; kc < nchunks; ++kc) {
                 // chunk kc landed (chunks kc + 1 .. kc + NS - 2 may stay in flight); after the barrier every
                 // consumer is done reading stage (kc + NS - 1 + roff) % NS (chunk kc - 1's)
                 if (WD_STAMPS && wave == 4) wd_lstamp(kc, 4);
+                static_assert(NS == 3, "chunks younger than kc: one, or none at the last");
                 if (nchunks - 1 - kc >= NS - 2) asm volatile("s_waitcnt vmcnt(%0)" ::"n"((NS - 2) * M) : "memory");
-                else wait_vmcnt((nchunks - 1 - kc) * M);
+                else asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
                 if (WD_STAMPS && wave == 4) wd_lstamp(kc, 5);
                 __builtin_amdgcn_s_barrier();
-                if (kc + NS - 1 < nchunks) issue(kc + NS - 1, on);
+                if (kc + NS - 1 < nchunks) issue(kc + NS - 1);
             }
         });
         __builtin_amdgcn_s_waitcnt(0x0070);  // (vmcnt(0): every copy of this wave landed)
@@ -1205,45 +1104,6 @@ __device__ __forceinline__ void h2_mainloop_pairs(const uint8_t *a_src, const ui
     };
     const uint32_t fcode = f16code(s0) | (f16code(s1) << 16);
     const int fsh = lane < 32 ? 0 : 16;
-    auto compute_n = [&](const uint8_t *st, const uint8_t *sb, auto na_c, _Float16 fl) {
-        constexpr int NA = decltype(na_c)::value;
-        constexpr int SCH = FRAG & 3, NB = SCH == 2 ? TN : 2;
-        f16x8 af[TM][2], bq[NB][2];
-#pragma unroll
-        for (int p = 0; p < 2; ++p) {
-#pragma unroll
-            for (int a = 0; a < NA; ++a) {
-                af[a][p] = *reinterpret_cast<const f16x8 *>(st + p * APL + ao[a]);
-                af[a][p] = af[a][p] * fl;
-            }
-#pragma unroll
-            for (int b = 0; b < (SCH == 2 ? TN : 1); ++b) bq[b][p] = *reinterpret_cast<const f16x8 *>(sb + p * BPL + bo[b]);
-        }
-#pragma unroll
-        for (int b = 0; b < TN; ++b) {
-            const int cb = SCH == 2 ? b : (b & 1);
-            if constexpr (SCH == 1) {
-                if (b + 1 < TN)
-#pragma unroll
-                    for (int p = 0; p < 2; ++p) bq[(b + 1) & 1][p] = *reinterpret_cast<const f16x8 *>(sb + p * BPL + bo[b + 1]);
-                __builtin_amdgcn_sched_barrier(0);
-            }
-#pragma unroll
-            for (int a = 0; a < NA; ++a)
-                acc[a][b] = __builtin_amdgcn_mfma_f32_16x16x32_f16(af[a][0], bq[cb][0], acc[a][b], 0, 0, 0);
-            __builtin_amdgcn_sched_barrier(0);
-            if (SCH == 0 && b + 1 < TN)
-#pragma unroll
-                for (int p = 0; p < 2; ++p) bq[(b + 1) & 1][p] = *reinterpret_cast<const f16x8 *>(sb + p * BPL + bo[b + 1]);
-            __builtin_amdgcn_sched_barrier(0);
-#pragma unroll
-            for (int a = 0; a < NA; ++a) {
-                acc[a][b] = __builtin_amdgcn_mfma_f32_16x16x32_f16(af[a][0], bq[cb][1], acc[a][b], 0, 0, 0);
-                acc[a][b] = __builtin_amdgcn_mfma_f32_16x16x32_f16(af[a][1], bq[cb][0], acc[a][b], 0, 0, 0);
-            }
-            __builtin_amdgcn_sched_barrier(0);
-        }
-    };
     dispatch_upto<TM>(na, [&](auto na_c) {
         for (int kc = 0; kc < nchunks; ++kc) {
             // this wave's fragment reads done (the stage of chunk kc - 1 is refilled after the barrier);
@@ -1256,7 +1116,7 @@ __device__ __forceinline__ void h2_mainloop_pairs(const uint8_t *a_src, const ui
             const uint8_t *st = lds + ((kc + roff) % NS) * STAGE, *sb = st + 2 * APL;
             const uint32_t fc = __builtin_amdgcn_readlane(fcode, kc);
             const _Float16 fl = __builtin_bit_cast(_Float16, (unsigned short)((fc >> fsh) & 0xffffu));
-            compute_n(st, sb, na_c, fl);
+            h2_chunk_product<decltype(na_c)::value, true, APL, BPL>(st, sb, ao, bo, acc, fl);
             if (WD_STAMPS && wave == 0) {
                 asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
                 wd_lstamp(kc, 3);
@@ -1267,9 +1127,12 @@ __device__ __forceinline__ void h2_mainloop_pairs(const uint8_t *a_src, const ui
     se_out = cur >= BIG ? -1 : cur;
 }
 
-// acc tile -> LDS fp32 [BM][BN + 4] (C/D map of 16x16: col = lane & 15, row = 4 (lane >> 4) + reg)
-template <int BM, int BN, int WM, int WN>
-__device__ __forceinline__ void x6_acc_to_lds(const floatx4 (&acc)[BM / WM / 16][BN / WN / 16], float *cl) {
+// acc tile -> LDS fp32 [BM][BN + 4] (C/D map of 16x16: col = lane & 15, row = 4 (lane >> 4) + reg).  SCALED:
+// every value multiplied by sa and then sb (the h2 operands' inverse scales: powers of two, exact unless the
+// result is subnormal)
+template <int BM, int BN, int WM, int WN, bool SCALED = false>
+__device__ __forceinline__ void x6_acc_to_lds(const floatx4 (&acc)[BM / WM / 16][BN / WN / 16], float *cl,
+                                              float sa = 1.f, float sb = 1.f) {
     constexpr int TM = BM / WM / 16, TN = BN / WN / 16, LDC = BN + 4;
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
     const int wi = wave / WN, wj = wave % WN, g = lane >> 4, i16 = lane & 15;
@@ -1279,24 +1142,8 @@ __device__ __forceinline__ void x6_acc_to_lds(const floatx4 (&acc)[BM / WM / 16]
         for (int b = 0; b < TN; ++b)
 #pragma unroll
             for (int r = 0; r < 4; ++r)
-                cl[(wi * (BM / WM) + a * 16 + 4 * g + r) * LDC + wj * (BN / WN) + b * 16 + i16] = acc[a][b][r];
-}
-
-// the same with every value multiplied by sa and then sb (the h2 operands' inverse scales: powers of two,
-// exact unless the result is subnormal)
-template <int BM, int BN, int WM, int WN>
-__device__ __forceinline__ void x6_acc_to_lds_scaled(const floatx4 (&acc)[BM / WM / 16][BN / WN / 16], float *cl,
-                                                     float sa, float sb) {
-    constexpr int TM = BM / WM / 16, TN = BN / WN / 16, LDC = BN + 4;
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    const int wi = wave / WN, wj = wave % WN, g = lane >> 4, i16 = lane & 15;
-#pragma unroll
-    for (int a = 0; a < TM; ++a)
-#pragma unroll
-        for (int b = 0; b < TN; ++b)
-#pragma unroll
-            for (int r = 0; r < 4; ++r)
-                cl[(wi * (BM / WM) + a * 16 + 4 * g + r) * LDC + wj * (BN / WN) + b * 16 + i16] = acc[a][b][r] * sa * sb;
+                cl[(wi * (BM / WM) + a * 16 + 4 * g + r) * LDC + wj * (BN / WN) + b * 16 + i16] =
+                    SCALED ? acc[a][b][r] * sa * sb : acc[a][b][r];
 }
 
 struct X6PParams {
@@ -1314,8 +1161,7 @@ struct X6PParams {
 __global__ __launch_bounds__(512) void gemm_x6g_kernel(X6PParams P) {
     constexpr int BM = 64, NT = 512;
     // two LDS stages (three measured slower: 11.1 vs 11.0 us here, 9.6 vs 8.5 us on QM9-shaped batches)
-    constexpr int S = 2;
-    __shared__ __attribute__((aligned(16))) uint8_t lds[S * x6_stage_bytes<BM, 64>()];
+    __shared__ __attribute__((aligned(16))) uint8_t lds[2 * x6_stage_bytes<BM, 64>()];
     const int tile = xcd_tile(blockIdx.x, P.tiles_m * P.tiles_n);
     const int mt = tile / P.tiles_n, nt = tile % P.tiles_n;
     const int m0 = mt * BM, n0 = nt * X6_BN;
@@ -1328,7 +1174,7 @@ __global__ __launch_bounds__(512) void gemm_x6g_kernel(X6PParams P) {
     O.a_rows = BM;
     O.b = P.b + (size_t)nt * (P.kpb >> 5) * X6_BLOCK;
     floatx4 acc[1][2];
-    x6_mainloop<BM, 64, 4, 2, S>(O, lds, acc);
+    x6_mainloop<BM, 64, 4, 2>(O, lds, acc);
     __syncthreads();
     float *cl = reinterpret_cast<float *>(lds);
     x6_acc_to_lds<BM, 64, 4, 2>(acc, cl);

@@ -59,31 +59,15 @@ __device__ __forceinline__ size_t x6_tile_off(int r, int k, int kp) {
 // fused layer than default-policy stores, which leave the lines dirty for the kernel-end write-back).
 // Emitted as relaxed agent-scope 8-byte atomic stores (global_store_dwordx2 ... sc1), which the
 // compiler tracks in its vmcnt accounting (inline-asm stores are invisible to it and broke later
-// waits).  WD_WT (experiments): 0 = default policy, 1 = sc1, 3 = nt.
-#ifndef WD_WT
-#define WD_WT 1
-#endif
-constexpr int WD_WT_POL = WD_WT == 1 ? 16 : WD_WT == 3 ? 2 : 0;  // buffer-store aux bits: sc1 = 16, nt = 2
+// waits).  The buffer stores carry the same policy in their aux bits.
+constexpr int WT_SC1 = 16;  // buffer-store aux bits: sc1
 __device__ __forceinline__ void gst8(void *p, const uint2 &v) {
-    if constexpr (WD_WT == 1) {
-        const unsigned long long w = (unsigned long long)v.x | ((unsigned long long)v.y << 32);
-        __hip_atomic_store(reinterpret_cast<unsigned long long *>(p), w, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    } else if constexpr (WD_WT == 3) {
-        __builtin_nontemporal_store(v.x, reinterpret_cast<uint32_t *>(p));
-        __builtin_nontemporal_store(v.y, reinterpret_cast<uint32_t *>(p) + 1);
-    } else {
-        *reinterpret_cast<uint2 *>(p) = v;
-    }
+    const unsigned long long w = (unsigned long long)v.x | ((unsigned long long)v.y << 32);
+    __hip_atomic_store(reinterpret_cast<unsigned long long *>(p), w, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
 }
 __device__ __forceinline__ void gst16(void *p, const u32x4 &v) {
-    if constexpr (WD_WT == 1) {
-        gst8(p, make_uint2(v.x, v.y));
-        gst8(reinterpret_cast<uint8_t *>(p) + 8, make_uint2(v.z, v.w));
-    } else if constexpr (WD_WT == 3) {
-        __builtin_nontemporal_store(v, reinterpret_cast<u32x4 *>(p));
-    } else {
-        *reinterpret_cast<u32x4 *>(p) = v;
-    }
+    gst8(p, make_uint2(v.x, v.y));
+    gst8(reinterpret_cast<uint8_t *>(p) + 8, make_uint2(v.z, v.w));
 }
 
 // write values lo, hi = columns k..k+7 (k % 8 == 0) of row r into a plane-tile matrix
@@ -116,9 +100,9 @@ __device__ __forceinline__ void x6_store8_blk(__amdgpu_buffer_rsrc_t rs, int r, 
     split_pair(hi.x, hi.y, h[2], m[2], l[2]);
     split_pair(hi.z, hi.w, h[3], m[3], l[3]);
     const int o = (k >> 5) * (3 * BR * 64) + r * 64 + 2 * (k & 31);
-    __builtin_amdgcn_raw_buffer_store_b128(u32x4{h[0], h[1], h[2], h[3]}, rs, o, 0, WD_WT_POL);
-    __builtin_amdgcn_raw_buffer_store_b128(u32x4{m[0], m[1], m[2], m[3]}, rs, o + BR * 64, 0, WD_WT_POL);
-    __builtin_amdgcn_raw_buffer_store_b128(u32x4{l[0], l[1], l[2], l[3]}, rs, o + 2 * BR * 64, 0, WD_WT_POL);
+    __builtin_amdgcn_raw_buffer_store_b128(u32x4{h[0], h[1], h[2], h[3]}, rs, o, 0, WT_SC1);
+    __builtin_amdgcn_raw_buffer_store_b128(u32x4{m[0], m[1], m[2], m[3]}, rs, o + BR * 64, 0, WT_SC1);
+    __builtin_amdgcn_raw_buffer_store_b128(u32x4{l[0], l[1], l[2], l[3]}, rs, o + 2 * BR * 64, 0, WT_SC1);
 }
 
 // columns k..k+3 (k % 4 == 0): three 8-byte pieces

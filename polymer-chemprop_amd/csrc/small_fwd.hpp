@@ -150,7 +150,7 @@ __device__ __forceinline__ float4 code_sum_g(const WdAtomCode &cd, const float *
     return s;
 }
 
-// acc -> fp32 LDS tile T[row][SF_LDI] (x sa x sb, in that order: the fused layer's x6_acc_to_lds_scaled)
+// acc -> fp32 LDS tile T[row][SF_LDI] (x sa x sb, in that order: the fused layer's x6_acc_to_lds<..., true>)
 template <bool SCALED>
 __device__ __forceinline__ void sf_acc_store(const floatx4 (&acc)[3][2], float *T, float sa, float sb) {
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6, g = lane >> 4, i16 = lane & 15;

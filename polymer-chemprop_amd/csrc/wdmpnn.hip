@@ -88,22 +88,8 @@ int self_check_once() {
     return c.rc ? fail(WD_ERR_UNSUPPORTED, "libwdmpnn self-check: %s", c.why.c_str()) : 0;
 }
 
-// W_o + readout on fp16 pair tiles (1; the last pair layer writes A as pairs) or on bf16x3 planes (0) in the
-// pair-operand forward
-#ifndef WD_WO_PAIRS
-#define WD_WO_PAIRS 1
-#endif
-
-// feed events that host threads wait for: hipEventBlockingSync (the waiting thread sleeps) or 0 (polls;
-// experiments)
-#ifndef WD_FEED_EVENT_SYNC
-#define WD_FEED_EVENT_SYNC hipEventBlockingSync
-#endif
-
-// the fused backward's data-gradient GEMMs dM = Y_t W_h on fp16 pairs (1) or bf16x3 planes (0)
-#ifndef WD_BWD_H2
-#define WD_BWD_H2 1
-#endif
+// feed events that host threads wait for: the waiting thread sleeps (0 would poll)
+constexpr unsigned FEED_EVENT_FLAGS = hipEventDisableTiming | hipEventBlockingSync;
 
 inline int rup(int x, int m) { return (x + m - 1) / m * m; }
 
@@ -144,15 +130,10 @@ Variant decode_variant(int v) {
     return V;
 }
 
-#ifndef WD_EMBED_PAIR_BN
-#define WD_EMBED_PAIR_BN 32
-#endif
-constexpr int EPB = WD_EMBED_PAIR_BN;  // the pair path's embed tile width (a multiple of 16 dividing every Hk: 32, 64)
+constexpr int EPB = 32;  // the pair path's embed tile width (a multiple of 16 dividing every Hk: 32, 64)
 // 40-column tiles for the embed when they divide Hk: twice the workgroups of the layer tiling (two per
 // CU at the benchmark size, 37 KB of LDS each), so one's staging overlaps the other's sums
-#ifndef WD_EMBED40
-#define WD_EMBED40 1
-#endif
+constexpr int EMBED40_BN = 40;
 
 struct Dims {
     int H, Hk, T, R, Rp, Va, Vap, B, Fa, Fak, Fb, Fbk, d, dk, Hd, Hdk, Kin, Kink;
@@ -165,8 +146,8 @@ struct Dims {
     bool blocked;  // molecule-blocked fused inference forward (fused_mp.hpp)
     bool small;    // ... as ONE launch, a workgroup per block (small_fwd.hpp: blocks <= 32 rows, Hk 320)
     bool pairs;    // ... the workspace holds M_t as fp16 pair tiles (LDS-DMA layer operands)
-    bool lay_pairs;   // ... and this call's layers hand M_t on in them (pairs, unless V.staged: debug stops)
-    bool wo_pairs;    // ... and W_o + readout reads A as pair tiles the last layer wrote (else bf16x3 planes)
+    bool lay_pairs;   // ... and this call's layers hand M_t on in them (pairs, unless V.staged: debug stops), the
+                      // last one A, which W_o + readout reads as pair tiles (else bf16x3 planes)
     bool pack_pairs;  // the packed weights hold W_o's pair tiles (a function of the encoder and config only:
                       // one inference pack serves every graph)
     int bn;  // fused column tile: 80 when it divides Hk (Hk 320: 4 tiles, a workgroup per CU at the benchmark size), else 64
@@ -232,10 +213,9 @@ int get_dims(const WdGraph *g, const WdParams *p, const WdConfig *c, Dims &D) {
     D.pack_pairs = !D.atom && !D.save && D.bn == 80 && D.Hk / 32 <= 64 && V.pair_tiles;
     D.pairs = D.pack_pairs && D.blocked && D.codes;
     D.lay_pairs = D.pairs && !V.staged;
-    D.wo_pairs = D.lay_pairs && WD_WO_PAIRS;
     // (the pair path: EPB-column embed tiles, one scale word per tile of M_0; measured, same box: 64-column
     // tiles -- 320 workgroups, one round at B = 64 -- 11.29 vs 9.63 us for 32, 186.5 vs 194.0 M edges/s)
-    D.ebn = D.lay_pairs ? EPB : (WD_EMBED40 && D.Hk % 40 == 0 ? 40 : D.bn);
+    D.ebn = D.lay_pairs ? EPB : (D.Hk % EMBED40_BN == 0 ? EMBED40_BN : D.bn);
     D.etiles = D.Hk / D.ebn;
     if (D.atom && D.undirected)
         return fail(WD_ERR_UNSUPPORTED, "undirected with atom_messages (the reference indexes atom messages "
@@ -607,29 +587,15 @@ int gemm_tn(const Src &dZ, const Src &X, int n_out, int m_rows, const TnPlan &tp
         if (sact < 0 || !b_words || a_cv <= 0 || b_bm <= 0 || b_tn <= 0)
             return fail(WD_ERR_ARG, "gemm_tn: fp16-pair words need a SEG_ACT operand and both word arrays");
         P.a_words = a_words; P.a_cv = a_cv; P.b_words = b_words; P.b_bm = b_bm; P.b_tn = b_tn;
-        switch (sact) {
-        case ACT_RELU: hipLaunchKernelGGL((gemm_tn_x6_kernel<ACT_RELU, true, true>), grid, dim3(256), 0, st, P); break;
-        case ACT_LEAKY: hipLaunchKernelGGL((gemm_tn_x6_kernel<ACT_LEAKY, true, true>), grid, dim3(256), 0, st, P); break;
-        case ACT_PRELU: hipLaunchKernelGGL((gemm_tn_x6_kernel<ACT_PRELU, true, true>), grid, dim3(256), 0, st, P); break;
-        case ACT_TANH: hipLaunchKernelGGL((gemm_tn_x6_kernel<ACT_TANH, true, true>), grid, dim3(256), 0, st, P); break;
-        case ACT_SELU: hipLaunchKernelGGL((gemm_tn_x6_kernel<ACT_SELU, true, true>), grid, dim3(256), 0, st, P); break;
-        case ACT_ELU: hipLaunchKernelGGL((gemm_tn_x6_kernel<ACT_ELU, true, true>), grid, dim3(256), 0, st, P); break;
-        default: hipLaunchKernelGGL((gemm_tn_x6_kernel<ACT_IDENTITY, true, true>), grid, dim3(256), 0, st, P); break;
-        }
-        WD_CHECK_LAUNCH("gemm_tn");
-        return 0;
     }
-    constexpr bool H2 = TN_H2;
-    switch (sact) {
-    case -1: hipLaunchKernelGGL((gemm_tn_x6_kernel<-1, false, H2>), grid, dim3(256), 0, st, P); break;
-    case ACT_RELU: hipLaunchKernelGGL((gemm_tn_x6_kernel<ACT_RELU, true, H2>), grid, dim3(256), 0, st, P); break;
-    case ACT_LEAKY: hipLaunchKernelGGL((gemm_tn_x6_kernel<ACT_LEAKY, true, H2>), grid, dim3(256), 0, st, P); break;
-    case ACT_PRELU: hipLaunchKernelGGL((gemm_tn_x6_kernel<ACT_PRELU, true, H2>), grid, dim3(256), 0, st, P); break;
-    case ACT_TANH: hipLaunchKernelGGL((gemm_tn_x6_kernel<ACT_TANH, true, H2>), grid, dim3(256), 0, st, P); break;
-    case ACT_SELU: hipLaunchKernelGGL((gemm_tn_x6_kernel<ACT_SELU, true, H2>), grid, dim3(256), 0, st, P); break;
-    case ACT_ELU: hipLaunchKernelGGL((gemm_tn_x6_kernel<ACT_ELU, true, H2>), grid, dim3(256), 0, st, P); break;
-    default: hipLaunchKernelGGL((gemm_tn_x6_kernel<ACT_IDENTITY, true, H2>), grid, dim3(256), 0, st, P); break;
-    }
+    if (sact < 0)
+        hipLaunchKernelGGL((gemm_tn_x6_kernel<-1, false, TN_H2>), grid, dim3(256), 0, st, P);
+    else
+        host_with_act(sact, [&](auto act_c) {
+            constexpr int A = decltype(act_c)::value;
+            if (a_words) hipLaunchKernelGGL((gemm_tn_x6_kernel<A, true, true>), grid, dim3(256), 0, st, P);
+            else hipLaunchKernelGGL((gemm_tn_x6_kernel<A, true, TN_H2>), grid, dim3(256), 0, st, P);
+        });
     WD_CHECK_LAUNCH("gemm_tn");
     return 0;
 }
@@ -1048,9 +1014,8 @@ int fused_layer(const FusedCtx &X, int t) {
             Q.aout = last ? nullptr : (uint8_t *)(J.ws + J.L.Mp[t & 1]);
             Q.zin = nullptr;
             Q.zout = nullptr;
-            // the last layer: A as pair tiles (D.wo_pairs), its words in the slot this layer does not read; else
-            // bf16x3 plane tiles
-            Q.apairs = last && D0.wo_pairs ? (uint8_t *)(J.ws + J.L.Ab) : nullptr;
+            // the last layer: A as pair tiles, its words in the slot this layer does not read
+            Q.apairs = last ? (uint8_t *)(J.ws + J.L.Ab) : nullptr;
             Q.amax_out = X.slot(J, t);
         }
     }, M);
@@ -1104,7 +1069,7 @@ int fused_wo_readout(const FusedCtx &X) {
         R.zosave = J.D.save ? X.F(J, J.L.Zo) : nullptr;
         if (D0.V.wo_dump && J.D.T == 3)  // (tools/debug_pairs.py)
             R.zosave = D0.lay_pairs ? X.F(J, J.L.Mp[1]) : X.F(J, J.L.Zb[1]);
-        if (D0.wo_pairs) {
+        if (D0.lay_pairs) {
             R.apairs = (const uint8_t *)(J.ws + J.L.Ab); R.a_amax = X.slot(J, J.D.T - 1); R.a_nw = Hk / BN; R.a_g = BN;
             R.woh = (const uint8_t *)(X.pk + PL.WoH); R.wo_amax = (const uint32_t *)(X.pk + PL.wo_amax) + 64;
         }
@@ -1113,7 +1078,7 @@ int fused_wo_readout(const FusedCtx &X) {
     with_jobs(X.n, M, [&](const auto &Mn, auto nj) {
         constexpr int NJ = decltype(nj)::value;
         // one batch: single-chunk stages (55 KB, co-resident with other streams' layers); several: two
-        if (D0.wo_pairs)
+        if (D0.lay_pairs)
             hipLaunchKernelGGL((wo_readout_kernel<80, 1, NJ, true>), dim3(grid), dim3(512), 0, X.st, Mn);
         else if (BN == 80)
             hipLaunchKernelGGL((wo_readout_kernel<80, NJ == 1 ? 1 : 2, NJ>), dim3(grid), dim3(64 * WoWaves<80>::WM * WoWaves<80>::WN), 0, X.st, Mn);
@@ -1529,13 +1494,13 @@ int wdmpnn_backward(const WdGraph *g, const WdParams *p, const WdConfig *c, cons
             Q.G = dZt; Q.ldg = Hk;
             Q.ptr = g->msg_gather_t.ptr; Q.idx = g->msg_gather_t.idx; Q.coef = g->msg_gather_t.coef;
             Q.rows = D.R; Q.rows_p = D.Rp; Q.cols = Hk; Q.ld = Hk; Q.out = D.undirected ? S(Bl.dMs) : Y;
-            if (WD_BWD_H2 && !D.undirected) Q.words = y_words;
+            if (!D.undirected) Q.words = y_words;
             WD_TRY(act_bwd(Q));
             if (D.undirected) {
                 ActBwd U{};
                 U.G = S(Bl.dMs); U.ldg = Hk; U.sym_rev = g->b2revb;
                 U.rows = D.R; U.rows_p = D.Rp; U.cols = Hk; U.ld = Hk; U.out = Y;
-                if (WD_BWD_H2) U.words = y_words;
+                U.words = y_words;
                 WD_TRY(act_bwd(U));
             }
         }
@@ -1556,15 +1521,15 @@ int wdmpnn_backward(const WdGraph *g, const WdParams *p, const WdConfig *c, cons
         }
         // (with Y_t as plane tiles written by the gather above and this GEMM on LDS-DMA staging, gemm_x6g: the
         // plane stores cost the gather 4-8 us, the GEMM gained 0-4.5 us; the in-kernel split is kept)
-        if (WD_BWD_H2) e.amax = m_words;
-        WD_TRY(gemm_nt(Y, Hk, Hk, nullptr, 0, 0, W(PL.WhT), Hk, D.Rp, Hk, e, st, true, WD_BWD_H2 ? y_words : nullptr,
+        e.amax = m_words;
+        WD_TRY(gemm_nt(Y, Hk, Hk, nullptr, 0, 0, W(PL.WhT), Hk, D.Rp, Hk, e, st, true, y_words,
                        Hk / 4, (const uint32_t *)W(PL.amax) + 64));
         // dW_h (+)= Y_t^T [M_{t-1} | 1], db_h (+)= sum dZ_t
         Seg m = seg_dense(F(L.Z[t - 1]), Hk, Hk);
         m.kind = SEG_ACT; m.act = c->activation; m.slope = p->prelu; m.p_drop = t - 1 == 0 ? 0.f : c->dropout;
         m.seed = c->seed; m.layer = t - 1;
         WD_TRY(gemm_tn(make_src(D.R, {seg_dense(Y, Hk, Hk)}), make_src(D.R, {m, seg_ones()}), Hk, D.R, tph,
-                       S(Bl.slab_h), t != D.T - 1, st, dZt, WD_BWD_H2 ? y_words : nullptr, Hk / 4, m_words,
+                       S(Bl.slab_h), t != D.T - 1, st, dZt, y_words, Hk / 4, m_words,
                        x6_bm(D.Rp), Hk / 64));
         cur = nxt;
     }
@@ -1909,9 +1874,9 @@ int wdmpnn_feed_create(const WdFeedSpec *spec, void **feed) {
         // (the two events host threads wait for are blocking-sync: a default event's hipEventSynchronize polls,
         // and the feeder, which runs several batches ahead, would hold a CPU busy for the whole stream -- one of
         // a rank's two CPUs when eight ranks share a 16-CPU quota)
-        ok = hipEventCreateWithFlags(&Q.copy_done, hipEventDisableTiming | WD_FEED_EVENT_SYNC) == hipSuccess &&
+        ok = hipEventCreateWithFlags(&Q.copy_done, FEED_EVENT_FLAGS) == hipSuccess &&
              hipEventCreateWithFlags(&Q.ready, hipEventDisableTiming) == hipSuccess &&
-             hipEventCreateWithFlags(&Q.released, hipEventDisableTiming | WD_FEED_EVENT_SYNC) == hipSuccess;
+             hipEventCreateWithFlags(&Q.released, FEED_EVENT_FLAGS) == hipSuccess;
     }
     if (!ok) {
         delete F;
@@ -1942,7 +1907,7 @@ int wdmpnn_feed_next(void *feed, void *stream, WdGraph *g, WdFeedBatch *info) {
         info->h2d_bytes = S.total;
     }
     F->handed = i + 1;
-    if (WD_FEED_GROUP) F->cv.notify_all();  // (the feeder groups its builds while the consumer holds built batches)
+    F->cv.notify_all();  // (the feeder groups its builds while the consumer holds built batches)
     return 0;
 }
 

@@ -1,9 +1,9 @@
 """GPU: the pair-operand layers on caller-owned workspaces whose never-written bytes are hostile.
 
 The pair layers' loader waves (gemm_x6.hpp h2_mainloop_pairs) copy M_{t-1} from pair tiles that the producers
-write only up to a block's last live 16-row group; with WD_H2P_EARLY the first NS - 1 chunks copy every group,
-past it too.  Whatever those rows hold is what the caller's workspace held, and the consumers must never
-multiply it.  The tests run wdmpnn_forward through the C-ABI on a workspace pre-filled with zero bytes and with
+write only up to a block's last live 16-row group (a measured variant, DESIGN.md "Measured dead ends", copied
+every group of the first NS - 1 chunks, past it too).  Whatever the rows past it hold is what the caller's
+workspace held, and the consumers must never multiply it.  The tests run wdmpnn_forward through the C-ABI on a workspace pre-filled with zero bytes and with
 0xFF bytes (every never-written fp16 then reads as NaN) and ask for bitwise equal, finite outputs, on blocks
 at the edges of the 16-row groups, and against the oracle and the register-staged layers.
 

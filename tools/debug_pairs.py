@@ -37,7 +37,7 @@ blocks = np.array(g.molecule_blocks(), np.int64)
 Hk = -(-H // 64) * 64
 nch = Hk // 32
 PAIRS, STAGED, WO_DUMP, stop = _native.DEBUG_PAIRS, _native.DEBUG_STAGED, _native.DEBUG_WO_DUMP, _native.variant_debug
-EPB = int(os.environ.get('WD_EMBED_PAIR_BN', '32'))  # the embed's pair tile width (wdmpnn.hip EPB)
+EPB = 32  # the embed's pair tile width (wdmpnn.hip EPB)
 
 
 def run(v):

@@ -1,5 +1,5 @@
 """Phase timeline of the pair-path embed kernel (experiment build with WD_STAMPS=1, selected with WDMPNN_LIB):
-one polymer B=64 forward (WD_EMBED_EO_LAST 0), per workgroup s_memrealtime stamps (100 MHz) at: 0 start,
+one polymer B=64 forward, per workgroup s_memrealtime stamps (100 MHz) at: 0 start,
 2 loads issued + Eo done, 3 the W_i tile in LDS, 4 Ea done, 5 inp rows stored, 6 tile max published, 7 M_0
 pair tiles stored.  (Round 6's log, profiles/round6_stamps_embed.log, also had a stamp 1 after the W_o tile.)
     WDMPNN_LIB=exp/libwdmpnn_est.so python tools/stamps_embed.py"""
