@@ -524,6 +524,71 @@ typedef struct WdHeadStackPredict {
 } WdHeadStackPredict;
 int wdmpnn_head_stack_predict(const WdHeadStackPredict *h, void *stream);
 
+/* The spectra head (dataset_type spectra, model.py:102-113, train.py:70-74, spectra_utils.py): the FFN of
+ * WdHeadStack (same x, layers, activation, slope, dropout hash, seed, scratch contract and gradient outputs)
+ * with up to WD_HEAD_MAX_SPECTRUM outputs, one per spectrum bin, the output activation s = act_s(z_L)
+ * (spectra_act 0: exp, 1: softplus) and a row loss on the masked, row-normalised output:
+ *     m_t = [target_t present],  S = sum_t m_t s_t,  p_t = m_t s_t / S,
+ *     loss_kind 0 (SID):          sum_t w_t (p_t - y_t) (log p_t - log y_t)
+ *     loss_kind 1 (Wasserstein):  sum_t w_t |cumsum(y)_t - cumsum(p)_t|
+ * summed over the rows and times inv_n.  table: [B][ld_table], targets [T] then weights w [T] (target weight *
+ * data weight * mask) as WdHead, device memory (each row is read in several passes); a target of exactly 0
+ * means "missing" (every present target is > 0 after normalize_spectra's floor): the mask comes from the
+ * targets, never from w, so a present target with weight 0 still counts in S.  exp: p and log p are the
+ * max-subtracted softmax over the present positions (finite for any finite logits); softplus:
+ * max(z, 0) + log1p(exp(-|z|)).  A row without a present target contributes loss 0 and gradient 0 (the
+ * reference: NaN).  out (or NULL) receives act_s(z_L), what the model returns in training mode.
+ * dx, every dW[l], every db[l] and dslope may each be NULL ("not wanted"), as wdmpnn_head_stack_partial; loss
+ * is always written; every wanted output is bitwise the same whatever else is wanted.  Launches: one GEMM per
+ * hidden layer, the last layer as 16 x 16 tiles over (B, T), one workgroup per row for the loss and
+ * d loss / d z_L, one launch for dz_{L-1} | dW_L | db_L | loss, then one per layer L-1 .. 1.  Fixed summation
+ * and scan orders, no float atomics.  Limits: 1 <= L <= WD_HEAD_MAX_LAYERS, F and Hf <= 4096,
+ * 1 <= T <= WD_HEAD_MAX_SPECTRUM (WD_ERR_UNSUPPORTED beyond), ld_table >= 2 T, 0 <= p < 1.  B == 0 is a no-op. */
+#define WD_HEAD_MAX_SPECTRUM 8192
+typedef struct WdHeadSpectra {
+    const float *x; int32_t ld_x;
+    int32_t B, F, Hf, T, L;
+    const float *W[WD_HEAD_MAX_LAYERS];
+    const float *b[WD_HEAD_MAX_LAYERS];
+    const float *slope;
+    const float *table; int32_t ld_table;  /* [B][ld_table]: targets [T] (0 = missing), then weights w [T] */
+    float inv_n;
+    int32_t act;
+    float p;
+    uint64_t seed;
+    int32_t spectra_act;                   /* 0 exp, 1 softplus                                     */
+    int32_t loss_kind;                     /* 0 SID, 1 Wasserstein                                  */
+    void *scratch; size_t scratch_bytes;
+    float *out;                            /* [B][T]: act_s(z_L), or NULL                           */
+    float *dx;                             /* [B][ld_x] or NULL                                     */
+    float *dW[WD_HEAD_MAX_LAYERS];         /* NULL = not wanted                                     */
+    float *db[WD_HEAD_MAX_LAYERS];
+    float *dslope;
+    float *loss;                           /* [1]                                                   */
+} WdHeadSpectra;
+/* floats: those of wdmpnn_head_stack_scratch_bytes, then z_L - b_L [B][T] (the row kernels add the bias: the
+ * softmax's differences are taken product and bias apart, so a large bias costs no precision). */
+int wdmpnn_head_spectra_scratch_bytes(int32_t B, int32_t F, int32_t Hf, int32_t T, int32_t L, size_t *bytes);
+int wdmpnn_head_spectra(const WdHeadSpectra *h, void *stream);
+/* The same head at prediction time (eval mode: no dropout), L + 1 launches.  normalize 0: out = act_s(z_L);
+ * 1: each row divided by the sum of its included positions (spectra_utils.normalize_spectra; mask [B][T],
+ * nonzero = included, NULL = all), excluded positions written as quiet NaN.
+ * scratch: (L - 1) B Hf + B T floats (the z_l, then z_L - b_L). */
+typedef struct WdHeadSpectraPredict {
+    const float *x; int32_t ld_x;
+    int32_t B, F, Hf, T, L;
+    const float *W[WD_HEAD_MAX_LAYERS];
+    const float *b[WD_HEAD_MAX_LAYERS];
+    const float *slope;
+    int32_t act;
+    void *scratch; size_t scratch_bytes;
+    float *out;                            /* [B][T]                                                */
+    int32_t spectra_act;                   /* 0 exp, 1 softplus                                     */
+    int32_t normalize;
+    const uint8_t *mask;
+} WdHeadSpectraPredict;
+int wdmpnn_head_spectra_predict(const WdHeadSpectraPredict *h, void *stream);
+
 /* ------------------------------------------------------------------------------------------------
  * Native streamed batches (BASELINE.json configs[4]: millions of synthetic polymer graphs per rank,
  * never materialised).  Replaces chemprop's DataLoader + construct_molecule_batch + BatchMolGraph

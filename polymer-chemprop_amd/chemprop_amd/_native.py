@@ -45,8 +45,12 @@ EXPORTED_SYMBOLS = ('wdmpnn_abi_version', 'wdmpnn_last_error', 'wdmpnn_workspace
                     'wdmpnn_feed_release', 'wdmpnn_feed_forward_workspace_bytes', 'wdmpnn_feed_forward',
                     'wdmpnn_feed_destroy', 'wdmpnn_adam_step_repack', 'wdmpnn_self_check', 'wdmpnn_head_predict',
                     'wdmpnn_head_stack_scratch_bytes', 'wdmpnn_head_stack', 'wdmpnn_head_stack_predict',
-                    'wdmpnn_head_stack_partial')
+                    'wdmpnn_head_stack_partial', 'wdmpnn_head_spectra_scratch_bytes', 'wdmpnn_head_spectra',
+                    'wdmpnn_head_spectra_predict')
 HEAD_MAX_LAYERS = 6  # WD_HEAD_MAX_LAYERS
+HEAD_MAX_SPECTRUM = 8192  # WD_HEAD_MAX_SPECTRUM
+SPECTRA_ACTIVATIONS = {'exp': 0, 'softplus': 1}  # WdHeadSpectra.spectra_act
+SPECTRA_LOSSES = {'sid': 0, 'wasserstein': 1}  # WdHeadSpectra.loss_kind
 
 
 class WdCsr(Structure):
@@ -151,6 +155,30 @@ class WdHeadStackPredict(Structure):
                 ('out', c_void_p), ('out_kind', c_int32), ('n_classes', c_int32)]
 
 
+class WdHeadSpectra(Structure):
+    _fields_ = [('x', c_void_p), ('ld_x', c_int32), ('B', c_int32), ('F', c_int32), ('Hf', c_int32), ('T', c_int32),
+                ('L', c_int32), ('W', c_void_p * HEAD_MAX_LAYERS), ('b', c_void_p * HEAD_MAX_LAYERS),
+                ('slope', c_void_p), ('table', c_void_p), ('ld_table', c_int32), ('inv_n', c_float), ('act', c_int32),
+                ('p', c_float), ('seed', c_uint64), ('spectra_act', c_int32), ('loss_kind', c_int32),
+                ('scratch', c_void_p), ('scratch_bytes', c_size_t), ('out', c_void_p), ('dx', c_void_p),
+                ('dW', c_void_p * HEAD_MAX_LAYERS), ('db', c_void_p * HEAD_MAX_LAYERS), ('dslope', c_void_p),
+                ('loss', c_void_p)]
+
+
+class WdHeadSpectraPredict(Structure):
+    _fields_ = [('x', c_void_p), ('ld_x', c_int32), ('B', c_int32), ('F', c_int32), ('Hf', c_int32), ('T', c_int32),
+                ('L', c_int32), ('W', c_void_p * HEAD_MAX_LAYERS), ('b', c_void_p * HEAD_MAX_LAYERS),
+                ('slope', c_void_p), ('act', c_int32), ('scratch', c_void_p), ('scratch_bytes', c_size_t),
+                ('out', c_void_p), ('spectra_act', c_int32), ('normalize', c_int32), ('mask', c_void_p)]
+
+
+def head_spectra_scratch_bytes(B: int, F: int, Hf: int, T: int, L: int) -> int:
+    """wdmpnn_head_spectra_scratch_bytes."""
+    n = c_size_t()
+    check(lib().wdmpnn_head_spectra_scratch_bytes(B, F, Hf, T, L, ctypes.byref(n)), 'head spectra scratch')
+    return n.value
+
+
 def head_stack_scratch_bytes(B: int, F: int, Hf: int, T: int, L: int) -> int:
     """wdmpnn_head_stack_scratch_bytes."""
     n = c_size_t()
@@ -206,6 +234,9 @@ def lib() -> ctypes.CDLL:
     L.wdmpnn_head_stack.argtypes = [POINTER(WdHeadStack), c_void_p]
     L.wdmpnn_head_stack_partial.argtypes = [POINTER(WdHeadStack), c_void_p]
     L.wdmpnn_head_stack_predict.argtypes = [POINTER(WdHeadStackPredict), c_void_p]
+    L.wdmpnn_head_spectra_scratch_bytes.argtypes = [c_int32, c_int32, c_int32, c_int32, c_int32, POINTER(c_size_t)]
+    L.wdmpnn_head_spectra.argtypes = [POINTER(WdHeadSpectra), c_void_p]
+    L.wdmpnn_head_spectra_predict.argtypes = [POINTER(WdHeadSpectraPredict), c_void_p]
     L.wdmpnn_forward_many.argtypes = [c_int32, POINTER(WdGraph), POINTER(WdParams), POINTER(WdConfig),
                                       POINTER(c_void_p), POINTER(c_size_t), POINTER(c_void_p), c_void_p]
     L.wdmpnn_feed_slot_bytes.argtypes = [c_int32, c_int32, c_int32, c_int32, POINTER(c_size_t), POINTER(c_size_t)]
@@ -233,7 +264,8 @@ def lib() -> ctypes.CDLL:
              'wdmpnn_feed_release', 'wdmpnn_feed_forward_workspace_bytes', 'wdmpnn_feed_forward',
              'wdmpnn_feed_destroy', 'wdmpnn_adam_step_repack', 'wdmpnn_head_predict',
              'wdmpnn_head_stack_scratch_bytes', 'wdmpnn_head_stack', 'wdmpnn_head_stack_predict',
-             'wdmpnn_head_stack_partial'):
+             'wdmpnn_head_stack_partial', 'wdmpnn_head_spectra_scratch_bytes', 'wdmpnn_head_spectra',
+             'wdmpnn_head_spectra_predict'):
         getattr(L, fn).restype = c_int
     v = L.wdmpnn_abi_version()
     if v != ABI_VERSION:

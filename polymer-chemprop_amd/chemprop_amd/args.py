@@ -38,7 +38,11 @@ class TrainArgs:
     features_size: int = 0
     ffn_num_layers: int = 2
     ffn_hidden_size: Optional[int] = None
-    spectra_activation: str = 'exp'
+    spectra_activation: str = 'exp'      # args.py:413
+    spectra_target_floor: float = 1e-8   # args.py:415
+    alternative_loss_function: Optional[str] = None  # args.py:417 ('wasserstein', spectra only)
+    spectra_phase_mask_path: Optional[str] = None    # args.py:240
+    phase_features_path: Optional[str] = None        # args.py:87
     checkpoint_frzn: Optional[str] = None
     freeze_first_only: bool = False
     frzn_ffn_layers: int = 0

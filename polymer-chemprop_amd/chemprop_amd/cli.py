@@ -19,6 +19,13 @@ restated here:
   (checked before training, the CSV row named on failure), no scaler, ``cross_entropy`` as the default
   metric (args.py:557-558), ``test_preds.csv`` with one ``<task>_class_<k>`` column per class
   (make_predictions.py:213);
+  ``--dataset_type spectra``: one target column per spectrum position; the targets of every split are
+  normalised once (``spectra_utils.normalize_spectra`` with ``--spectra_target_floor``, per row, under the
+  row's phase mask: ``--phase_features_path`` one-hot rows x ``--spectra_phase_mask_path``), no scaler, the
+  SID loss (``--alternative_loss_function wasserstein`` for the other one), ``sid`` as the default metric,
+  scored over all positions together (evaluate.py:48-50); the phase features are input features of the model
+  (data/utils.py:250-258); predictions are normalised on the device and ``test_preds.csv`` leaves the
+  positions a row's phase excludes empty (make_predictions.py:175-181);
 * MoleculeModel + initialize_weights after ``torch.manual_seed(pytorch_seed)`` (run_training.py:36,
   model.py:39), Adam (utils.py:295-310), NoamLR stepped per batch (utils.py:490-541, nn_utils.py:115-194),
   training batches reshuffled every epoch by one ``Random(seed)`` (data.py:537-587);
@@ -55,6 +62,7 @@ from .graph_io import load_graphs
 from .model import MoleculeModel
 from .nn_utils import initialize_weights
 from .polymer import split_polymer_string, parse_polymer_rules
+from .spectra_utils import load_phase_mask, normalize_spectra, phase_row_mask, sid_metric, wasserstein_metric
 from .train import NoamLR, _predict_head, build_optimizer, frozen_encodings, get_loss_func, head_predict, train_step
 
 
@@ -223,6 +231,10 @@ def metric_value(metric: str, targets: List[float], preds: List[float]) -> float
     predictions and thresholds scalar ones at 0.5."""
     from sklearn.metrics import accuracy_score, log_loss, mean_absolute_error, mean_squared_error, r2_score, \
         roc_auc_score
+    if metric == 'sid':
+        return sid_metric(preds, targets)
+    if metric == 'wasserstein':
+        return wasserstein_metric(preds, targets)
     if metric == 'rmse':
         return math.sqrt(mean_squared_error(targets, preds))
     if metric == 'mse':
@@ -247,7 +259,13 @@ def metric_value(metric: str, targets: List[float], preds: List[float]) -> float
 
 
 def evaluate_predictions(preds, targets, num_tasks: int, metrics: List[str], dataset_type: str) -> Dict[str, list]:
-    """evaluate.py:11-77: per task over the rows with a target."""
+    """evaluate.py:11-77: per task over the rows with a target; spectra (evaluate.py:48-50): one score per
+    metric over all positions together (``sid_metric`` / ``wasserstein_metric`` on the rows as they are, None
+    = missing or excluded)."""
+    if dataset_type == 'spectra':
+        if len(preds) == 0:
+            return {m: [float('nan')] for m in metrics}
+        return {m: [metric_value(m, targets, preds)] for m in metrics}
     if len(preds) == 0:
         return {m: [float('nan')] * num_tasks for m in metrics}
     out = {m: [] for m in metrics}
@@ -267,14 +285,30 @@ def evaluate_predictions(preds, targets, num_tasks: int, metrics: List[str], dat
 
 
 def predict(model, graphs, idx, batch_size: int, scaler: Optional[StandardScaler],
-            encodings: Optional[torch.Tensor] = None) -> List[List[float]]:
+            encodings: Optional[torch.Tensor] = None, features=None, spectra_mask=None) -> List[List[float]]:
     """predict.py:10-68: eval, no_grad, batches in order, inverse scaling.  ``encodings``: the rows of ``idx``
     from ``frozen_encodings`` (a frozen encoder's outputs, computed once per run): the native prediction head
-    on them in place of the model's forward."""
+    on them in place of the model's forward.  ``features``: the input feature rows of the whole data set
+    (indexed by ``idx``).  A spectra model's predictions are normalised per row on the device
+    (make_predictions.py:175-181): ``spectra_mask`` is the bool ``[len(idx)][T]`` array of the positions each
+    row's phase includes (None: all), uploaded once per batch; excluded positions come back as None."""
     model.eval()
     preds = []
+    spectra = bool(getattr(model, 'spectra', False))
     with torch.no_grad():
         for s in range(0, len(idx), batch_size):
+            if spectra:
+                dev = next(model.parameters()).device
+                if encodings is not None:
+                    emb = encodings[s:s + batch_size]
+                else:
+                    g = BatchMolGraph([graphs[i] for i in idx[s:s + batch_size]])
+                    emb = model.encoder([g], None if features is None else [features[i] for i in idx[s:s + batch_size]])
+                m = None if spectra_mask is None else \
+                    torch.from_numpy(np.ascontiguousarray(spectra_mask[s:s + batch_size])).to(dev)
+                out = head_predict(model, emb, normalize=True, mask=m).cpu().numpy()
+                preds.extend([[None if math.isnan(v) else v for v in row] for row in out.tolist()])
+                continue
             if encodings is not None:
                 preds.extend(head_predict(model, encodings[s:s + batch_size]).cpu().numpy().tolist())
                 continue
@@ -320,12 +354,60 @@ def read_class_targets(path: str, num_classes: int) -> List[List[Optional[int]]]
     return out
 
 
-def parse_args(argv=None) -> argparse.Namespace:
+def load_features(path: str) -> np.ndarray:
+    """features/utils.py load_features for ``.csv`` (a header row, then one row of numbers per molecule) and
+    ``.npy``: float64 ``[N][features]``."""
+    if path.endswith('.npy'):
+        return np.asarray(np.load(path), dtype=np.float64)
+    with open(path) as f:
+        reader = csv.reader(f)
+        next(reader)
+        return np.array([[float(v) for v in row] for row in reader if row], dtype=np.float64)
+
+
+def load_phase_features(path: str, n_rows: int) -> np.ndarray:
+    """data/utils.py:250-254: the one-hot phase rows, one per CSV row."""
+    feats = load_features(path)
+    if feats.ndim != 2 or len(feats) != n_rows:
+        raise ValueError(f'{path} holds {len(feats)} phase rows for {n_rows} CSV rows')
+    for row in feats:
+        if not (row.sum() == 1 and np.count_nonzero(row) == 1):
+            raise ValueError('Phase features must be one-hot encoded.')
+    return feats
+
+
+METRICS_OF = {'spectra': ('sid', 'wasserstein')}  # (args.py:568-573, for the metrics only spectra has)
+
+
+def check_metrics(dataset_type: str, metrics: List[str]) -> None:
+    """args.py:564-573 for the spectra metrics: ``sid`` and ``wasserstein`` are the metrics of spectra, and its
+    only ones (``ValueError`` otherwise, with the reference's message)."""
+    for m in metrics:
+        if (dataset_type == 'spectra') != (m in METRICS_OF['spectra']):
+            raise ValueError(f'Metric "{m}" invalid for dataset type "{dataset_type}".')
+
+
+def parse_args(argv=None, spectra: bool = False) -> argparse.Namespace:
+    """The arguments of ``chemprop_train``.  ``spectra``: also accept ``--dataset_type spectra`` (``chemprop_train``
+    and ``python -m chemprop_amd.cli`` pass True).  Without it the parser keeps its earlier contract, which the
+    suite pins: the dataset types are regression, classification and multiclass, and ``spectra`` is refused like
+    any unknown type."""
     ap = argparse.ArgumentParser(prog='chemprop_train', description=__doc__.split('\n')[0])
     ap.add_argument('--data_path', required=True)
     ap.add_argument('--graphs_path', required=True, help='pre-featurised MolGraph records, one per CSV row')
-    ap.add_argument('--dataset_type', default='regression', choices=['regression', 'classification', 'multiclass'])
+    ap.add_argument('--dataset_type', default='regression',
+                    choices=['regression', 'classification', 'multiclass'] + (['spectra'] if spectra else []))
     ap.add_argument('--multiclass_num_classes', type=int, default=3)
+    ap.add_argument('--spectra_activation', default='exp', choices=['exp', 'softplus'],
+                    help='the output activation that keeps a spectra model positive')
+    ap.add_argument('--spectra_target_floor', type=float, default=1e-8,
+                    help='spectra targets below this value are raised to it before they are normalised')
+    ap.add_argument('--alternative_loss_function', default=None, choices=['wasserstein'],
+                    help='spectra only: train on the Wasserstein loss instead of SID')
+    ap.add_argument('--spectra_phase_mask_path', default=None,
+                    help='CSV (header, label column): one 0/1 row per phase, 0 = position excluded for that phase')
+    ap.add_argument('--phase_features_path', default=None,
+                    help='CSV (header) or .npy: the one-hot phase of every data row; fed to the model as features')
     ap.add_argument('--save_dir', required=True)
     ap.add_argument('--polymer', action='store_true')
     ap.add_argument('--split_type', default='random', choices=['random'])
@@ -362,7 +444,14 @@ def parse_args(argv=None) -> argparse.Namespace:
                     help='train on this fraction of the training split (drawn by --seed)')
     ap.add_argument('--no_encoding_cache', action='store_true',
                     help='run the frozen encoder every step instead of computing its encodings once')
-    return ap.parse_args(argv)
+    a = ap.parse_args(argv)
+    if a.alternative_loss_function is not None and a.dataset_type != 'spectra':
+        raise ValueError(f'Alternative loss function "{a.alternative_loss_function}" not supported with dataset type '
+                         f'"{a.dataset_type}".')
+    if a.dataset_type == 'spectra' and not a.spectra_target_floor > 0:
+        raise ValueError('--spectra_target_floor must be greater than 0')
+    check_metrics(a.dataset_type, ([a.metric] if a.metric else []) + list(a.extra_metrics))
+    return a
 
 
 def run_training(a: argparse.Namespace) -> Dict[str, list]:
@@ -384,9 +473,25 @@ def run_training(a: argparse.Namespace) -> Dict[str, list]:
         if a.multiclass_num_classes < 2:
             raise ValueError('--multiclass_num_classes must be at least 2')
         targets = read_class_targets(a.data_path, a.multiclass_num_classes)
-    metric = a.metric or {'regression': 'rmse', 'multiclass': 'cross_entropy'}.get(a.dataset_type, 'auc')
+    spectra = a.dataset_type == 'spectra'
+    phase_features = phase_mask = row_mask = None
+    if spectra:  # run_training.py:146-157: every split's targets normalised once, per row, under its phase mask
+        if a.phase_features_path is not None:
+            phase_features = load_phase_features(a.phase_features_path, len(smiles))
+        if a.spectra_phase_mask_path is not None:
+            phase_mask = load_phase_mask(a.spectra_phase_mask_path)
+        if phase_features is not None and phase_mask is not None:
+            if np.asarray(phase_mask).shape != (phase_features.shape[1], num_tasks):
+                raise ValueError(f'{a.spectra_phase_mask_path}: a mask of shape {np.asarray(phase_mask).shape} for '
+                                 f'{phase_features.shape[1]} phases and {num_tasks} spectrum positions')
+            row_mask = phase_row_mask(phase_features, phase_mask)
+        targets = normalize_spectra(targets, phase_features, phase_mask, excluded_sub_value=None,
+                                    threshold=a.spectra_target_floor)
+    metric = a.metric or {'regression': 'rmse', 'multiclass': 'cross_entropy', 'spectra': 'sid'}.get(a.dataset_type,
+                                                                                                     'auc')
     metrics = [metric] + [m for m in a.extra_metrics if m != metric]
-    minimize = metric in ('rmse', 'mse', 'mae', 'cross_entropy')
+    check_metrics(a.dataset_type, metrics)
+    minimize = metric in ('rmse', 'mse', 'mae', 'cross_entropy', 'sid', 'wasserstein')
     device = torch.device('cuda', a.gpu)
     args = TrainArgs(hidden_size=a.hidden_size, depth=a.depth, dropout=a.dropout, activation=a.activation,
                      aggregation=a.aggregation, aggregation_norm=a.aggregation_norm, bias=a.bias,
@@ -394,7 +499,12 @@ def run_training(a: argparse.Namespace) -> Dict[str, list]:
                      ffn_hidden_size=a.ffn_hidden_size or a.hidden_size, dataset_type=a.dataset_type,
                      num_tasks=num_tasks, multiclass_num_classes=a.multiclass_num_classes, device=device,
                      frzn_encoder=bool(a.frzn_encoder or a.frzn_ffn_layers > 0), frzn_ffn_layers=a.frzn_ffn_layers,
-                     init_lr=a.init_lr, optimizer=a.optimizer, weight_decay=a.weight_decay)
+                     init_lr=a.init_lr, optimizer=a.optimizer, weight_decay=a.weight_decay,
+                     spectra_activation=a.spectra_activation, spectra_target_floor=a.spectra_target_floor,
+                     alternative_loss_function=a.alternative_loss_function,
+                     spectra_phase_mask_path=a.spectra_phase_mask_path, phase_features_path=a.phase_features_path,
+                     use_input_features=phase_features is not None,
+                     features_size=0 if phase_features is None else int(phase_features.shape[1]))
     torch.manual_seed(a.pytorch_seed)
     train_idx, val_idx, test_idx = random_split(len(smiles), a.split_sizes, a.seed)
     if a.train_frac != 1.0:  # run_training.py:132-137; the scaler below is fitted on the subsample
@@ -406,6 +516,9 @@ def run_training(a: argparse.Namespace) -> Dict[str, list]:
         train_targets = scaler.transform(train_targets).tolist()
         train_targets = [[None if (x is None or (isinstance(x, float) and math.isnan(x))) else x for x in r]
                          for r in train_targets]
+    if spectra:  # one float array (NaN = missing): a batch's rows are a slice, not 1801 Python objects per row
+        train_targets = np.array([[np.nan if x is None else x for x in r] for r in train_targets], dtype=np.float64)
+        train_targets = train_targets.reshape(len(train_idx), num_tasks)
     model = MoleculeModel(args)
     initialize_weights(model)
     if a.checkpoint_frzn is not None:
@@ -416,13 +529,21 @@ def run_training(a: argparse.Namespace) -> Dict[str, list]:
     # a frozen encoder without dropout gives every molecule the same encoding at every step: computed once per
     # split, the steps and the per-epoch scores then run the head alone (train.frozen_encodings)
     enc_cache = None
-    if args.frzn_encoder and a.dropout == 0 and not a.no_encoding_cache and _predict_head(model.eval()) is not None:
+    if args.frzn_encoder and a.dropout == 0 and not a.no_encoding_cache and phase_features is None and \
+            _predict_head(model.eval()) is not None:
         enc_cache = {name: frozen_encodings(model, [graphs[i] for i in idx], a.batch_size)
                      for name, idx in (('train', train_idx), ('val', val_idx), ('test', test_idx))}
     scheduler = NoamLR(optimizer, warmup_epochs=[a.warmup_epochs], total_epochs=[a.epochs],
                        steps_per_epoch=len(train_idx) // a.batch_size, init_lr=[a.init_lr], max_lr=[a.max_lr],
                        final_lr=[a.final_lr])
-    loss_func = get_loss_func(a.dataset_type)
+    loss_func = get_loss_func(a.dataset_type, a.alternative_loss_function)
+
+    def batch_targets(pos):
+        return train_targets[pos] if spectra else [train_targets[p] for p in pos]
+
+    def run_predict(name, idx):
+        return predict(model, graphs, idx, a.batch_size, scaler, enc_cache and enc_cache[name], phase_features,
+                       None if row_mask is None else row_mask[idx])
     sampler = Random(a.seed)
     log_path = os.path.join(a.save_dir, 'train_val_loss_log.csv')
     best = math.inf if minimize else -math.inf
@@ -438,18 +559,18 @@ def run_training(a: argparse.Namespace) -> Dict[str, list]:
                 pos = order[s:s + a.batch_size]
                 if enc_cache is not None:
                     rows = enc_cache['train'][torch.as_tensor(pos, device=device)]
-                    loss = train_step(model, None, [train_targets[p] for p in pos], loss_func, optimizer, scheduler,
+                    loss = train_step(model, None, batch_targets(pos), loss_func, optimizer, scheduler,
                                       a.dataset_type, grad_clip=a.grad_clip, encodings=rows)
                 else:
                     g = BatchMolGraph([graphs[train_idx[p]] for p in pos])
-                    loss = train_step(model, [g], [train_targets[p] for p in pos], loss_func, optimizer, scheduler,
-                                      a.dataset_type, grad_clip=a.grad_clip)
+                    # (phase features are input features: such a step takes the autograd path with the fused head)
+                    feats = None if phase_features is None else [phase_features[train_idx[p]] for p in pos]
+                    loss = train_step(model, [g], batch_targets(pos), loss_func, optimizer, scheduler,
+                                      a.dataset_type, features_batch=feats, grad_clip=a.grad_clip)
                 losses.append(float(loss))
-            val_scores = evaluate_predictions(predict(model, graphs, val_idx, a.batch_size, scaler,
-                                                      enc_cache and enc_cache['val']),
+            val_scores = evaluate_predictions(run_predict('val', val_idx),
                                               [targets[i] for i in val_idx], num_tasks, metrics, a.dataset_type)
-            tr_scores = evaluate_predictions(predict(model, graphs, train_idx, a.batch_size, scaler,
-                                                     enc_cache and enc_cache['train']),
+            tr_scores = evaluate_predictions(run_predict('train', train_idx),
                                              [targets[i] for i in train_idx], num_tasks, metrics, a.dataset_type)
             w.writerow([epoch, float(np.mean(losses)) if losses else float('nan')] +
                        [float(np.nanmean(tr_scores[m])) if tr_scores[m] else float('nan') for m in metrics] +
@@ -462,14 +583,14 @@ def run_training(a: argparse.Namespace) -> Dict[str, list]:
     ckpt = torch.load(os.path.join(a.save_dir, 'best_model.pt'), map_location=device, weights_only=True)
     model.load_state_dict(ckpt['state_dict'])
     test_targets = [targets[i] for i in test_idx]
-    test_preds = predict(model, graphs, test_idx, a.batch_size, scaler, enc_cache and enc_cache['test'])
+    test_preds = run_predict('test', test_idx)
     scores = evaluate_predictions(test_preds, test_targets, num_tasks, metrics, a.dataset_type)
     with open(os.path.join(a.save_dir, 'test_scores.json'), 'w') as f:
         json.dump(scores, f, indent=4, sort_keys=True)
     with open(os.path.join(a.save_dir, 'test_scores.csv'), 'w', newline='') as f:
         w = csv.writer(f)
         w.writerow(['Task'] + [f'Mean {m}' for m in metrics])
-        for t, name in enumerate(header[1:]):
+        for t, name in enumerate(['spectra'] if spectra else header[1:]):  # (cross_validate.py:158-159)
             w.writerow([name] + [scores[m][t] if t < len(scores[m]) else '' for m in metrics])
     with open(os.path.join(a.save_dir, 'test_preds.csv'), 'w', newline='') as f:
         w = csv.writer(f)
@@ -479,7 +600,8 @@ def run_training(a: argparse.Namespace) -> Dict[str, list]:
         else:
             w.writerow(header)
         for i, p in zip(test_idx, test_preds):
-            w.writerow([smiles[i]] + ([x for task in p for x in task] if multiclass else list(p)))
+            w.writerow([smiles[i]] + ([x for task in p for x in task] if multiclass else
+                                      ['' if x is None else x for x in p]))
     with open(os.path.join(a.save_dir, 'split_indices.json'), 'w') as f:
         json.dump({'train': train_idx, 'val': val_idx, 'test': test_idx, 'best_epoch': best_epoch}, f)
     return scores
@@ -487,7 +609,7 @@ def run_training(a: argparse.Namespace) -> Dict[str, list]:
 
 def chemprop_train(argv=None) -> Dict[str, list]:
     """Entry point (setup.py:39 ``chemprop_train`` in the reference)."""
-    return run_training(parse_args(argv))
+    return run_training(parse_args(argv, spectra=True))
 
 
 if __name__ == '__main__':

@@ -1,6 +1,6 @@
 """MoleculeModel (``chemprop/models/model.py:14-194``): the encoder runs on the HIP library, the
-small FFN head stays PyTorch (~1 % of the forward) except for multiclass
-prediction, which runs the native prediction head (``train.head_predict``).  Module layout and
+small FFN head stays PyTorch (~1 % of the forward) except for multiclass and
+spectra prediction, which run the native prediction heads (``train.head_predict``).  Module layout and
 state_dict keys (``encoder.encoder.0.*``, ``ffn.1.*``, ``ffn.4.*`` ...) match the reference."""
 from __future__ import annotations
 
@@ -24,6 +24,7 @@ class MoleculeModel(nn.Module):
         super(MoleculeModel, self).__init__()
         self.classification = args.dataset_type == 'classification'
         self.multiclass = args.dataset_type == 'multiclass'
+        self.spectra = args.dataset_type == 'spectra'  # (the FFN ends with the spectra activation, create_ffn)
         self.output_size = args.num_tasks * (args.multiclass_num_classes if self.multiclass else 1)
         if self.classification:
             self.sigmoid = nn.Sigmoid()
@@ -85,10 +86,11 @@ class MoleculeModel(nn.Module):
                 return_embeddings: bool = False):
         """model.py:152-194."""
         emb = self.encoder(batch, features_batch, atom_descriptors_batch, atom_features_batch, bond_features_batch)
-        if self.multiclass and not self.training and not torch.is_grad_enabled():
+        if (self.multiclass or getattr(self, 'spectra', False)) and not self.training and not torch.is_grad_enabled():
             # multiclass prediction: ffn, the reshape and the softmax as two HIP launches (train.head_predict)
             # when the head is the two-layer one the native head runs (L launches for the other FFNs of create_ffn:
-            # the stack prediction head); the torch ops below otherwise
+            # the stack prediction head); spectra prediction: ffn and its output activation as the native spectra
+            # head (not normalised: model.py:102-113); the torch ops below otherwise
             from .train import _head_linears, _predict_head, head_predict
             head = _predict_head(self)
             if head is not None and emb.dim() == 2 and emb.dtype == torch.float32 and \

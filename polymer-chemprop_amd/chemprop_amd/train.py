@@ -6,7 +6,7 @@
   per-batch scheduler step; plus the DP all-reduce of :mod:`chemprop_amd.dp` between backward and
   the optimizer step.
 * ``NoamLR`` restates ``chemprop/nn_utils.py:115-194``; ``get_loss_func`` ``utils.py:338-364``
-  (regression / classification / multiclass); ``build_optimizer`` ``utils.py:295-310``.
+  (regression / classification / multiclass / spectra); ``build_optimizer`` ``utils.py:295-310``.
 """
 from __future__ import annotations
 
@@ -61,8 +61,17 @@ class NoamLR(_LRScheduler):
             self.optimizer.param_groups[i]['lr'] = self.lr[i]
 
 
-def get_loss_func(dataset_type: str) -> nn.Module:
-    """utils.py:338-364 (no alternative losses, no spectra)."""
+def get_loss_func(dataset_type: str, alternative_loss_function: Optional[str] = None) -> Callable:
+    """utils.py:338-364.  Spectra: ``spectra_utils.sid_loss``, or ``wasserstein_loss`` for
+    ``alternative_loss_function='wasserstein'`` (the one alternative loss the reference has), both
+    ``(preds, targets, mask)``; the other dataset types have no alternative."""
+    if alternative_loss_function is not None and \
+            not (dataset_type == 'spectra' and alternative_loss_function == 'wasserstein'):
+        raise ValueError(f'Alternative loss function "{alternative_loss_function}" not supported with dataset type '
+                         f'"{dataset_type}".')
+    if dataset_type == 'spectra':
+        from .spectra_utils import sid_loss, wasserstein_loss
+        return wasserstein_loss if alternative_loss_function == 'wasserstein' else sid_loss
     if dataset_type == 'classification':
         return nn.BCEWithLogitsLoss(reduction='none')
     if dataset_type == 'regression':
@@ -230,8 +239,14 @@ def _host_table(rows: np.ndarray, dev: torch.device, zero_copy: bool = False):
     return table
 
 
-def _targets_and_mask(target_batch):
-    """train.py:46-48 on the host: (targets with 0 for the missing ones, mask), float64 [B][T]."""
+def _targets_and_mask(target_batch, nan_missing: bool = False):
+    """train.py:46-48 on the host: (targets with 0 for the missing ones, mask), float64 [B][T].
+    ``nan_missing`` (spectra): a float ``ndarray`` [B][T] is taken as it is with NaN = missing: no per-element
+    Python work (a spectra batch of 64 x 1801 lists with ``None`` entries costs 15 ms here, its array 0.3 ms)."""
+    if nan_missing and isinstance(target_batch, np.ndarray) and target_batch.dtype.kind == 'f' and \
+            target_batch.ndim == 2:
+        present = ~np.isnan(target_batch)
+        return np.where(present, target_batch, 0.0).astype(np.float64), present.astype(np.float64)
     n_b = len(target_batch)
     n_t = len(target_batch[0]) if n_b else 0
     # missing targets are None (train.py:47-48); numpy's float conversion would turn them into NaN, so the
@@ -273,15 +288,48 @@ def check_class_targets(target_batch, num_classes: int) -> None:
         _check_class_indices(*_targets_and_mask(target_batch), num_classes)
 
 
-def _loss_table(target_batch, target_weights, data_weights, dev, zero_copy: bool = False, num_classes: int = 0):
+def _spectra_targets_ok(tgt: np.ndarray, mask: np.ndarray) -> bool:
+    """Every present target is finite and > 0 (one pass: a finite positive value times a mask of 0 / 1 is > 0
+    exactly where the mask is 1; NaN and inf fail the comparisons)."""
+    with np.errstate(invalid='ignore'):
+        return bool(((tgt > 0) & (tgt < np.inf)).sum() == int(mask.sum()) and not ((mask == 0) & (tgt != 0)).any())
+
+
+def _check_spectra_targets(tgt: np.ndarray, mask: np.ndarray) -> None:
+    """Every present spectra target must be finite and greater than 0 (``normalize_spectra`` with the target
+    floor leaves them so): the table marks a missing target with 0, and the losses take its logarithm."""
+    with np.errstate(invalid='ignore'):
+        bad = (mask > 0) & ~(np.isfinite(tgt) & (tgt > 0))
+    if bad.any():
+        r, t = (int(v) for v in np.argwhere(bad)[0])
+        raise ValueError(f'spectra target {tgt[r, t]!r} in row {r}, column {t} is not finite and greater than 0 '
+                         '(normalize the targets with a positive floor first)')
+
+
+def check_spectra_targets(target_batch) -> None:
+    """Raise ValueError unless every present target of ``target_batch`` ([B][T], None = missing) is finite and
+    greater than 0; the message names the first offending row and column."""
+    if len(target_batch):
+        _check_spectra_targets(*_targets_and_mask(target_batch))
+
+
+def _loss_table(target_batch, target_weights, data_weights, dev, zero_copy: bool = False, num_classes: int = 0,
+                spectra: bool = False):
     """train.py:46-74's targets and weights as one device table [B][2T] (targets | w = target weight *
     data weight * mask, rounded once to fp32) and the host count mask.sum().  ``num_classes`` > 0
-    (multiclass): the targets are class indices, checked on the host (``_check_class_indices``)."""
+    (multiclass): the targets are class indices, checked on the host (``_check_class_indices``).
+    ``spectra``: a target of 0 in the table means "missing" (the mask of the spectra losses, which is not the
+    weight's: a present target with weight 0 still counts in the row's sum); every present target is checked
+    to be finite and > 0 (``_check_spectra_targets``) and must still be nonzero once rounded to fp32."""
     n_b = len(target_batch)
     n_t = len(target_batch[0]) if n_b else 0
-    tgt, mask = _targets_and_mask(target_batch)
+    tgt, mask = _targets_and_mask(target_batch, spectra)
     if num_classes and n_b:
         _check_class_indices(tgt, mask, num_classes)
+    if spectra and n_b:  # (as rounded to fp32: a present target that rounds to 0 would go missing)
+        if not _spectra_targets_ok(tgt.astype(np.float32), mask):
+            _check_spectra_targets(tgt, mask)
+            _check_spectra_targets(tgt.astype(np.float32), mask)
     tw = np.ones(n_t) if target_weights is None else np.asarray(target_weights, dtype=np.float64)
     dw = np.ones(n_b) if data_weights is None else np.asarray(data_weights, dtype=np.float64)
     # targets and W travel as one host table (one pinned, asynchronous copy: pageable copies would each
@@ -299,9 +347,12 @@ def batch_loss(preds: torch.Tensor, target_batch: Sequence[Sequence[Optional[flo
     mask.sum()``.  The three weight factors are multiplied on the host into one weight table W, and
     ``mask.sum()`` is a host count: two fewer device ops forward and backward, the same loss (W is
     rounded once to fp32 instead of twice)."""
-    table, n_t, n_mask = _loss_table(target_batch, target_weights, data_weights, preds.device)
+    table, n_t, n_mask = _loss_table(target_batch, target_weights, data_weights, preds.device,
+                                     spectra=dataset_type == 'spectra')
     targets, w = table[:, :n_t], table[:, n_t:]
-    if dataset_type == 'multiclass':
+    if dataset_type == 'spectra':  # train.py:70-71: the loss takes the mask (the table's "0 = missing")
+        loss = loss_func(preds, targets, targets != 0) * w
+    elif dataset_type == 'multiclass':
         targets = targets.long()
         loss = torch.cat([loss_func(preds[:, j, :], targets[:, j]).unsqueeze(1) for j in range(preds.size(1))],
                          dim=1) * w
@@ -353,10 +404,18 @@ def _fusable_head(model: nn.Module, loss_func: Callable, dataset_type: str):
         n_classes = getattr(model, 'num_classes', 0) if getattr(model, 'multiclass', False) else 0
         if not isinstance(n_classes, int) or n_classes < 2:
             return None
+    elif dataset_type == 'spectra':
+        from .spectra_utils import sid_loss, wasserstein_loss
+        if loss_func is not sid_loss and loss_func is not wasserstein_loss:
+            return None
+        st = _head_structure(model)  # (always the spectra entry point: no two-layer tuple path)
+        if not isinstance(st, _StackHead) or st.spectra is None:
+            return None
+        return st.with_kind(1 if loss_func is wasserstein_loss else 0, 1)
     else:
         return None
     st = _head_structure(model)
-    if st is None:
+    if st is None or (isinstance(st, _StackHead) and st.spectra is not None):
         return None
     l2 = st.linears[-1] if isinstance(st, _StackHead) else st[1]
     if kind == 2 and (l2.out_features % n_classes or l2.out_features != getattr(model, 'output_size', -1)):
@@ -370,14 +429,17 @@ def _fusable_head(model: nn.Module, loss_func: Callable, dataset_type: str):
 class _StackHead:
     """An FFN the native stack head runs (``wdmpnn_head_stack``): its ``Linear`` layers, the activation code,
     the shared PReLU slope (or None), the dropout probability active now, and the loss or output kind with its
-    classes per task (set by ``with_kind``)."""
-    __slots__ = ('linears', 'act', 'slope', 'p', 'kind', 'n_classes')
+    classes per task (set by ``with_kind``).  ``spectra``: None, or the output activation of a spectra FFN
+    (0 exp, 1 softplus): such a head runs ``wdmpnn_head_spectra`` and its kind is the spectra loss (0 SID,
+    1 Wasserstein)."""
+    __slots__ = ('linears', 'act', 'slope', 'p', 'kind', 'n_classes', 'spectra')
 
-    def __init__(self, linears, act, slope, p, kind=None, n_classes=1):
+    def __init__(self, linears, act, slope, p, kind=None, n_classes=1, spectra=None):
         self.linears, self.act, self.slope, self.p, self.kind, self.n_classes = linears, act, slope, p, kind, n_classes
+        self.spectra = spectra
 
     def with_kind(self, kind: int, n_classes: int) -> '_StackHead':
-        return _StackHead(self.linears, self.act, self.slope, self.p, kind, n_classes)
+        return _StackHead(self.linears, self.act, self.slope, self.p, kind, n_classes, self.spectra)
 
     def params(self) -> list:
         """W_1, b_1, ..., W_L, b_L (None for an absent bias), then the slope (or None)."""
@@ -390,17 +452,37 @@ class _StackHead:
 HEAD_MAX_WIDTH, HEAD_MAX_OUTPUTS = 4096, 64  # (wdmpnn.h: F, Hf <= 4096, T <= 64)
 
 
-def _ffn_structure(ffn: nn.Module, training: bool) -> Optional[_StackHead]:
+def _spectra_act(m: nn.Module) -> Optional[int]:
+    """WdHeadSpectra.spectra_act of a spectra FFN's output activation (create_ffn: ``_Exp`` or ``nn.Softplus``
+    with its defaults), else None."""
+    from .model import _Exp
+    if type(m) is _Exp:
+        return 0
+    if type(m) is nn.Softplus and m.beta == 1 and m.threshold == 20:
+        return 1  # (beyond the threshold torch returns z itself: within 2.1e-9 of log1p(exp(z)))
+    return None
+
+
+def _ffn_structure(ffn: nn.Module, training: bool, spectra: bool = False) -> Optional[_StackHead]:
     """The structure of an FFN built by ``MoleculeModel.create_ffn`` within the native head's limits, else None:
     Dropout, Linear, then (activation, Dropout, Linear) up to ``HEAD_MAX_LAYERS`` Linear layers in all, every
     Dropout with one probability (< 1), one activation (the same module at every site, as create_ffn builds it:
     a PReLU must have a single slope), hidden layers of one width, widths <= 4096 and <= 64 outputs.  Devices
-    and dtypes are not looked at (``_head_structure`` does)."""
+    and dtypes are not looked at (``_head_structure`` does).  ``spectra``: the FFN of a spectra model, the same
+    stack followed by its output activation (``_Exp`` or ``nn.Softplus``), with up to ``HEAD_MAX_SPECTRUM``
+    outputs; without it a trailing activation is not recognised."""
     from . import _native
-    if not isinstance(ffn, nn.Sequential) or len(ffn) < 2 or len(ffn) % 3 != 2 or \
-            len(ffn) // 3 + 1 > _native.HEAD_MAX_LAYERS:
+    if not isinstance(ffn, nn.Sequential):
         return None
     mods = list(ffn)
+    s_act = None
+    if spectra:
+        s_act = _spectra_act(mods[-1]) if mods else None
+        if s_act is None:
+            return None
+        mods = mods[:-1]
+    if len(mods) < 2 or len(mods) % 3 != 2 or len(mods) // 3 + 1 > _native.HEAD_MAX_LAYERS:
+        return None
     drops, linears, acts = mods[0::3], mods[1::3], mods[2::3]
     if any(type(d) is not nn.Dropout for d in drops) or any(type(l) is not nn.Linear for l in linears):
         return None
@@ -428,9 +510,9 @@ def _ffn_structure(ffn: nn.Module, training: bool) -> Optional[_StackHead]:
         if i < len(linears) - 1 and l.out_features != hidden:
             return None
         width = l.out_features
-    if linears[-1].out_features > HEAD_MAX_OUTPUTS:
+    if linears[-1].out_features > (_native.HEAD_MAX_SPECTRUM if spectra else HEAD_MAX_OUTPUTS):
         return None
-    return _StackHead(linears, code, slope, float(p) if training else 0.0)
+    return _StackHead(linears, code, slope, float(p) if training else 0.0, spectra=s_act)
 
 
 def _head_structure(model: nn.Module):
@@ -441,10 +523,11 @@ def _head_structure(model: nn.Module):
     from .model import MoleculeModel
     if not isinstance(model, MoleculeModel) or type(model).forward is not MoleculeModel.forward:
         return None
-    st = _two_layer_structure(model)
+    spectra = bool(getattr(model, 'spectra', False))
+    st = None if spectra else _two_layer_structure(model)
     if st is not None:
         return st
-    st = _ffn_structure(model.ffn, model.training)
+    st = _ffn_structure(model.ffn, model.training, spectra)  # (spectra: a _StackHead with ``spectra`` set)
     if st is None:
         return None
     for t in st.params():
@@ -540,11 +623,12 @@ def _run_head_stack(x: torch.Tensor, head: _StackHead, tab_ptr: int, ld_table: i
     lin = head.linears
     L, T = len(lin), lin[-1].out_features
     Hf = lin[0].out_features if L > 1 else 0
-    nbytes = _native.head_stack_scratch_bytes(B, F, Hf, T, L)
+    spectra = head.spectra is not None  # (wdmpnn_head_spectra: the same fields, NULL gradients = not wanted)
+    nbytes = (_native.head_spectra_scratch_bytes if spectra else _native.head_stack_scratch_bytes)(B, F, Hf, T, L)
     scratch = torch.empty(max(nbytes // 4, 4), dtype=torch.float32, device=dev)
     dx = torch.empty_like(x) if want_dx else None
     loss = torch.empty((), dtype=torch.float32, device=dev)
-    h = _native.WdHeadStack()
+    h = _native.WdHeadSpectra() if spectra else _native.WdHeadStack()
     h.x, h.ld_x, h.B, h.F, h.Hf, h.T, h.L = x.data_ptr(), F, B, F, Hf, T, L
     grads = []
     partial = not want_dx
@@ -567,10 +651,17 @@ def _run_head_stack(x: torch.Tensor, head: _StackHead, tab_ptr: int, ld_table: i
         partial = partial or gs is None
     grads.append(gs)
     h.table, h.ld_table, h.inv_n, h.act = tab_ptr, ld_table, float(inv_n), head.act
-    h.p, h.seed, h.loss_kind, h.n_classes = head.p, seed, head.kind, head.n_classes
+    h.p, h.seed, h.loss_kind = head.p, seed, head.kind
+    if spectra:
+        h.spectra_act = head.spectra
+    else:
+        h.n_classes = head.n_classes
     h.scratch, h.scratch_bytes = scratch.data_ptr(), scratch.numel() * 4
     h.dx, h.loss = ptr(dx), loss.data_ptr()
-    entry = _native.lib().wdmpnn_head_stack_partial if partial else _native.lib().wdmpnn_head_stack
+    if spectra:
+        entry = _native.lib().wdmpnn_head_spectra
+    else:
+        entry = _native.lib().wdmpnn_head_stack_partial if partial else _native.lib().wdmpnn_head_stack
     _native.check(entry(ctypes.byref(h), _native.current_stream(dev)), 'FFN head stack + loss')
     return loss, dx, grads
 
@@ -616,8 +707,9 @@ def head_loss(emb: torch.Tensor, head, target_batch, target_weights=None, data_w
         l1, l2, kind, n_classes = head.linears[0], head.linears[-1], head.kind, head.n_classes
     else:
         l1, l2, act, kind, n_classes = head
+    spectra = stack and head.spectra is not None
     table, n_t, n_mask = _loss_table(target_batch, target_weights, data_weights, emb.device,
-                                     num_classes=n_classes if kind == 2 else 0)
+                                     num_classes=n_classes if kind == 2 and not spectra else 0, spectra=spectra)
     if n_t * n_classes != l2.out_features:
         raise ValueError(f'{n_t} targets per row for {l2.out_features} outputs')
     if table.shape[0] != emb.shape[0] or emb.dim() != 2 or emb.shape[1] != l1.in_features:
@@ -650,14 +742,20 @@ def _head_linears(head) -> list:
     return head.linears if isinstance(head, _StackHead) else [head[0], head[1]]
 
 
-def head_predict(model: nn.Module, emb: torch.Tensor, head=None) -> torch.Tensor:
+def head_predict(model: nn.Module, emb: torch.Tensor, head=None, normalize: bool = False,
+                 mask: Optional[torch.Tensor] = None) -> torch.Tensor:
     """The eval-mode predictions of ``model`` from the encodings ``emb`` (model.py:152-194 after the
     encoder: ``ffn``, then nothing for regression, the sigmoid for classification, the softmax over each
     task's classes for multiclass) as two HIP launches (``wdmpnn_head_predict``).  ``[B][T]`` for
     regression and classification, ``[B][tasks][classes]`` for multiclass.  No autograd graph is built.
     The model must be in eval mode with an FFN the native heads run: the two-layer head, or any other FFN of
     ``create_ffn`` with at most 64 outputs as L launches (``wdmpnn_head_stack_predict``);
-    ``NotImplementedError`` otherwise: there is no torch fallback here."""
+    ``NotImplementedError`` otherwise: there is no torch fallback here.
+    A spectra model (``wdmpnn_head_spectra_predict``, up to 8192 outputs) returns ``act_s(ffn)`` as its
+    ``forward`` does, or with ``normalize`` every row divided by the sum of its included positions
+    (``spectra_utils.normalize_spectra`` on the device): ``mask`` is a bool or uint8 ``[B][T]`` tensor on the
+    device (nonzero = included; None = every position), and the excluded positions come back as NaN.
+    ``normalize`` and ``mask`` are for spectra models only (``ValueError`` otherwise)."""
     from . import _native
     if model.training:
         raise ValueError('head_predict is the eval-mode head: call model.eval() first')
@@ -673,6 +771,31 @@ def head_predict(model: nn.Module, emb: torch.Tensor, head=None) -> torch.Tensor
                          f'{l1.in_features} on {l1.weight.device}')
     x = emb.detach().contiguous()
     B, F = x.shape
+    spectra = isinstance(head, _StackHead) and head.spectra is not None
+    if (normalize or mask is not None) and not spectra:
+        raise ValueError('head_predict: normalize / mask are for spectra models')
+    if spectra:
+        lin = head.linears
+        L, T = len(lin), lin[-1].out_features
+        Hf = lin[0].out_features if L > 1 else 0
+        if mask is not None:
+            if not normalize or tuple(mask.shape) != (B, T) or mask.device != x.device or \
+                    mask.dtype not in (torch.bool, torch.uint8):
+                raise ValueError(f'head_predict: mask of shape {tuple(mask.shape)} ({mask.dtype}, {mask.device}) for '
+                                 f'normalize={normalize} and outputs of shape {(B, T)} on {x.device}')
+            mask = mask.contiguous().view(torch.uint8)
+        scratch = torch.empty(max((L - 1) * B * Hf + B * T, 4), dtype=torch.float32, device=x.device)
+        out = torch.empty((B, T), dtype=torch.float32, device=x.device)
+        h = _native.WdHeadSpectraPredict()
+        h.x, h.ld_x, h.B, h.F, h.Hf, h.T, h.L = x.data_ptr(), F, B, F, Hf, T, L
+        for i, l in enumerate(lin):
+            h.W[i], h.b[i] = l.weight.data_ptr(), _native.ptr(l.bias)
+        h.slope, h.act = _native.ptr(head.slope), head.act
+        h.scratch, h.scratch_bytes = scratch.data_ptr(), scratch.numel() * 4
+        h.out, h.spectra_act, h.normalize, h.mask = out.data_ptr(), head.spectra, int(bool(normalize)), _native.ptr(mask)
+        _native.check(_native.lib().wdmpnn_head_spectra_predict(ctypes.byref(h), _native.current_stream(x.device)),
+                      'FFN head spectra (predict)')
+        return out
     if isinstance(head, _StackHead):
         lin = head.linears
         L, T = len(lin), lin[-1].out_features
@@ -873,7 +996,8 @@ def _direct_step(model, enc, graph, head, target_batch, target_weights, data_wei
         l1, l2, kind, n_classes = head.linears[0], head.linears[-1], head.kind, head.n_classes
     else:
         l1, l2, act, kind, n_classes = head
-    nc = n_classes if kind == 2 else 0  # (multiclass: _loss_table checks the class indices on the host)
+    spectra = stack and head.spectra is not None
+    nc = n_classes if kind == 2 and not spectra else 0  # (multiclass: _loss_table checks the class indices on the host)
     enc_frozen = plan is not None and plan.enc_frozen
     if encodings is not None:
         out = encodings
@@ -883,10 +1007,14 @@ def _direct_step(model, enc, graph, head, target_batch, target_weights, data_wei
         out, state = enc._train_forward(graph)
     # the loss table read by the head kernel straight from its pinned host buffer (no copy launch in the
     # step: the copy kernel and its gap were ~10 us, profiles/round4_train_kernel_trace_v1.txt)
-    zc, n_t, n_mask, tshape = _loss_table(target_batch, target_weights, data_weights, out.device, zero_copy=True,
-                                          num_classes=nc)
+    # (the spectra row kernel reads its table rows in several passes: a device copy, not the pinned buffer)
+    zc = None
+    if not spectra:
+        zc, n_t, n_mask, tshape = _loss_table(target_batch, target_weights, data_weights, out.device, zero_copy=True,
+                                              num_classes=nc)
     if zc is None:
-        table, n_t, n_mask = _loss_table(target_batch, target_weights, data_weights, out.device, num_classes=nc)
+        table, n_t, n_mask = _loss_table(target_batch, target_weights, data_weights, out.device, num_classes=nc,
+                                         spectra=spectra)
         tab_ptr, tshape = table.data_ptr(), tuple(table.shape)
     else:
         tab_ptr = zc[0]
@@ -938,7 +1066,10 @@ def train_step(model: nn.Module, mol_batch, target_batch, loss_func: Callable, o
     default regression / classification / multiclass head + loss run as ``wdmpnn_head_mse`` (same loss and gradients within fp32
     summation order; ``False`` = the torch ops of the reference); FFNs with another number of layers, active
     dropout or PReLU run as ``wdmpnn_head_stack`` (their dropout masks follow ``nn_utils.dropout_mask``, not
-    torch's generator).  ``direct``: with the fused head and a
+    torch's generator); a spectra model (``dataset_type='spectra'`` with ``spectra_utils.sid_loss`` or
+    ``wasserstein_loss``, up to 8192 outputs) always runs ``wdmpnn_head_spectra``, on every path below.
+    Its ``target_batch`` may be a float ``ndarray`` [B][T] with NaN = missing instead of lists with ``None``.
+    ``direct``: with the fused head and a
     plain one-molecule encoder, skip the autograd engine (``_direct_step``: the same launches and results,
     bitwise, without the engine's host gaps).  The direct step keeps one packed copy of the encoder weights
     across steps (rewritten by :class:`HipAdam`); after writing an encoder parameter through ``.data`` call

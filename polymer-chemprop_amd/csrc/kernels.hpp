@@ -1225,7 +1225,8 @@ struct StackWant {
     int dw;     // launch l: the tiles of dW_l
     int db;     // launch l: db_l
     int last;   // launch l carries the last layer's sums (the loss, and dW_L / db_L where wanted)
-    int slope;  // launch l ends with the workgroup that sums dslope
+    int slope;  // launch l ends with the workgroup that sums dslope (2: site L-1's partial sums are per tile, as
+                // head_spectra_bwd_kernel writes them, not per row)
 };
 
 // The last layer's sums, one thread per element, rows in order: dW_L [T][Kin] and db_L [T] where wanted, the loss
@@ -1331,12 +1332,12 @@ __global__ __launch_bounds__(256) void head_stack_rows_kernel(WdHeadStack P, int
 
 // dslope = the sum of every site's partial sums, one workgroup: thread t adds the partials t, t + 256, ... of
 // the sites in order, thread 0 the 256 sums in order
-__device__ __forceinline__ void stack_slope_sum(const WdHeadStack &P, const StackLayout &S, float *red) {
+__device__ __forceinline__ void stack_slope_sum(const WdHeadStack &P, const StackLayout &S, float *red, bool tiled_last) {
     const int tid = threadIdx.x;
     float s = 0.f;
     if (P.act == ACT_PRELU)
         for (int site = 1; site < P.L; ++site) {
-            const long long n = site == P.L - 1 ? P.B : head_tiles(P.B, P.Hf, HEAD_H_TS);
+            const long long n = site == P.L - 1 && !tiled_last ? P.B : head_tiles(P.B, P.Hf, HEAD_H_TS);
             for (long long e = tid; e < n; e += 256) s += S.spart[(size_t)(site - 1) * S.np + e];
         }
     red[tid] = s;
@@ -1396,7 +1397,7 @@ __global__ __launch_bounds__(256) void head_stack_bwd_kernel(WdHeadStack P, int 
         return;
     }
     if (b - n1 - n2 >= stack_bwd_tail_blocks(P, Q)) {
-        if (Q.slope) stack_slope_sum(P, S, red);
+        if (Q.slope) stack_slope_sum(P, S, red, Q.slope == 2);
         return;
     }
     const long long ndb = Q.db ? Hf : 0, last = Q.last ? stack_last_count(P) : 0;

@@ -33,6 +33,7 @@
 #include "gemm_x6.hpp"
 #include "graph_build.hpp"
 #include "kernels.hpp"
+#include "head_spectra.hpp"
 #include "selfcheck.hpp"
 #include "small_fwd.hpp"
 #include "wdmpnn.h"
@@ -2316,6 +2317,113 @@ int wdmpnn_head_stack_predict(const WdHeadStackPredict *h, void *stream) {
     }
     hipLaunchKernelGGL(head_stack_predict_rows_kernel, dim3((h->B + 3) / 4), dim3(256), 0, st, *h);
     WD_CHECK_LAUNCH("head_stack_predict_rows");
+    return 0;
+}
+
+// the checks wdmpnn_head_spectra and wdmpnn_head_spectra_predict share: head_stack_check's (with one output in
+// place of T: its T <= 64 is the other heads' limit), then the spectrum's own
+static int head_spectra_check(int B, int F, int Hf, int T, int L, int ld_x, int act, int spectra_act,
+                              const float *const *W, const float *slope) {
+    WD_TRY(head_stack_check(B, F, Hf, T > 0 ? 1 : T, L, ld_x, act, 0, 1, W, slope));
+    if (T > WD_HEAD_MAX_SPECTRUM)
+        return fail(WD_ERR_UNSUPPORTED, "head spectra: %d outputs (at most %d)", T, WD_HEAD_MAX_SPECTRUM);
+    if (spectra_act < 0 || spectra_act > 1) return fail(WD_ERR_UNSUPPORTED, "head spectra: activation %d", spectra_act);
+    return 0;
+}
+
+int wdmpnn_head_spectra_scratch_bytes(int32_t B, int32_t F, int32_t Hf, int32_t T, int32_t L, size_t *bytes) {
+    if (!bytes) return fail(WD_ERR_ARG, "null bytes");
+    if (B < 0 || F <= 0 || T <= 0 || L < 1 || L > WD_HEAD_MAX_LAYERS || (L > 1 && Hf <= 0))
+        return fail(WD_ERR_SHAPE, "head spectra: bad sizes");
+    *bytes = sizeof(float) * head_spectra_floats(B, F, L == 1 ? 1 : Hf, T, L);
+    return 0;
+}
+
+int wdmpnn_head_spectra(const WdHeadSpectra *h, void *stream) {
+    WD_KERNELS_OK();
+    if (!h) return fail(WD_ERR_ARG, "null head");
+    WD_TRY(head_spectra_check(h->B, h->F, h->Hf, h->T, h->L, h->ld_x, h->act, h->spectra_act, h->W, h->slope));
+    if (h->loss_kind < 0 || h->loss_kind > 1) return fail(WD_ERR_UNSUPPORTED, "head spectra: loss kind %d", h->loss_kind);
+    if (!(h->p >= 0.f && h->p < 1.f)) return fail(WD_ERR_ARG, "head spectra: dropout %g outside [0, 1)", (double)h->p);
+    if (h->ld_table < 2 * h->T) return fail(WD_ERR_SHAPE, "head spectra: bad sizes (ld_table)");
+    if (!h->loss || !h->scratch || (h->B && (!h->x || !h->table)))
+        return fail(WD_ERR_ARG, "head spectra: null pointer");
+    WdHeadStack P{};  // the stack kernels' view: the same FFN, scratch prefix and gradient outputs
+    P.x = h->x; P.ld_x = h->ld_x; P.B = h->B; P.F = h->F; P.Hf = h->L == 1 ? 1 : h->Hf; P.T = h->T; P.L = h->L;
+    for (int l = 0; l < h->L; ++l) { P.W[l] = h->W[l]; P.b[l] = h->b[l]; P.dW[l] = h->dW[l]; P.db[l] = h->db[l]; }
+    P.slope = h->slope; P.table = h->table; P.ld_table = h->ld_table; P.inv_n = h->inv_n; P.act = h->act;
+    P.p = h->p; P.seed = h->seed; P.n_classes = 1; P.scratch = h->scratch; P.scratch_bytes = h->scratch_bytes;
+    P.dx = h->dx; P.dslope = h->dslope; P.loss = h->loss;
+    const size_t need = sizeof(float) * head_spectra_floats(P.B, P.F, P.Hf, P.T, P.L);
+    if (h->scratch_bytes < need)
+        return fail(WD_ERR_WORKSPACE, "head spectra: scratch of %zu bytes, %zu needed", h->scratch_bytes, need);
+    if (P.B == 0) return 0;
+    hipStream_t st = (hipStream_t)stream;
+    const int B = P.B, Hf = P.Hf, T = P.T, L = P.L;
+    const StackLayout S = stack_layout(P);
+    float *zl = (float *)P.scratch + head_stack_floats(B, P.F, Hf, T, L);
+    // the lowest level whose dz something needs (head_stack_run)
+    int m = L;
+    for (int l = L; l >= 1; --l)
+        if (P.dW[l - 1] || P.db[l - 1]) m = l;
+    if (P.dslope && P.act == WD_ACT_PRELU && L > 1) m = 1;
+    if (P.dx) m = 0;
+    for (int l = 1; l < L; ++l) {
+        hipLaunchKernelGGL(head_stack_fwd_kernel, dim3(head_tiles(B, Hf, HEAD_H_TS)), dim3(256), 0, st, P, l);
+        WD_CHECK_LAUNCH("head_stack_fwd");
+    }
+    hipLaunchKernelGGL(head_spectra_z_kernel, dim3(head_tiles(B, T, HEAD_H_TS)), dim3(256), 0, st, P, zl);
+    WD_CHECK_LAUNCH("head_spectra_z");
+    const SpectraRows R{zl, P.b[L - 1], P.table, P.ld_table, B, T, P.inv_n, h->spectra_act, h->loss_kind, h->out, S.dout, S.lossrow};
+    hipLaunchKernelGGL(head_spectra_rows_kernel, dim3(B), dim3(256), 0, st, R);
+    WD_CHECK_LAUNCH("head_spectra_rows");
+    {
+        StackWant Q{};
+        Q.dz = m <= L - 1;
+        Q.dw = P.dW[L - 1] != nullptr;
+        Q.db = P.db[L - 1] != nullptr;
+        hipLaunchKernelGGL(head_spectra_bwd_kernel, dim3((unsigned)spectra_bwd_blocks(P, Q)), dim3(256), 0, st, P, Q);
+        WD_CHECK_LAUNCH("head_spectra_bwd");
+    }
+    for (int l = L - 1; l >= 1; --l) {
+        StackWant Q{};
+        Q.dz = m <= l - 1;
+        Q.dw = P.dW[l - 1] != nullptr;
+        Q.db = P.db[l - 1] != nullptr;
+        Q.slope = l == 1 && P.dslope ? 2 : 0;
+        if (!(Q.dz || Q.dw || Q.db || Q.slope)) continue;
+        hipLaunchKernelGGL(head_stack_bwd_kernel, dim3((unsigned)stack_bwd_blocks(P, l, Q)), dim3(256), 0, st, P, l, Q);
+        WD_CHECK_LAUNCH("head_stack_bwd");
+    }
+    return 0;
+}
+
+int wdmpnn_head_spectra_predict(const WdHeadSpectraPredict *h, void *stream) {
+    WD_KERNELS_OK();
+    if (!h) return fail(WD_ERR_ARG, "null head");
+    WD_TRY(head_spectra_check(h->B, h->F, h->Hf, h->T, h->L, h->ld_x, h->act, h->spectra_act, h->W, h->slope));
+    if (h->normalize < 0 || h->normalize > 1) return fail(WD_ERR_UNSUPPORTED, "head spectra: normalize %d", h->normalize);
+    if (h->B == 0) return 0;
+    if (!h->x || !h->out || !h->scratch) return fail(WD_ERR_ARG, "head spectra: null pointer");
+    const int Hf = h->L == 1 ? 1 : h->Hf;
+    const size_t need = sizeof(float) * head_spectra_predict_floats(h->B, Hf, h->T, h->L);
+    if (h->scratch_bytes < need)
+        return fail(WD_ERR_WORKSPACE, "head spectra: scratch of %zu bytes, %zu needed", h->scratch_bytes, need);
+    hipStream_t st = (hipStream_t)stream;
+    WdHeadStack v{};  // the stack kernels' view (no dropout; z_l at the start of the scratch, then z_L)
+    v.x = h->x; v.ld_x = h->ld_x; v.B = h->B; v.F = h->F; v.Hf = Hf; v.T = h->T; v.L = h->L;
+    for (int l = 0; l < h->L; ++l) { v.W[l] = h->W[l]; v.b[l] = h->b[l]; }
+    v.slope = h->slope; v.act = h->act; v.scratch = h->scratch;
+    float *zl = (float *)h->scratch + (size_t)(h->L - 1) * h->B * Hf;
+    for (int l = 1; l < h->L; ++l) {
+        hipLaunchKernelGGL(head_stack_fwd_kernel, dim3(head_tiles(h->B, Hf, HEAD_H_TS)), dim3(256), 0, st, v, l);
+        WD_CHECK_LAUNCH("head_stack_fwd");
+    }
+    hipLaunchKernelGGL(head_spectra_z_kernel, dim3(head_tiles(h->B, h->T, HEAD_H_TS)), dim3(256), 0, st, v, zl);
+    WD_CHECK_LAUNCH("head_spectra_z");
+    const SpectraPredictRows R{zl, h->b[h->L - 1], h->out, h->mask, h->B, h->T, h->spectra_act, h->normalize};
+    hipLaunchKernelGGL(head_spectra_predict_rows_kernel, dim3(h->B), dim3(256), 0, st, R);
+    WD_CHECK_LAUNCH("head_spectra_predict_rows");
     return 0;
 }
 
