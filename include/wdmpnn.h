@@ -372,6 +372,33 @@ int wdmpnn_index_select_rows(const float *src, int64_t n_src_rows, int64_t row_l
 int wdmpnn_index_select_rows_backward(const float *grad, int64_t n_index, int64_t row_len, const int64_t *perm,
                                       const int64_t *ptr, int64_t n_src_rows, float *dsrc, void *stream);
 
+/* Join, gather or split rows: one launch builds the row-major fp32 matrix `out` [B][ld_out] from up to
+ * WD_JOIN_MAX_SEGMENTS column segments, each optionally gathered by a row index:
+ *     out[b][o_s + j] = src_s[(idx_s ? idx_s[b] : b) * ld_s + c0_s + j]     j < w_s,  o_s = w_0 + ... + w_{s-1}
+ * Uses: the FFN input x = [encoding | feature_table[idx]] of a model with molecule features (mpn.py:281-285,
+ * the torch.cat of MPN.forward) as two segments; a row gather (one segment with an index); the contiguous
+ * copy of a column range, dEmb = dx[:, 0:H] (one segment, c0 = 0, ld = ld_x).
+ * A pure copy: every payload bit is preserved (NaN payloads, -0.0).  Columns of `out` at and beyond the
+ * sum of the widths are not written.  No atomics, a fixed thread-to-element map.  A segment moves as
+ * 16-byte vectors when src, ld, c0, its destination offset, out and ld_out are all multiples of 16 bytes
+ * (the last w % 4 columns as single words), else word by word.  Indices are int64 like
+ * wdmpnn_index_select_rows'; the kernel clamps nothing and reads src[idx[b]]: range checking is the caller's.
+ * Refused before any launch: n_seg > WD_JOIN_MAX_SEGMENTS (WD_ERR_UNSUPPORTED), n_seg < 1 or a NULL struct
+ * (WD_ERR_ARG); B < 0, w <= 0, c0 < 0, ld < c0 + w, ld_out < sum of w (WD_ERR_SHAPE); out or a src NULL
+ * with B > 0 (WD_ERR_ARG).  B == 0 is a no-op. */
+#define WD_JOIN_MAX_SEGMENTS 4
+typedef struct WdJoin {
+    int32_t B, n_seg;
+    struct {
+        const float *src;    /* [rows][ld]                                   */
+        int32_t ld, c0, w;   /* leading dimension, first column, columns     */
+        const int64_t *idx;  /* [B] source rows, or NULL: row b              */
+    } seg[WD_JOIN_MAX_SEGMENTS];
+    float *out;              /* [B][ld_out]                                  */
+    int32_t ld_out;
+} WdJoin;
+int wdmpnn_join_rows(const WdJoin *j, void *stream);
+
 /* One Adam / AdamW optimizer step (torch.optim.Adam / AdamW semantics without amsgrad: the optimizer
  * step of train/train.py:84, built by utils.py:295-310) over n tensors in one launch per 16 tensors.
  * Replaces torch's multi-tensor / fused Adam kernels; per element: g += wd p (AdamW: p -= lr wd p),

@@ -7,9 +7,11 @@ Drop-in replacements for ``chemprop.models.mpn.MPNEncoder`` / ``MPN``,
 """
 from .args import TrainArgs
 from .featurization import BatchMolGraph, get_atom_fdim, get_bond_fdim, mol2graph
+from .features import FeatureIndex, FeatureRows, FeatureTable
 from .model import MoleculeModel
 from .mpn import MPN, MPNEncoder
 from .nn_utils import get_activation_function, index_select_ND, initialize_weights
 
 __all__ = ['TrainArgs', 'BatchMolGraph', 'get_atom_fdim', 'get_bond_fdim', 'mol2graph', 'MoleculeModel', 'MPN',
-           'MPNEncoder', 'get_activation_function', 'index_select_ND', 'initialize_weights']
+           'MPNEncoder', 'get_activation_function', 'index_select_ND', 'initialize_weights', 'FeatureTable',
+           'FeatureIndex', 'FeatureRows']

@@ -46,11 +46,12 @@ EXPORTED_SYMBOLS = ('wdmpnn_abi_version', 'wdmpnn_last_error', 'wdmpnn_workspace
                     'wdmpnn_feed_destroy', 'wdmpnn_adam_step_repack', 'wdmpnn_self_check', 'wdmpnn_head_predict',
                     'wdmpnn_head_stack_scratch_bytes', 'wdmpnn_head_stack', 'wdmpnn_head_stack_predict',
                     'wdmpnn_head_stack_partial', 'wdmpnn_head_spectra_scratch_bytes', 'wdmpnn_head_spectra',
-                    'wdmpnn_head_spectra_predict')
+                    'wdmpnn_head_spectra_predict', 'wdmpnn_join_rows')
 HEAD_MAX_LAYERS = 6  # WD_HEAD_MAX_LAYERS
 HEAD_MAX_SPECTRUM = 8192  # WD_HEAD_MAX_SPECTRUM
 SPECTRA_ACTIVATIONS = {'exp': 0, 'softplus': 1}  # WdHeadSpectra.spectra_act
 SPECTRA_LOSSES = {'sid': 0, 'wasserstein': 1}  # WdHeadSpectra.loss_kind
+JOIN_MAX_SEGMENTS = 4  # WD_JOIN_MAX_SEGMENTS
 
 
 class WdCsr(Structure):
@@ -172,6 +173,32 @@ class WdHeadSpectraPredict(Structure):
                 ('out', c_void_p), ('spectra_act', c_int32), ('normalize', c_int32), ('mask', c_void_p)]
 
 
+class WdJoinSegment(Structure):
+    _fields_ = [('src', c_void_p), ('ld', c_int32), ('c0', c_int32), ('w', c_int32), ('idx', c_void_p)]
+
+
+class WdJoin(Structure):
+    _fields_ = [('B', c_int32), ('n_seg', c_int32), ('seg', WdJoinSegment * JOIN_MAX_SEGMENTS), ('out', c_void_p),
+                ('ld_out', c_int32)]
+
+
+def join_rows(out, segments, stream: int) -> None:
+    """wdmpnn_join_rows into ``out`` (float32 device tensor ``[B][ld_out]``, row-major): ``segments`` are
+    ``(src data pointer, ld, c0, w, index data pointer or 0)``.  Every index must have been range-checked by the
+    caller (``features.FeatureTable.index``)."""
+    j = WdJoin()
+    j.B, j.n_seg = out.shape[0], len(segments)
+    if len(segments) > JOIN_MAX_SEGMENTS:
+        raise NotImplementedError(f'join_rows: {len(segments)} segments (at most {JOIN_MAX_SEGMENTS})')
+    for k, (src, ld, c0, w, idx) in enumerate(segments):
+        g = j.seg[k]
+        g.src, g.ld, g.c0, g.w, g.idx = src, ld, c0, w, idx or None
+    if out.dim() != 2 or not out.is_contiguous() or out.dtype != torch.float32:
+        raise TypeError('join_rows writes a contiguous float32 matrix')
+    j.out, j.ld_out = out.data_ptr(), out.shape[1]
+    check(lib().wdmpnn_join_rows(ctypes.byref(j), stream), 'join rows')
+
+
 def head_spectra_scratch_bytes(B: int, F: int, Hf: int, T: int, L: int) -> int:
     """wdmpnn_head_spectra_scratch_bytes."""
     n = c_size_t()
@@ -237,6 +264,7 @@ def lib() -> ctypes.CDLL:
     L.wdmpnn_head_spectra_scratch_bytes.argtypes = [c_int32, c_int32, c_int32, c_int32, c_int32, POINTER(c_size_t)]
     L.wdmpnn_head_spectra.argtypes = [POINTER(WdHeadSpectra), c_void_p]
     L.wdmpnn_head_spectra_predict.argtypes = [POINTER(WdHeadSpectraPredict), c_void_p]
+    L.wdmpnn_join_rows.argtypes = [POINTER(WdJoin), c_void_p]
     L.wdmpnn_forward_many.argtypes = [c_int32, POINTER(WdGraph), POINTER(WdParams), POINTER(WdConfig),
                                       POINTER(c_void_p), POINTER(c_size_t), POINTER(c_void_p), c_void_p]
     L.wdmpnn_feed_slot_bytes.argtypes = [c_int32, c_int32, c_int32, c_int32, POINTER(c_size_t), POINTER(c_size_t)]
@@ -265,7 +293,7 @@ def lib() -> ctypes.CDLL:
              'wdmpnn_feed_destroy', 'wdmpnn_adam_step_repack', 'wdmpnn_head_predict',
              'wdmpnn_head_stack_scratch_bytes', 'wdmpnn_head_stack', 'wdmpnn_head_stack_predict',
              'wdmpnn_head_stack_partial', 'wdmpnn_head_spectra_scratch_bytes', 'wdmpnn_head_spectra',
-             'wdmpnn_head_spectra_predict'):
+             'wdmpnn_head_spectra_predict', 'wdmpnn_join_rows'):
         getattr(L, fn).restype = c_int
     v = L.wdmpnn_abi_version()
     if v != ABI_VERSION:

@@ -4,7 +4,7 @@ real reference ``TrainArgs``) can be passed instead."""
 from __future__ import annotations
 
 from dataclasses import dataclass, field
-from typing import Optional
+from typing import List, Optional
 
 import torch
 
@@ -36,6 +36,8 @@ class TrainArgs:
     num_tasks: int = 1
     multiclass_num_classes: int = 3
     features_size: int = 0
+    features_path: Optional[List[str]] = None        # args.py:85 (the files whose columns are the input features)
+    no_features_scaling: bool = False                # args.py:230
     ffn_num_layers: int = 2
     ffn_hidden_size: Optional[int] = None
     spectra_activation: str = 'exp'      # args.py:413

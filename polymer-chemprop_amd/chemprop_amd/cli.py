@@ -26,6 +26,12 @@ restated here:
   scored over all positions together (evaluate.py:48-50); the phase features are input features of the model
   (data/utils.py:250-258); predictions are normalised on the device and ``test_preds.csv`` leaves the
   positions a row's phase excludes empty (make_predictions.py:175-181);
+* ``--features_path F [F ...]``: molecule features, the files' columns side by side (data/utils.py:242-246),
+  standardised by a StandardScaler(replace_nan_token=0) fit on the training split unless
+  ``--no_features_scaling`` (run_training.py:111-114; stored as the checkpoint's ``features_scaler``), phase
+  features appended after them unscaled; each split's rows live in one ``features.FeatureTable`` on the
+  device, an epoch's shuffled order is one index upload and a step takes a slice of it, so these models
+  train on the direct step and from cached encodings;
 * MoleculeModel + initialize_weights after ``torch.manual_seed(pytorch_seed)`` (run_training.py:36,
   model.py:39), Adam (utils.py:295-310), NoamLR stepped per batch (utils.py:490-541, nn_utils.py:115-194),
   training batches reshuffled every epoch by one ``Random(seed)`` (data.py:537-587);
@@ -58,6 +64,7 @@ import torch
 
 from .args import TrainArgs
 from .featurization import BatchMolGraph
+from .features import FeatureTable, join_features
 from .graph_io import load_graphs
 from .model import MoleculeModel
 from .nn_utils import initialize_weights
@@ -289,31 +296,52 @@ def predict(model, graphs, idx, batch_size: int, scaler: Optional[StandardScaler
     """predict.py:10-68: eval, no_grad, batches in order, inverse scaling.  ``encodings``: the rows of ``idx``
     from ``frozen_encodings`` (a frozen encoder's outputs, computed once per run): the native prediction head
     on them in place of the model's forward.  ``features``: the input feature rows of the whole data set
-    (indexed by ``idx``).  A spectra model's predictions are normalised per row on the device
+    (numpy rows, indexed by ``idx``), or the split's own ``features.FeatureTable`` (row k = ``idx[k]``'s
+    features, on the device: each batch is then a slice of one index upload, joined to the encodings by one
+    launch).  A spectra model's predictions are normalised per row on the device
     (make_predictions.py:175-181): ``spectra_mask`` is the bool ``[len(idx)][T]`` array of the positions each
     row's phase includes (None: all), uploaded once per batch; excluded positions come back as None."""
     model.eval()
     preds = []
     spectra = bool(getattr(model, 'spectra', False))
+    findex = None
+    if isinstance(features, FeatureTable):
+        if len(features) != len(idx):
+            raise ValueError(f'a feature table of {len(features)} rows for {len(idx)} molecules')
+        findex = features.index(range(len(idx)))
+
+    def batch_features(s):
+        if features is None:
+            return None
+        return findex[s:s + batch_size] if findex is not None else [features[i] for i in idx[s:s + batch_size]]
+
+    def cached_rows(s):  # (the head's input from cached encodings: their rows, joined with the batch's features)
+        emb = encodings[s:s + batch_size]
+        f = batch_features(s)
+        if f is None:
+            return emb
+        if findex is None:
+            f = torch.from_numpy(np.stack(f)).float().to(emb.device)
+        return join_features(emb, f)
     with torch.no_grad():
         for s in range(0, len(idx), batch_size):
             if spectra:
                 dev = next(model.parameters()).device
                 if encodings is not None:
-                    emb = encodings[s:s + batch_size]
+                    emb = cached_rows(s)
                 else:
                     g = BatchMolGraph([graphs[i] for i in idx[s:s + batch_size]])
-                    emb = model.encoder([g], None if features is None else [features[i] for i in idx[s:s + batch_size]])
+                    emb = model.encoder([g], batch_features(s))
                 m = None if spectra_mask is None else \
                     torch.from_numpy(np.ascontiguousarray(spectra_mask[s:s + batch_size])).to(dev)
                 out = head_predict(model, emb, normalize=True, mask=m).cpu().numpy()
                 preds.extend([[None if math.isnan(v) else v for v in row] for row in out.tolist()])
                 continue
             if encodings is not None:
-                preds.extend(head_predict(model, encodings[s:s + batch_size]).cpu().numpy().tolist())
+                preds.extend(head_predict(model, cached_rows(s)).cpu().numpy().tolist())
                 continue
             g = BatchMolGraph([graphs[i] for i in idx[s:s + batch_size]])
-            preds.extend(model([g]).cpu().numpy().tolist())
+            preds.extend(model([g], batch_features(s)).cpu().numpy().tolist())
     if scaler is not None and preds:
         preds = scaler.inverse_transform(preds).tolist()
     return preds
@@ -376,6 +404,30 @@ def load_phase_features(path: str, n_rows: int) -> np.ndarray:
     return feats
 
 
+def load_input_features(paths: List[str], n_rows: int) -> np.ndarray:
+    """``--features_path`` (data/utils.py:242-246): the files' columns side by side, one row per CSV row,
+    float64 ``[n_rows][features]``."""
+    parts = []
+    for path in paths:
+        f = load_features(path)
+        if f.ndim != 2 or len(f) != n_rows or f.shape[1] < 1:
+            raise ValueError(f'{path} holds features of shape {f.shape} for {n_rows} CSV rows')
+        parts.append(f)
+    if not parts:
+        raise ValueError('--features_path needs at least one file')
+    return np.concatenate(parts, axis=1)
+
+
+def scale_features(features: np.ndarray, train_idx: List[int], no_features_scaling: bool = False):
+    """run_training.py:111-114: ``(features of every row as the model sees them, the scaler or None)``.  Unless
+    ``no_features_scaling``, a ``StandardScaler(replace_nan_token=0)`` is fitted on the training rows and applied
+    to every row: NaN cells become 0, a column without variance keeps std 1."""
+    if no_features_scaling:
+        return features, None
+    sc = StandardScaler(replace_nan_token=0).fit(features[train_idx])
+    return sc.transform(features), sc
+
+
 METRICS_OF = {'spectra': ('sid', 'wasserstein')}  # (args.py:568-573, for the metrics only spectra has)
 
 
@@ -408,6 +460,12 @@ def parse_args(argv=None, spectra: bool = False) -> argparse.Namespace:
                     help='CSV (header, label column): one 0/1 row per phase, 0 = position excluded for that phase')
     ap.add_argument('--phase_features_path', default=None,
                     help='CSV (header) or .npy: the one-hot phase of every data row; fed to the model as features')
+    ap.add_argument('--features_path', nargs='+', default=None,
+                    help='CSV (header) or .npy files of molecule features, one row per data row; their columns are '
+                         'concatenated and fed to the FFN next to the encoding')
+    ap.add_argument('--no_features_scaling', action='store_true',
+                    help='feed the features of --features_path as they are (default: standardised on the training '
+                         'split, NaN -> 0)')
     ap.add_argument('--save_dir', required=True)
     ap.add_argument('--polymer', action='store_true')
     ap.add_argument('--split_type', default='random', choices=['random'])
@@ -493,6 +551,17 @@ def run_training(a: argparse.Namespace) -> Dict[str, list]:
     check_metrics(a.dataset_type, metrics)
     minimize = metric in ('rmse', 'mse', 'mae', 'cross_entropy', 'sid', 'wasserstein')
     device = torch.device('cuda', a.gpu)
+    train_idx, val_idx, test_idx = random_split(len(smiles), a.split_sizes, a.seed)
+    if a.train_frac != 1.0:  # run_training.py:132-137; the scalers below are fitted on the subsample
+        train_idx = [train_idx[k] for k in subsample_train(len(train_idx), a.train_frac, a.seed)]
+    # the model's input features: the --features_path columns, standardised on the training split
+    # (run_training.py:111-114), then the phase features as they are (the reference scales those as well)
+    features = features_scaler = None
+    if a.features_path:
+        features, features_scaler = scale_features(load_input_features(a.features_path, len(smiles)), train_idx,
+                                                   a.no_features_scaling)
+    if phase_features is not None:
+        features = phase_features if features is None else np.concatenate([features, phase_features], axis=1)
     args = TrainArgs(hidden_size=a.hidden_size, depth=a.depth, dropout=a.dropout, activation=a.activation,
                      aggregation=a.aggregation, aggregation_norm=a.aggregation_norm, bias=a.bias,
                      undirected=a.undirected, ffn_num_layers=a.ffn_num_layers,
@@ -503,12 +572,11 @@ def run_training(a: argparse.Namespace) -> Dict[str, list]:
                      spectra_activation=a.spectra_activation, spectra_target_floor=a.spectra_target_floor,
                      alternative_loss_function=a.alternative_loss_function,
                      spectra_phase_mask_path=a.spectra_phase_mask_path, phase_features_path=a.phase_features_path,
-                     use_input_features=phase_features is not None,
-                     features_size=0 if phase_features is None else int(phase_features.shape[1]))
+                     features_path=list(a.features_path) if a.features_path else None,
+                     no_features_scaling=bool(a.no_features_scaling),
+                     use_input_features=features is not None,
+                     features_size=0 if features is None else int(features.shape[1]))
     torch.manual_seed(a.pytorch_seed)
-    train_idx, val_idx, test_idx = random_split(len(smiles), a.split_sizes, a.seed)
-    if a.train_frac != 1.0:  # run_training.py:132-137; the scaler below is fitted on the subsample
-        train_idx = [train_idx[k] for k in subsample_train(len(train_idx), a.train_frac, a.seed)]
     scaler = None
     train_targets = [targets[i] for i in train_idx]
     if a.dataset_type == 'regression':
@@ -526,13 +594,15 @@ def run_training(a: argparse.Namespace) -> Dict[str, list]:
     apply_freezing(model, a.frzn_encoder, a.frzn_ffn_layers)
     model = model.to(device)
     optimizer = build_optimizer(model, args)
+    # one resident feature table per split, in split order: a batch is a slice of an index into it
+    splits = (('train', train_idx), ('val', val_idx), ('test', test_idx))
+    tables = None if features is None else {name: FeatureTable(features[idx], device) if len(idx) else None
+                                            for name, idx in splits}
     # a frozen encoder without dropout gives every molecule the same encoding at every step: computed once per
     # split, the steps and the per-epoch scores then run the head alone (train.frozen_encodings)
     enc_cache = None
-    if args.frzn_encoder and a.dropout == 0 and not a.no_encoding_cache and phase_features is None and \
-            _predict_head(model.eval()) is not None:
-        enc_cache = {name: frozen_encodings(model, [graphs[i] for i in idx], a.batch_size)
-                     for name, idx in (('train', train_idx), ('val', val_idx), ('test', test_idx))}
+    if args.frzn_encoder and a.dropout == 0 and not a.no_encoding_cache and _predict_head(model.eval()) is not None:
+        enc_cache = {name: frozen_encodings(model, [graphs[i] for i in idx], a.batch_size) for name, idx in splits}
     scheduler = NoamLR(optimizer, warmup_epochs=[a.warmup_epochs], total_epochs=[a.epochs],
                        steps_per_epoch=len(train_idx) // a.batch_size, init_lr=[a.init_lr], max_lr=[a.max_lr],
                        final_lr=[a.final_lr])
@@ -542,8 +612,8 @@ def run_training(a: argparse.Namespace) -> Dict[str, list]:
         return train_targets[pos] if spectra else [train_targets[p] for p in pos]
 
     def run_predict(name, idx):
-        return predict(model, graphs, idx, a.batch_size, scaler, enc_cache and enc_cache[name], phase_features,
-                       None if row_mask is None else row_mask[idx])
+        return predict(model, graphs, idx, a.batch_size, scaler, enc_cache and enc_cache[name],
+                       tables and tables[name], None if row_mask is None else row_mask[idx])
     sampler = Random(a.seed)
     log_path = os.path.join(a.save_dir, 'train_val_loss_log.csv')
     best = math.inf if minimize else -math.inf
@@ -555,16 +625,17 @@ def run_training(a: argparse.Namespace) -> Dict[str, list]:
             order = list(range(len(train_idx)))
             sampler.shuffle(order)
             losses = []
+            # the epoch's order as one validated index upload; every step takes a slice of it
+            findex = tables['train'].index(order) if tables is not None and order else None
             for s in range(0, len(order), a.batch_size):
                 pos = order[s:s + a.batch_size]
+                feats = None if findex is None else findex[s:s + a.batch_size]
                 if enc_cache is not None:
                     rows = enc_cache['train'][torch.as_tensor(pos, device=device)]
                     loss = train_step(model, None, batch_targets(pos), loss_func, optimizer, scheduler,
-                                      a.dataset_type, grad_clip=a.grad_clip, encodings=rows)
+                                      a.dataset_type, features_batch=feats, grad_clip=a.grad_clip, encodings=rows)
                 else:
                     g = BatchMolGraph([graphs[train_idx[p]] for p in pos])
-                    # (phase features are input features: such a step takes the autograd path with the fused head)
-                    feats = None if phase_features is None else [phase_features[train_idx[p]] for p in pos]
                     loss = train_step(model, [g], batch_targets(pos), loss_func, optimizer, scheduler,
                                       a.dataset_type, features_batch=feats, grad_clip=a.grad_clip)
                 losses.append(float(loss))
@@ -575,11 +646,11 @@ def run_training(a: argparse.Namespace) -> Dict[str, list]:
             w.writerow([epoch, float(np.mean(losses)) if losses else float('nan')] +
                        [float(np.nanmean(tr_scores[m])) if tr_scores[m] else float('nan') for m in metrics] +
                        [float(np.nanmean(val_scores[m])) if val_scores[m] else float('nan') for m in metrics])
-            save_checkpoint(os.path.join(a.save_dir, 'model.pt'), model, scaler, None, args)
+            save_checkpoint(os.path.join(a.save_dir, 'model.pt'), model, scaler, features_scaler, args)
             v = float(np.nanmean(val_scores[metric])) if val_scores[metric] else float('nan')
             if (minimize and v < best) or (not minimize and v > best) or (epoch == 0 and math.isnan(v)):
                 best, best_epoch = v, epoch
-                save_checkpoint(os.path.join(a.save_dir, 'best_model.pt'), model, scaler, None, args)
+                save_checkpoint(os.path.join(a.save_dir, 'best_model.pt'), model, scaler, features_scaler, args)
     ckpt = torch.load(os.path.join(a.save_dir, 'best_model.pt'), map_location=device, weights_only=True)
     model.load_state_dict(ckpt['state_dict'])
     test_targets = [targets[i] for i in test_idx]

@@ -631,8 +631,19 @@ class MPN(nn.Module):
                                           'per input (i.e., number_of_molecules = 1).')
             batch = [mol2graph(b) for b in batch]
         dev = self.encoder[0].W_i.weight.device if not self.features_only else torch.device(self.device)
+        join = None
         if self.use_input_features:
-            features_batch = torch.from_numpy(np.stack(features_batch)).float().to(dev)
+            from .features import FeatureRows, is_device_features
+            if is_device_features(features_batch):
+                # rows already on the device (features.FeatureTable, or a float32 tensor): no host copy.  With
+                # gradients off and one encoder the output below is one join launch; otherwise the rows become
+                # a tensor (one gather launch) for the torch.cat
+                if not self.features_only and len(self.encoder) == 1 and not torch.is_grad_enabled():
+                    join = features_batch
+                elif isinstance(features_batch, FeatureRows):
+                    features_batch = features_batch.to_tensor()
+            else:
+                features_batch = torch.from_numpy(np.stack(features_batch)).float().to(dev)
             if self.features_only:
                 return features_batch
         if self.atom_descriptors == 'descriptor':
@@ -643,6 +654,9 @@ class MPN(nn.Module):
         else:
             encodings = [enc(ba) for enc, ba in zip(self.encoder, batch)]
         output = reduce(lambda x, y: torch.cat((x, y), dim=1), encodings)
+        if join is not None:
+            from .features import join_features
+            return join_features(output, join)
         if self.use_input_features:
             if len(features_batch.shape) == 1:
                 features_batch = features_batch.view(1, -1)

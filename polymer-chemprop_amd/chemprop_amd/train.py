@@ -20,6 +20,7 @@ from torch.optim import Adam, Optimizer
 from torch.optim.lr_scheduler import _LRScheduler
 
 from .dp import GradBucket
+from .features import features_width, is_device_features, join_features, split_columns  # noqa: F401 (join_features: public)
 
 
 class NoamLR(_LRScheduler):
@@ -834,16 +835,25 @@ def _grad_buffer(p: torch.Tensor) -> torch.Tensor:
     return g
 
 
+def _features_ok(mpn, features_batch) -> bool:
+    """The features side of a direct step: a model without input features gets none; a model with them gets
+    rows that are on the device already (``features.FeatureRows`` or a float32 ``[B][Ff]`` tensor there).  A list
+    of numpy rows keeps the autograd path."""
+    if mpn.use_input_features:
+        return is_device_features(features_batch)
+    return features_batch is None
+
+
 def _direct_encoder(model: nn.Module, mol_batch, features_batch, head):
-    """The MPNEncoder when the step can skip autograd: one molecule per input, no extra features or
-    descriptors, depth >= 2, every parameter trainable and written by the direct step (the encoder's
-    native gradients and the fused head's); else None."""
+    """The MPNEncoder when the step can skip autograd: one molecule per input, no descriptors, extra features
+    only as device rows (``_features_ok``), depth >= 2, every parameter trainable and written by the direct
+    step (the encoder's native gradients and the fused head's); else None."""
     from .model import MoleculeModel
     from .mpn import MPNEncoder
     if not isinstance(model, MoleculeModel) or type(model).forward is not MoleculeModel.forward:
         return None
     mpn = model.encoder
-    if features_batch is not None or mpn.features_only or mpn.use_input_features or mpn.atom_descriptors or \
+    if mpn.features_only or not _features_ok(mpn, features_batch) or mpn.atom_descriptors or \
             len(mpn.encoder) != 1 or not isinstance(mol_batch, (list, tuple)) or len(mol_batch) != 1:
         return None
     enc = mpn.encoder[0]
@@ -919,7 +929,7 @@ def _frozen_plan(model: nn.Module, mol_batch, features_batch, head, cached: bool
     if head is None or not isinstance(model, MoleculeModel) or type(model).forward is not MoleculeModel.forward:
         return None
     mpn = model.encoder
-    if features_batch is not None or mpn.features_only or mpn.use_input_features or mpn.atom_descriptors or \
+    if mpn.features_only or not _features_ok(mpn, features_batch) or mpn.atom_descriptors or \
             len(mpn.encoder) != 1:
         return None
     if not cached and (not isinstance(mol_batch, (list, tuple)) or len(mol_batch) != 1 or
@@ -979,7 +989,7 @@ def frozen_encodings(model: nn.Module, graphs: Sequence, batch_size: int) -> tor
 
 
 def _direct_step(model, enc, graph, head, target_batch, target_weights, data_weights, bucket=None,
-                 plan: _FrozenPlan = None, encodings: torch.Tensor = None) -> torch.Tensor:
+                 plan: _FrozenPlan = None, encodings: torch.Tensor = None, features=None) -> torch.Tensor:
     """Forward, loss and every gradient of a fused-head step without the autograd engine: the encoder's
     training forward, wdmpnn_head_mse (loss, d loss / d encoding, the head's gradients) and the encoder's
     backward on that gradient (the incoming gradient of the loss is 1), each written straight into the
@@ -989,7 +999,12 @@ def _direct_step(model, enc, graph, head, target_batch, target_weights, data_wei
     (``wdmpnn_head_stack_partial``) and sets their ``.grad`` to None; a frozen encoder runs its inference
     forward on a pack that outlives optimizer steps (``MPNEncoder._frozen_forward``), the head computes no dx and
     there is no encoder backward.  ``encodings`` (frozen encoder only): this batch's rows of
-    ``frozen_encodings`` in place of the forward."""
+    ``frozen_encodings`` in place of the forward.
+    ``features`` (a model with input features: ``features.FeatureRows`` or a float32 device tensor [B][Ff]):
+    one ``wdmpnn_join_rows`` launch builds the head's input x = [encoding | features] after the encoder
+    forward, the head runs on x (F = ld_x = H + Ff), and one more launch makes the encoder's slice of dx,
+    dx[:, 0:H], contiguous for the encoder backward (a frozen encoder has no dx and no such launch): what
+    ``torch.cat`` and its backward do on the autograd path, bitwise."""
     from . import _native
     stack = isinstance(head, _StackHead)
     if stack:
@@ -1005,6 +1020,9 @@ def _direct_step(model, enc, graph, head, target_batch, target_weights, data_wei
         out = enc._frozen_forward(graph)
     else:
         out, state = enc._train_forward(graph)
+    n_emb = out.shape[1] if out.dim() == 2 else 0
+    if features is not None:
+        out = join_features(out, features)  # (x: the head's input from here on)
     # the loss table read by the head kernel straight from its pinned host buffer (no copy launch in the
     # step: the copy kernel and its gap were ~10 us, profiles/round4_train_kernel_trace_v1.txt)
     # (the spectra row kernel reads its table rows in several passes: a device copy, not the pinned buffer)
@@ -1052,6 +1070,8 @@ def _direct_step(model, enc, graph, head, target_batch, target_weights, data_wei
         for p in plan.frozen:  # (as zero_grad(set_to_none=True) on the autograd path: the optimizer skips them)
             p.grad = None
     if not enc_frozen:
+        if features is not None:
+            dx = split_columns(dx, 0, n_emb)  # (the encoder's slice of dx, contiguous: torch.cat's backward)
         enc._train_backward(state, dx, {n: _grad_buffer(p) for n, p in enc._direct_names()})
     return loss
 
@@ -1081,7 +1101,13 @@ def train_step(model: nn.Module, mol_batch, target_batch, loss_func: Callable, o
     inference forward on a weight pack kept across optimizer steps with no backward, and the frozen
     parameters' ``.grad`` is None after the step.  ``encodings``: this batch's rows of ``frozen_encodings``
     (frozen encoder without dropout): the step is then the head and the optimizer alone, with the same result,
-    bitwise; ``mol_batch`` is not read."""
+    bitwise; ``mol_batch`` is not read.
+
+    ``features_batch`` (a model with ``use_input_features``): a list of numpy rows as in the reference takes the
+    autograd path (``MPN.forward`` stacks, copies and concatenates them); ``features.FeatureRows`` (rows of a
+    device-resident ``FeatureTable``) or a float32 device tensor ``[B][Ff]`` take the direct step, frozen plans and
+    ``encodings=`` included: two more launches than the same step without features (the join and the split of
+    dx), one with a frozen encoder or cached encodings, and the same losses and gradients, bitwise."""
     if not model.training:  # (module.train() walks every submodule: the reference sets it once per epoch)
         model.train()
     head = _fusable_head(model, loss_func, dataset_type) if fused_head else None
@@ -1097,22 +1123,24 @@ def train_step(model: nn.Module, mol_batch, target_batch, loss_func: Callable, o
             raise ValueError('train_step(encodings=...) needs the direct step of a model with a frozen encoder without '
                              'dropout and an FFN the native head runs')
         l1 = plan.head.linears[0]
-        if encodings.dim() != 2 or encodings.shape[1] != l1.in_features or encodings.dtype != torch.float32 or \
-                encodings.device != l1.weight.device:
-            raise ValueError(f'encodings of shape {tuple(encodings.shape)} ({encodings.dtype}, {encodings.device}) for '
-                             f'an FFN input of {l1.in_features} on {l1.weight.device}')
+        n_feat = features_width(features_batch) if features_batch is not None else 0
+        if encodings.dim() != 2 or encodings.shape[1] + n_feat != l1.in_features or \
+                encodings.dtype != torch.float32 or encodings.device != l1.weight.device:
+            raise ValueError(f'encodings of shape {tuple(encodings.shape)} ({encodings.dtype}, {encodings.device}) '
+                             f'and {n_feat} features for an FFN input of {l1.in_features} on {l1.weight.device}')
         encodings = encodings.detach().contiguous()
     if plan is not None and not direct:
         plan = None
     if plan is not None:
         enc = plan.enc if not plan.enc_frozen else None  # (HipAdam rewrites a trainable encoder's pack)
         loss = _direct_step(model, plan.enc, None if encodings is not None else mol_batch[0], head, target_batch,
-                            target_weights, data_weights, None, plan, encodings)
+                            target_weights, data_weights, None, plan, encodings, features_batch)
     elif enc is not None:
         # every trainable parameter's gradient is overwritten: no zeroing, no autograd
         if bucket is not None:
             bucket.attach()
-        loss = _direct_step(model, enc, mol_batch[0], head, target_batch, target_weights, data_weights, bucket)
+        loss = _direct_step(model, enc, mol_batch[0], head, target_batch, target_weights, data_weights, bucket,
+                            features=features_batch)
     else:
         if bucket is not None:
             bucket.zero()

@@ -575,6 +575,45 @@ __global__ __launch_bounds__(256) void index_select_rows_kernel(const float *__r
     }
 }
 
+// wdmpnn_join_rows: out[b][o_s + j] = src_s[(idx_s ? idx_s[b] : b) * ld_s + c0_s + j], a pure copy (moved as
+// 32-bit words, so every payload bit survives).  Each row is cut into units, a segment after the other: a
+// segment on the vector path (`vec`, chosen by the host from the alignment of both sides) is w / 4 16-byte
+// units followed by w % 4 single words, a scalar segment is w single words.  One thread per unit in a fixed
+// map (unit t of the launch = row t / units, unit t % units of that row); u0 is the segment's first unit.
+struct JoinSeg {
+    const uint32_t *src;
+    const int64_t *idx;
+    int ld, c0, w, o, vec, u0;
+};
+struct JoinArgs {
+    JoinSeg seg[4];
+    uint32_t *out;
+    int B, n_seg, ld_out, units;
+};
+__global__ __launch_bounds__(256) void join_rows_kernel(const JoinArgs A) {
+    const size_t total = (size_t)A.B * A.units;
+    for (size_t t = (size_t)blockIdx.x * blockDim.x + threadIdx.x; t < total; t += (size_t)gridDim.x * blockDim.x) {
+        const int b = (int)(t / A.units);
+        int u = (int)(t % A.units);
+        int s = 0;
+#pragma unroll
+        for (int k = 1; k < 4; ++k)
+            if (k < A.n_seg && u >= A.seg[k].u0) s = k;
+        const JoinSeg &S = A.seg[s];
+        u -= S.u0;
+        const int64_t r = S.idx ? S.idx[b] : (int64_t)b;
+        const uint32_t *from = S.src + r * S.ld + S.c0;
+        uint32_t *to = A.out + (size_t)b * A.ld_out + S.o;
+        const int nv = S.vec ? S.w >> 2 : 0;
+        if (u < nv) {
+            reinterpret_cast<uint4 *>(to)[u] = reinterpret_cast<const uint4 *>(from)[u];
+        } else {
+            const int c = 4 * nv + (u - nv);
+            to[c] = from[c];
+        }
+    }
+}
+
 // Gradient of index_select_rows: dsrc[j] = sum over positions p with index[p] == j of grad[p], added in
 // increasing p (deterministic, no atomics).  perm = positions sorted stably by index, ptr[j] .. ptr[j+1]
 // the positions of row j in perm; one thread per output value.

@@ -1703,6 +1703,54 @@ int wdmpnn_index_select_rows(const float *src, int64_t n_src_rows, int64_t row_l
     return 0;
 }
 
+int wdmpnn_join_rows(const WdJoin *j, void *stream) {
+    WD_KERNELS_OK();
+    if (!j) return fail(WD_ERR_ARG, "join_rows: null struct");
+    if (j->n_seg > WD_JOIN_MAX_SEGMENTS)
+        return fail(WD_ERR_UNSUPPORTED, "join_rows: %d segments (at most %d)", j->n_seg, WD_JOIN_MAX_SEGMENTS);
+    if (j->n_seg < 1) return fail(WD_ERR_ARG, "join_rows: %d segments (at least 1)", j->n_seg);
+    if (j->B < 0) return fail(WD_ERR_SHAPE, "join_rows: B %d", j->B);
+    int64_t width = 0;
+    for (int s = 0; s < j->n_seg; ++s) {
+        const auto &g = j->seg[s];
+        if (g.w <= 0 || g.c0 < 0 || (int64_t)g.ld < (int64_t)g.c0 + g.w)
+            return fail(WD_ERR_SHAPE, "join_rows: segment %d needs w > 0, c0 >= 0, ld >= c0 + w (got w %d c0 %d ld %d)",
+                        s, g.w, g.c0, g.ld);
+        width += g.w;
+    }
+    if (j->ld_out < width)
+        return fail(WD_ERR_SHAPE, "join_rows: ld_out %d for %lld columns", j->ld_out, (long long)width);
+    if (j->B == 0) return 0;
+    if (!j->out) return fail(WD_ERR_ARG, "join_rows: null out");
+    JoinArgs A{};
+    A.out = reinterpret_cast<uint32_t *>(j->out);
+    A.B = j->B;
+    A.n_seg = j->n_seg;
+    A.ld_out = j->ld_out;
+    const bool out_vec = aligned16(j->out) && j->ld_out % 4 == 0;
+    int o = 0, units = 0;
+    for (int s = 0; s < j->n_seg; ++s) {
+        const auto &g = j->seg[s];
+        if (!g.src) return fail(WD_ERR_ARG, "join_rows: null src %d", s);
+        JoinSeg &S = A.seg[s];
+        S.src = reinterpret_cast<const uint32_t *>(g.src);
+        S.idx = g.idx;
+        S.ld = g.ld;
+        S.c0 = g.c0;
+        S.w = g.w;
+        S.o = o;
+        S.u0 = units;
+        // the 16-byte path: every row's first source and destination word on a 16-byte boundary
+        S.vec = out_vec && o % 4 == 0 && aligned16(g.src) && g.ld % 4 == 0 && g.c0 % 4 == 0;
+        units += S.vec ? g.w / 4 + g.w % 4 : g.w;
+        o += g.w;
+    }
+    A.units = units;
+    hipLaunchKernelGGL(join_rows_kernel, dim3(ew_blocks((size_t)j->B * units)), dim3(256), 0, (hipStream_t)stream, A);
+    WD_CHECK_LAUNCH("join_rows");
+    return 0;
+}
+
 int wdmpnn_graph_bytes(const WdCompact *c, size_t *bytes) {
     GraphLayout L;
     WD_TRY(graph_layout(c, L));
