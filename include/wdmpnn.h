@@ -399,6 +399,57 @@ typedef struct WdJoin {
 } WdJoin;
 int wdmpnn_join_rows(const WdJoin *j, void *stream);
 
+/* Ensembles (make_predictions.py:129-201): the per-cell mean and variance of the predictions of M models, and the
+ * pairwise SID of an ensemble of spectra, accumulated on the device in double precision, which is what the
+ * reference's numpy float64 sums of fp32 predictions are.  Both kernels are bandwidth-bound; no atomics, fixed
+ * thread-to-element maps and reduction orders, plain vector stores.
+ *
+ * Add: folds model k's predictions of the data set's rows row0 .. row0 + B into the accumulators, one launch.
+ * Per cell (b, c), c < W:
+ *     v = (double)pred[b][c] * scale_std[c] + scale_mean[c]     (a rounded product, then a rounded sum: bitwise
+ *                                                                 scaler.py's inverse_transform in numpy; without
+ *                                                                 the two scale pointers v = (double)pred[b][c])
+ *     k == 0:  mean = v, m2 = 0                                  (the buffers need no zeroing)
+ *     k  > 0:  d = v - mean;  mean += d / (k + 1);  m2 += d * (v - mean)         (Welford)
+ * on mean[row0 + b][c] and m2[row0 + b][c]; keep[row0 + b][c] = v when `keep` (this model's slab) is given.
+ * m2 / M is the population variance (np.var).  A NaN v makes its own cell NaN and no other.  Columns at and beyond
+ * W of the accumulators are not written.
+ * Refused before any launch: a NULL struct, or pred or mean NULL with B > 0 (WD_ERR_ARG); B < 0, W <= 0,
+ * ld_pred < W, ld_acc < W, row0 < 0, k < 0, exactly one of the scale pointers (WD_ERR_SHAPE);
+ * k >= WD_ENSEMBLE_MAX_MODELS (WD_ERR_UNSUPPORTED).  B == 0 is a no-op. */
+#define WD_ENSEMBLE_MAX_MODELS 32
+typedef struct WdEnsembleAdd {
+    const float *pred;        /* [B][ld_pred], W columns used                       */
+    int32_t ld_pred, B, W;
+    int32_t k;                /* 0-based index of this model                        */
+    int64_t row0;             /* first row of the accumulators this block covers    */
+    const double *scale_mean; /* [W] the model's target scaler, or both NULL        */
+    const double *scale_std;
+    double *mean;             /* [rows][ld_acc]                                     */
+    double *m2;               /* [rows][ld_acc], or NULL                            */
+    double *keep;             /* this model's slab [rows][ld_acc], or NULL          */
+    int32_t ld_acc;
+} WdEnsembleAdd;
+int wdmpnn_ensemble_add(const WdEnsembleAdd *e, void *stream);
+
+/* Pairwise SID: roundrobin_sid (spectra_utils.py:211-241) of the kept slabs, value of model m, row n, position t
+ * at preds[m * model_stride + n * ld + t].  Its head / tail concatenation holds every unordered pair once:
+ *     out[n] = 1 / (M (M - 1) / 2) * sum over a < b, over t, of (p_a - p_b) (log p_a - log p_b)
+ * Positions where model 0 holds NaN contribute 0 (the reference's nan_mask); with threshold > 0 every value below
+ * it is raised to it first (threshold <= 0: off); M == 1 gives NaN, the reference's mean over no pairs.  One
+ * workgroup per row; each position's M logs are computed once.  Elements of `out` at and beyond N are not written.
+ * Refused before any launch: a NULL struct (WD_ERR_ARG); M < 1, T < 1, N < 0, ld < T, model_stride < N * ld
+ * (WD_ERR_SHAPE); M > WD_ENSEMBLE_MAX_MODELS (WD_ERR_UNSUPPORTED); preds or out NULL with N > 0 (WD_ERR_ARG).
+ * N == 0 is a no-op. */
+typedef struct WdEnsembleSid {
+    const double *preds;
+    int64_t model_stride;     /* elements between two models' slabs                 */
+    int32_t ld, M, N, T;
+    double threshold;
+    double *out;              /* [N]                                                */
+} WdEnsembleSid;
+int wdmpnn_ensemble_sid(const WdEnsembleSid *e, void *stream);
+
 /* One Adam / AdamW optimizer step (torch.optim.Adam / AdamW semantics without amsgrad: the optimizer
  * step of train/train.py:84, built by utils.py:295-310) over n tensors in one launch per 16 tensors.
  * Replaces torch's multi-tensor / fused Adam kernels; per element: g += wd p (AdamW: p -= lr wd p),

@@ -11,7 +11,7 @@ from __future__ import annotations
 
 import ctypes
 import os
-from ctypes import POINTER, Structure, c_char_p, c_float, c_int, c_int32, c_int64, c_size_t, c_uint64, c_void_p
+from ctypes import POINTER, Structure, c_char_p, c_double, c_float, c_int, c_int32, c_int64, c_size_t, c_uint64, c_void_p
 
 import torch  # noqa: F401  (must precede the CDLL load, see module docstring)
 
@@ -46,12 +46,14 @@ EXPORTED_SYMBOLS = ('wdmpnn_abi_version', 'wdmpnn_last_error', 'wdmpnn_workspace
                     'wdmpnn_feed_destroy', 'wdmpnn_adam_step_repack', 'wdmpnn_self_check', 'wdmpnn_head_predict',
                     'wdmpnn_head_stack_scratch_bytes', 'wdmpnn_head_stack', 'wdmpnn_head_stack_predict',
                     'wdmpnn_head_stack_partial', 'wdmpnn_head_spectra_scratch_bytes', 'wdmpnn_head_spectra',
-                    'wdmpnn_head_spectra_predict', 'wdmpnn_join_rows')
+                    'wdmpnn_head_spectra_predict', 'wdmpnn_join_rows', 'wdmpnn_ensemble_add',
+                    'wdmpnn_ensemble_sid')
 HEAD_MAX_LAYERS = 6  # WD_HEAD_MAX_LAYERS
 HEAD_MAX_SPECTRUM = 8192  # WD_HEAD_MAX_SPECTRUM
 SPECTRA_ACTIVATIONS = {'exp': 0, 'softplus': 1}  # WdHeadSpectra.spectra_act
 SPECTRA_LOSSES = {'sid': 0, 'wasserstein': 1}  # WdHeadSpectra.loss_kind
 JOIN_MAX_SEGMENTS = 4  # WD_JOIN_MAX_SEGMENTS
+ENSEMBLE_MAX_MODELS = 32  # WD_ENSEMBLE_MAX_MODELS
 
 
 class WdCsr(Structure):
@@ -182,6 +184,17 @@ class WdJoin(Structure):
                 ('ld_out', c_int32)]
 
 
+class WdEnsembleAdd(Structure):
+    _fields_ = [('pred', c_void_p), ('ld_pred', c_int32), ('B', c_int32), ('W', c_int32), ('k', c_int32),
+                ('row0', c_int64), ('scale_mean', c_void_p), ('scale_std', c_void_p), ('mean', c_void_p),
+                ('m2', c_void_p), ('keep', c_void_p), ('ld_acc', c_int32)]
+
+
+class WdEnsembleSid(Structure):
+    _fields_ = [('preds', c_void_p), ('model_stride', c_int64), ('ld', c_int32), ('M', c_int32), ('N', c_int32),
+                ('T', c_int32), ('threshold', c_double), ('out', c_void_p)]
+
+
 def join_rows(out, segments, stream: int) -> None:
     """wdmpnn_join_rows into ``out`` (float32 device tensor ``[B][ld_out]``, row-major): ``segments`` are
     ``(src data pointer, ld, c0, w, index data pointer or 0)``.  Every index must have been range-checked by the
@@ -265,6 +278,8 @@ def lib() -> ctypes.CDLL:
     L.wdmpnn_head_spectra.argtypes = [POINTER(WdHeadSpectra), c_void_p]
     L.wdmpnn_head_spectra_predict.argtypes = [POINTER(WdHeadSpectraPredict), c_void_p]
     L.wdmpnn_join_rows.argtypes = [POINTER(WdJoin), c_void_p]
+    L.wdmpnn_ensemble_add.argtypes = [POINTER(WdEnsembleAdd), c_void_p]
+    L.wdmpnn_ensemble_sid.argtypes = [POINTER(WdEnsembleSid), c_void_p]
     L.wdmpnn_forward_many.argtypes = [c_int32, POINTER(WdGraph), POINTER(WdParams), POINTER(WdConfig),
                                       POINTER(c_void_p), POINTER(c_size_t), POINTER(c_void_p), c_void_p]
     L.wdmpnn_feed_slot_bytes.argtypes = [c_int32, c_int32, c_int32, c_int32, POINTER(c_size_t), POINTER(c_size_t)]
@@ -293,7 +308,7 @@ def lib() -> ctypes.CDLL:
              'wdmpnn_feed_destroy', 'wdmpnn_adam_step_repack', 'wdmpnn_head_predict',
              'wdmpnn_head_stack_scratch_bytes', 'wdmpnn_head_stack', 'wdmpnn_head_stack_predict',
              'wdmpnn_head_stack_partial', 'wdmpnn_head_spectra_scratch_bytes', 'wdmpnn_head_spectra',
-             'wdmpnn_head_spectra_predict', 'wdmpnn_join_rows'):
+             'wdmpnn_head_spectra_predict', 'wdmpnn_join_rows', 'wdmpnn_ensemble_add', 'wdmpnn_ensemble_sid'):
         getattr(L, fn).restype = c_int
     v = L.wdmpnn_abi_version()
     if v != ABI_VERSION:

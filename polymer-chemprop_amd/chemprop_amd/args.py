@@ -50,6 +50,8 @@ class TrainArgs:
     frzn_ffn_layers: int = 0
     frzn_encoder: bool = False           # (run_training.py:287-291's --frzn_encoder; cli.apply_freezing)
     polymer: bool = False
+    ensemble_size: int = 1                           # args.py:299 (models trained by one chemprop_train run)
+    task_names: Optional[List[str]] = None           # args.py:439 (the target columns; chemprop_predict's header)
     # optimizer (args.py:397-407, utils.py:295-310)
     init_lr: float = 1e-4
     optimizer: str = 'adam'

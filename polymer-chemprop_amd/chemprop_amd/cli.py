@@ -38,7 +38,16 @@ restated here:
 * each epoch: train, evaluate validation and training sets (evaluate.py), ``train_val_loss_log.csv``,
   ``model.pt``; the best validation score (``--metric``, rmse by default) keeps ``best_model.pt``;
 * test: best weights, predictions inverse-scaled, ``test_scores.json`` / ``test_scores.csv``
-  (run_training.py:440-491, cross_validate.py:149-172) and ``test_preds.csv``.
+  (run_training.py:440-491, cross_validate.py:149-172) and ``test_preds.csv``;
+* ``--ensemble_size M`` (run_training.py:208-499): M models, one after the other, each into ``save_dir/model_<k>/``
+  with its own ``test_scores.json``; the seeds are set once, so model 0 is the model of a run without the flag and
+  the later ones continue the random streams; every model's test predictions are folded into one
+  ``ensemble.EnsembleAccumulator`` on the device, and the top-level scores and ``test_preds.csv`` are the ensemble's.
+
+``chemprop_predict`` (``python -m chemprop_amd.cli predict --test_path CSV --graphs_path NPZ --preds_path OUT
+--checkpoint_dir D | --checkpoint_path P | --checkpoint_paths P ...``) is make_predictions.py's counterpart: the
+predictions of one checkpoint or the mean of an ensemble (``ensemble.predict_ensemble``), with
+``--ensemble_variance`` (spectra: the round-robin SID) and ``--individual_ensemble_predictions``.
 
 The encoder runs on the HIP path (a GPU is required, like every ``chemprop_amd`` forward).  Checkpoints
 (``model.pt``, ``best_model.pt``) have the layout of the reference's ``save_checkpoint`` (utils.py:47-73):
@@ -62,6 +71,7 @@ from typing import Dict, List, Optional
 import numpy as np
 import torch
 
+from ._native import ENSEMBLE_MAX_MODELS
 from .args import TrainArgs
 from .featurization import BatchMolGraph
 from .features import FeatureTable, join_features
@@ -502,7 +512,12 @@ def parse_args(argv=None, spectra: bool = False) -> argparse.Namespace:
                     help='train on this fraction of the training split (drawn by --seed)')
     ap.add_argument('--no_encoding_cache', action='store_true',
                     help='run the frozen encoder every step instead of computing its encodings once')
+    ap.add_argument('--ensemble_size', type=int, default=1,
+                    help='train this many models, one after the other, into save_dir/model_<k>/; the test '
+                         'predictions and scores are the ensemble\'s')
     a = ap.parse_args(argv)
+    if not 1 <= a.ensemble_size <= ENSEMBLE_MAX_MODELS:
+        raise ValueError(f'--ensemble_size must be in 1 .. {ENSEMBLE_MAX_MODELS}')
     if a.alternative_loss_function is not None and a.dataset_type != 'spectra':
         raise ValueError(f'Alternative loss function "{a.alternative_loss_function}" not supported with dataset type '
                          f'"{a.dataset_type}".')
@@ -519,12 +534,7 @@ def run_training(a: argparse.Namespace) -> Dict[str, list]:
     if len(graphs) != len(smiles):
         raise ValueError(f'{a.graphs_path} holds {len(graphs)} graphs for {len(smiles)} CSV rows')
     if a.polymer:  # every row must be a well-formed polymer string (data.py:695-703, featurization.py:335-364)
-        for s, g in zip(smiles, graphs):
-            _, _, rules = split_polymer_string(s)
-            if rules:
-                _, deg = parse_polymer_rules(rules)
-                if not np.isclose(deg, g.degree_of_polym, rtol=1e-6):
-                    raise ValueError(f'graph degree_of_polym {g.degree_of_polym} != 1 + log10(Xn) = {deg} for {s}')
+        check_polymer_rows(smiles, graphs)
     num_tasks = len(header) - 1
     multiclass = a.dataset_type == 'multiclass'
     if multiclass:  # class indices, checked here: a bad one must not reach the loss on the device
@@ -575,7 +585,8 @@ def run_training(a: argparse.Namespace) -> Dict[str, list]:
                      features_path=list(a.features_path) if a.features_path else None,
                      no_features_scaling=bool(a.no_features_scaling),
                      use_input_features=features is not None,
-                     features_size=0 if features is None else int(features.shape[1]))
+                     features_size=0 if features is None else int(features.shape[1]),
+                     polymer=bool(a.polymer), ensemble_size=a.ensemble_size, task_names=list(header[1:]))
     torch.manual_seed(a.pytorch_seed)
     scaler = None
     train_targets = [targets[i] for i in train_idx]
@@ -587,74 +598,113 @@ def run_training(a: argparse.Namespace) -> Dict[str, list]:
     if spectra:  # one float array (NaN = missing): a batch's rows are a slice, not 1801 Python objects per row
         train_targets = np.array([[np.nan if x is None else x for x in r] for r in train_targets], dtype=np.float64)
         train_targets = train_targets.reshape(len(train_idx), num_tasks)
-    model = MoleculeModel(args)
-    initialize_weights(model)
-    if a.checkpoint_frzn is not None:
-        load_frzn_checkpoint(model, a.checkpoint_frzn)
-    apply_freezing(model, a.frzn_encoder, a.frzn_ffn_layers)
-    model = model.to(device)
-    optimizer = build_optimizer(model, args)
     # one resident feature table per split, in split order: a batch is a slice of an index into it
     splits = (('train', train_idx), ('val', val_idx), ('test', test_idx))
     tables = None if features is None else {name: FeatureTable(features[idx], device) if len(idx) else None
                                             for name, idx in splits}
-    # a frozen encoder without dropout gives every molecule the same encoding at every step: computed once per
-    # split, the steps and the per-epoch scores then run the head alone (train.frozen_encodings)
-    enc_cache = None
-    if args.frzn_encoder and a.dropout == 0 and not a.no_encoding_cache and _predict_head(model.eval()) is not None:
-        enc_cache = {name: frozen_encodings(model, [graphs[i] for i in idx], a.batch_size) for name, idx in splits}
-    scheduler = NoamLR(optimizer, warmup_epochs=[a.warmup_epochs], total_epochs=[a.epochs],
-                       steps_per_epoch=len(train_idx) // a.batch_size, init_lr=[a.init_lr], max_lr=[a.max_lr],
-                       final_lr=[a.final_lr])
     loss_func = get_loss_func(a.dataset_type, a.alternative_loss_function)
 
     def batch_targets(pos):
         return train_targets[pos] if spectra else [train_targets[p] for p in pos]
 
-    def run_predict(name, idx):
+    def run_predict(model, enc_cache, name, idx):
         return predict(model, graphs, idx, a.batch_size, scaler, enc_cache and enc_cache[name],
                        tables and tables[name], None if row_mask is None else row_mask[idx])
-    sampler = Random(a.seed)
-    log_path = os.path.join(a.save_dir, 'train_val_loss_log.csv')
-    best = math.inf if minimize else -math.inf
-    best_epoch = 0
-    with open(log_path, 'w', newline='') as f:
-        w = csv.writer(f)
-        w.writerow(['epoch', 'train_loss'] + [f'train_avg_{m}' for m in metrics] + [f'val_avg_{m}' for m in metrics])
-        for epoch in range(a.epochs):
-            order = list(range(len(train_idx)))
-            sampler.shuffle(order)
-            losses = []
-            # the epoch's order as one validated index upload; every step takes a slice of it
-            findex = tables['train'].index(order) if tables is not None and order else None
-            for s in range(0, len(order), a.batch_size):
-                pos = order[s:s + a.batch_size]
-                feats = None if findex is None else findex[s:s + a.batch_size]
-                if enc_cache is not None:
-                    rows = enc_cache['train'][torch.as_tensor(pos, device=device)]
-                    loss = train_step(model, None, batch_targets(pos), loss_func, optimizer, scheduler,
-                                      a.dataset_type, features_batch=feats, grad_clip=a.grad_clip, encodings=rows)
-                else:
-                    g = BatchMolGraph([graphs[train_idx[p]] for p in pos])
-                    loss = train_step(model, [g], batch_targets(pos), loss_func, optimizer, scheduler,
-                                      a.dataset_type, features_batch=feats, grad_clip=a.grad_clip)
-                losses.append(float(loss))
-            val_scores = evaluate_predictions(run_predict('val', val_idx),
-                                              [targets[i] for i in val_idx], num_tasks, metrics, a.dataset_type)
-            tr_scores = evaluate_predictions(run_predict('train', train_idx),
-                                             [targets[i] for i in train_idx], num_tasks, metrics, a.dataset_type)
-            w.writerow([epoch, float(np.mean(losses)) if losses else float('nan')] +
-                       [float(np.nanmean(tr_scores[m])) if tr_scores[m] else float('nan') for m in metrics] +
-                       [float(np.nanmean(val_scores[m])) if val_scores[m] else float('nan') for m in metrics])
-            save_checkpoint(os.path.join(a.save_dir, 'model.pt'), model, scaler, features_scaler, args)
-            v = float(np.nanmean(val_scores[metric])) if val_scores[metric] else float('nan')
-            if (minimize and v < best) or (not minimize and v > best) or (epoch == 0 and math.isnan(v)):
-                best, best_epoch = v, epoch
-                save_checkpoint(os.path.join(a.save_dir, 'best_model.pt'), model, scaler, features_scaler, args)
-    ckpt = torch.load(os.path.join(a.save_dir, 'best_model.pt'), map_location=device, weights_only=True)
-    model.load_state_dict(ckpt['state_dict'])
+    sampler = Random(a.seed)  # (one stream of shuffles for the run: an ensemble's later models continue it)
+
+    def train_model(save_dir):
+        """One model, trained into ``save_dir`` (``model.pt``, ``best_model.pt``, ``train_val_loss_log.csv``):
+        (the model with its best weights, its cached encodings or None, the best epoch)."""
+        model = MoleculeModel(args)
+        initialize_weights(model)
+        if a.checkpoint_frzn is not None:
+            load_frzn_checkpoint(model, a.checkpoint_frzn)
+        apply_freezing(model, a.frzn_encoder, a.frzn_ffn_layers)
+        model = model.to(device)
+        optimizer = build_optimizer(model, args)
+        # a frozen encoder without dropout gives every molecule the same encoding at every step: computed once
+        # per split, the steps and the per-epoch scores then run the head alone (train.frozen_encodings)
+        enc_cache = None
+        if args.frzn_encoder and a.dropout == 0 and not a.no_encoding_cache and \
+                _predict_head(model.eval()) is not None:
+            enc_cache = {name: frozen_encodings(model, [graphs[i] for i in idx], a.batch_size)
+                         for name, idx in splits}
+        scheduler = NoamLR(optimizer, warmup_epochs=[a.warmup_epochs], total_epochs=[a.epochs],
+                           steps_per_epoch=len(train_idx) // a.batch_size, init_lr=[a.init_lr], max_lr=[a.max_lr],
+                           final_lr=[a.final_lr])
+        log_path = os.path.join(save_dir, 'train_val_loss_log.csv')
+        best = math.inf if minimize else -math.inf
+        best_epoch = 0
+        with open(log_path, 'w', newline='') as f:
+            w = csv.writer(f)
+            w.writerow(['epoch', 'train_loss'] + [f'train_avg_{m}' for m in metrics] +
+                       [f'val_avg_{m}' for m in metrics])
+            for epoch in range(a.epochs):
+                order = list(range(len(train_idx)))
+                sampler.shuffle(order)
+                losses = []
+                # the epoch's order as one validated index upload; every step takes a slice of it
+                findex = tables['train'].index(order) if tables is not None and order else None
+                for s in range(0, len(order), a.batch_size):
+                    pos = order[s:s + a.batch_size]
+                    feats = None if findex is None else findex[s:s + a.batch_size]
+                    if enc_cache is not None:
+                        rows = enc_cache['train'][torch.as_tensor(pos, device=device)]
+                        loss = train_step(model, None, batch_targets(pos), loss_func, optimizer, scheduler,
+                                          a.dataset_type, features_batch=feats, grad_clip=a.grad_clip,
+                                          encodings=rows)
+                    else:
+                        g = BatchMolGraph([graphs[train_idx[p]] for p in pos])
+                        loss = train_step(model, [g], batch_targets(pos), loss_func, optimizer, scheduler,
+                                          a.dataset_type, features_batch=feats, grad_clip=a.grad_clip)
+                    losses.append(float(loss))
+                val_scores = evaluate_predictions(run_predict(model, enc_cache, 'val', val_idx),
+                                                  [targets[i] for i in val_idx], num_tasks, metrics, a.dataset_type)
+                tr_scores = evaluate_predictions(run_predict(model, enc_cache, 'train', train_idx),
+                                                 [targets[i] for i in train_idx], num_tasks, metrics,
+                                                 a.dataset_type)
+                w.writerow([epoch, float(np.mean(losses)) if losses else float('nan')] +
+                           [float(np.nanmean(tr_scores[m])) if tr_scores[m] else float('nan') for m in metrics] +
+                           [float(np.nanmean(val_scores[m])) if val_scores[m] else float('nan') for m in metrics])
+                save_checkpoint(os.path.join(save_dir, 'model.pt'), model, scaler, features_scaler, args)
+                v = float(np.nanmean(val_scores[metric])) if val_scores[metric] else float('nan')
+                if (minimize and v < best) or (not minimize and v > best) or (epoch == 0 and math.isnan(v)):
+                    best, best_epoch = v, epoch
+                    save_checkpoint(os.path.join(save_dir, 'best_model.pt'), model, scaler, features_scaler, args)
+        ckpt = torch.load(os.path.join(save_dir, 'best_model.pt'), map_location=device, weights_only=True)
+        model.load_state_dict(ckpt['state_dict'])
+        return model, enc_cache, best_epoch
+
     test_targets = [targets[i] for i in test_idx]
-    test_preds = run_predict('test', test_idx)
+    if a.ensemble_size == 1:
+        model, enc_cache, best_epoch = train_model(a.save_dir)
+        test_preds = run_predict(model, enc_cache, 'test', test_idx)
+    else:
+        # run_training.py:208-499: model k trains into save_dir/model_k; every model's test predictions are folded
+        # into one accumulator on the device, and the top-level scores and predictions are the ensemble's
+        from .ensemble import EnsembleAccumulator, accumulate_model, make_batches
+        width = num_tasks * (a.multiclass_num_classes if multiclass else 1)
+        acc = EnsembleAccumulator(len(test_idx), width, device, keep=True, n_models=a.ensemble_size)
+        test_batches = make_batches([graphs[i] for i in test_idx], a.batch_size)
+        test_mask = None if row_mask is None or not len(test_idx) else \
+            torch.from_numpy(np.ascontiguousarray(row_mask[test_idx])).to(device)
+        best_epoch = []
+        for k in range(a.ensemble_size):
+            model_dir = os.path.join(a.save_dir, f'model_{k}')
+            os.makedirs(model_dir, exist_ok=True)
+            model, _, epoch = train_model(model_dir)
+            best_epoch.append(epoch)
+            if len(test_idx):
+                accumulate_model(acc, k, model, test_batches, scaler, tables and tables['test'], test_mask)
+            del model
+        each = acc.individual().cpu().numpy() if len(test_idx) else np.zeros((a.ensemble_size, 0, width))
+        mean = acc.mean().cpu().numpy() if len(test_idx) else np.zeros((0, width))
+        for k in range(a.ensemble_size):  # each model's own scores (run_training.py:440-469)
+            own = evaluate_predictions(prediction_rows(each[k], a.dataset_type, a.multiclass_num_classes),
+                                       test_targets, num_tasks, metrics, a.dataset_type)
+            with open(os.path.join(a.save_dir, f'model_{k}', 'test_scores.json'), 'w') as f:
+                json.dump(own, f, indent=4, sort_keys=True)
+        test_preds = prediction_rows(mean, a.dataset_type, a.multiclass_num_classes)
     scores = evaluate_predictions(test_preds, test_targets, num_tasks, metrics, a.dataset_type)
     with open(os.path.join(a.save_dir, 'test_scores.json'), 'w') as f:
         json.dump(scores, f, indent=4, sort_keys=True)
@@ -678,10 +728,208 @@ def run_training(a: argparse.Namespace) -> Dict[str, list]:
     return scores
 
 
+def prediction_rows(preds: np.ndarray, dataset_type: str, num_classes: int = 1) -> list:
+    """A float64 ``[N][W]`` array of predictions as the rows ``predict`` returns: lists of floats, multiclass as
+    ``[tasks][classes]`` per row, a spectrum's excluded (NaN) positions as None."""
+    preds = np.asarray(preds, dtype=np.float64)
+    if dataset_type == 'multiclass':
+        return preds.reshape(len(preds), -1, num_classes).tolist()
+    if dataset_type == 'spectra':
+        return [[None if math.isnan(v) else v for v in row] for row in preds.tolist()]
+    return preds.tolist()
+
+
 def chemprop_train(argv=None) -> Dict[str, list]:
     """Entry point (setup.py:39 ``chemprop_train`` in the reference)."""
     return run_training(parse_args(argv, spectra=True))
 
 
+def parse_predict_args(argv=None) -> argparse.Namespace:
+    """The arguments of ``chemprop_predict`` (args.py PredictArgs).  Exactly one of ``--checkpoint_dir``,
+    ``--checkpoint_path`` and ``--checkpoint_paths`` names the models (``ValueError`` otherwise)."""
+    ap = argparse.ArgumentParser(prog='chemprop_predict',
+                                 description='Predictions of a checkpoint, or of an ensemble of checkpoints.')
+    ap.add_argument('--test_path', required=True, help='CSV with a header; the first column holds the SMILES')
+    ap.add_argument('--graphs_path', required=True, help='pre-featurised MolGraph records, one per CSV row')
+    ap.add_argument('--preds_path', required=True, help='the CSV to write')
+    ap.add_argument('--checkpoint_dir', default=None,
+                    help='every best_model.pt below this directory if there is one, else every .pt file')
+    ap.add_argument('--checkpoint_path', default=None)
+    ap.add_argument('--checkpoint_paths', nargs='+', default=None)
+    ap.add_argument('--features_path', nargs='+', default=None,
+                    help='the molecule features the models were trained with, one row per CSV row')
+    ap.add_argument('--phase_features_path', default=None)
+    ap.add_argument('--no_features_scaling', action='store_true',
+                    help='feed the features as they are instead of through each checkpoint\'s features scaler')
+    ap.add_argument('--batch_size', type=int, default=50)
+    ap.add_argument('--gpu', type=int, default=0)
+    ap.add_argument('--ensemble_variance', action='store_true',
+                    help='also write the spread of the ensemble: the variance per task, the pairwise SID for spectra')
+    ap.add_argument('--individual_ensemble_predictions', action='store_true',
+                    help='also write every model\'s own predictions')
+    ap.add_argument('--drop_extra_columns', action='store_true',
+                    help='keep only the SMILES column of the input next to the predictions')
+    a = ap.parse_args(argv)
+    given = [x is not None for x in (a.checkpoint_dir, a.checkpoint_path, a.checkpoint_paths)]
+    if sum(given) != 1:
+        raise ValueError('give exactly one of --checkpoint_dir, --checkpoint_path and --checkpoint_paths')
+    if a.batch_size < 1:
+        raise ValueError('--batch_size must be at least 1')
+    return a
+
+
+def find_checkpoints(checkpoint_dir: str) -> List[str]:
+    """``--checkpoint_dir``: every ``best_model.pt`` below the directory if there is one, else every ``*.pt``,
+    sorted by path.  (The reference takes every ``.pt``, args.py:34-47; this package writes ``model.pt``, the last
+    epoch, next to ``best_model.pt``, and an ensemble is made of the best ones.)  ``ValueError`` without any."""
+    found = sorted(os.path.join(root, f) for root, _, files in os.walk(checkpoint_dir) for f in files
+                   if f.endswith('.pt'))
+    best = [p for p in found if os.path.basename(p) == 'best_model.pt']
+    if not found:
+        raise ValueError(f'no checkpoint (.pt file) below {checkpoint_dir}')
+    return best or found
+
+
+def checkpoint_paths_of(a: argparse.Namespace) -> List[str]:
+    if a.checkpoint_dir is not None:
+        return find_checkpoints(a.checkpoint_dir)
+    return [a.checkpoint_path] if a.checkpoint_path is not None else list(a.checkpoint_paths)
+
+
+def update_prediction_args(paths: List[str]) -> Dict[str, object]:
+    """What the checkpoints decide about a prediction run (make_predictions.py ``update_prediction_args``): the
+    first checkpoint's dataset type, task names (``task_0 ..`` when an older checkpoint holds none), class count,
+    spectra phase-mask path and ``polymer``.  ``ValueError`` when a later checkpoint disagrees on the dataset type
+    or the output width, or a file holds no ``args``."""
+    out = None
+    for k, path in enumerate(paths):
+        state = torch.load(path, map_location='cpu', weights_only=True)
+        if not isinstance(state, dict) or not isinstance(state.get('args'), dict):
+            raise ValueError(f'{path} is not a checkpoint with its training args')
+        t = state['args']
+        dataset_type = t.get('dataset_type', 'regression')
+        num_tasks = int(t.get('num_tasks', 1))
+        classes = int(t.get('multiclass_num_classes', 3)) if dataset_type == 'multiclass' else 1
+        if out is None:
+            names = t.get('task_names')
+            if not names or len(names) != num_tasks:
+                names = [f'task_{i}' for i in range(num_tasks)]
+            out = {'dataset_type': dataset_type, 'num_tasks': num_tasks, 'multiclass_num_classes': classes,
+                   'task_names': list(names), 'spectra_phase_mask_path': t.get('spectra_phase_mask_path'),
+                   'polymer': bool(t.get('polymer', False)), 'width': num_tasks * classes}
+        elif dataset_type != out['dataset_type'] or num_tasks * classes != out['width']:
+            raise ValueError(f'{path} ({dataset_type}, {num_tasks * classes} outputs) does not fit the ensemble\'s '
+                             f'first checkpoint {paths[0]} ({out["dataset_type"]}, {out["width"]} outputs)')
+    if out is None:
+        raise ValueError('no checkpoint given')
+    return out
+
+
+def write_predictions(path: str, header: List[str], rows: List[List[str]], task_names: List[str], mean,
+                      dataset_type: str = 'regression', num_classes: int = 1, spread=None, individual=None,
+                      drop_extra_columns: bool = False) -> List[str]:
+    """The predictions CSV (make_predictions.py:211-263); returns its header.  ``header`` / ``rows``: the input
+    CSV; ``mean`` ``[N][W]``, ``spread`` ``[N][W]`` (spectra: the pairwise SID ``[N]``) or None, ``individual``
+    ``[M][N][W]`` or None.  Columns: the input row's (``drop_extra_columns``: its first, the SMILES), one per task
+    (multiclass: ``<task>_class_<i>``), then ``<task>_model_<k>`` task by task, then ``<task>_epi_unc`` per task
+    (spectra: one ``epi_unc``); a prediction column named like a kept input column (the target column of a
+    training CSV) replaces it where it stands, as the reference's per-row dict does.  NaN cells (a spectrum's excluded positions) are written empty, as
+    ``chemprop_train`` writes them in ``test_preds.csv``."""
+    mean = np.asarray(mean, dtype=np.float64)
+    mean = mean.reshape(len(mean), -1)
+    names = [f'{t}_class_{i}' for t in task_names for i in range(num_classes)] if dataset_type == 'multiclass' \
+        else list(task_names)
+    if len(rows) != len(mean) or mean.shape[1] != len(names):
+        raise ValueError(f'predictions of shape {mean.shape} for {len(rows)} rows and {len(names)} columns')
+    spectra = dataset_type == 'spectra'
+    if individual is not None:
+        individual = np.asarray(individual, dtype=np.float64).reshape(-1, len(mean), len(names))
+    if spread is not None:
+        spread = np.asarray(spread, dtype=np.float64).reshape((len(mean),) if spectra else mean.shape)
+    keep = 1 if drop_extra_columns else len(header)
+    added = list(names)
+    if individual is not None:
+        added += [f'{n}_model_{k}' for n in names for k in range(len(individual))]
+    if spread is not None:
+        added += ['epi_unc'] if spectra else [f'{n}_epi_unc' for n in names]
+    # the reference fills a dict per row: a prediction column named like an input column takes its place
+    out_header = list(header[:keep])
+    slot = []
+    for name in added:
+        if name not in out_header:
+            out_header.append(name)
+        slot.append(out_header.index(name))
+
+    def cells(values):
+        return ['' if math.isnan(v) else v for v in values]
+    parent = os.path.dirname(path)
+    if parent:
+        os.makedirs(parent, exist_ok=True)
+    with open(path, 'w', newline='') as f:
+        w = csv.writer(f)
+        w.writerow(out_header)
+        for n, row in enumerate(rows):
+            values = cells(mean[n].tolist())
+            if individual is not None:
+                values += cells(individual[:, n, :].T.reshape(-1).tolist())
+            if spread is not None:
+                values += cells([float(spread[n])] if spectra else spread[n].tolist())
+            line = (list(row) + [''] * len(out_header))[:keep] + [''] * (len(out_header) - keep)
+            for at, v in zip(slot, values):
+                line[at] = v
+            w.writerow(line)
+    return out_header
+
+
+def check_polymer_rows(smiles: List[str], graphs) -> None:
+    """Every row a well-formed polymer string whose degree of polymerisation is its graph's (data.py:695-703,
+    featurization.py:335-364)."""
+    for s, g in zip(smiles, graphs):
+        _, _, rules = split_polymer_string(s)
+        if rules:
+            _, deg = parse_polymer_rules(rules)
+            if not np.isclose(deg, g.degree_of_polym, rtol=1e-6):
+                raise ValueError(f'graph degree_of_polym {g.degree_of_polym} != 1 + log10(Xn) = {deg} for {s}')
+
+
+def make_predictions(a: argparse.Namespace):
+    """make_predictions.py:272-372 for this package's checkpoints: the ensemble's predictions of ``--test_path``
+    written to ``--preds_path``; returns the mean predictions ``[N][W]`` (float64)."""
+    from .ensemble import predict_ensemble
+    paths = checkpoint_paths_of(a)
+    if len(paths) > ENSEMBLE_MAX_MODELS:
+        raise ValueError(f'{len(paths)} checkpoints (an ensemble holds at most {ENSEMBLE_MAX_MODELS})')
+    info = update_prediction_args(paths)
+    with open(a.test_path) as f:
+        table = list(csv.reader(f))
+    header, rows = table[0], [r for r in table[1:] if r]
+    graphs = load_graphs(a.graphs_path)
+    if len(graphs) != len(rows):
+        raise ValueError(f'{a.graphs_path} holds {len(graphs)} graphs for {len(rows)} CSV rows')
+    if info['polymer']:
+        check_polymer_rows([r[0] for r in rows], graphs)
+    features = load_input_features(a.features_path, len(rows)) if a.features_path else None
+    phase_features = phase_mask = None
+    if a.phase_features_path is not None:
+        phase_features = load_phase_features(a.phase_features_path, len(rows))
+    if info['dataset_type'] == 'spectra' and info['spectra_phase_mask_path'] is not None:
+        phase_mask = load_phase_mask(info['spectra_phase_mask_path'])
+    mean, spread, individual = predict_ensemble(
+        paths, graphs, a.batch_size, features=features, phase_features=phase_features, phase_mask=phase_mask,
+        variance=a.ensemble_variance, individual=a.individual_ensemble_predictions,
+        device=torch.device('cuda', a.gpu), features_scaling=not a.no_features_scaling)
+    write_predictions(a.preds_path, header, rows, info['task_names'], mean, info['dataset_type'],
+                      info['multiclass_num_classes'], spread, individual, a.drop_extra_columns)
+    return mean
+
+
+def chemprop_predict(argv=None):
+    """Entry point (setup.py:40 ``chemprop_predict`` in the reference)."""
+    return make_predictions(parse_predict_args(argv))
+
+
 if __name__ == '__main__':
-    print(json.dumps(chemprop_train(sys.argv[1:])))
+    if sys.argv[1:2] == ['predict']:  # python -m chemprop_amd.cli predict --test_path ...
+        chemprop_predict(sys.argv[2:])
+    else:
+        print(json.dumps(chemprop_train(sys.argv[1:])))

@@ -1,0 +1,297 @@
+"""Ensembles on the device (make_predictions.py:129-201): the mean, the variance and the individual predictions
+of M models, and the pairwise SID of an ensemble of spectra (``roundrobin_sid``, spectra_utils.py:211-241).
+
+The reference sums each model's fp32 predictions into a numpy float64 array on the host, one copy per batch
+and model.  Here a model's predictions stay where the head wrote them: ``EnsembleAccumulator.add`` folds a
+batch into float64 running statistics in one ``wdmpnn_ensemble_add`` launch (Welford's update, with the model's
+own inverse target scaling applied in double as ``scaler.py`` does), and the results leave the device once,
+after the last model.  ``predict_ensemble`` is the loop around it: per model, the batches in groups of eight
+through ``MPNEncoder.forward_many``, ``join_features`` for a model with input features, the native prediction
+head, the accumulator.
+"""
+from __future__ import annotations
+
+import ctypes
+from typing import Optional, Sequence
+
+import numpy as np
+import torch
+
+from . import _native
+from .features import FeatureTable, join_features
+from .featurization import BatchMolGraph
+from .spectra_utils import phase_row_mask
+
+
+class EnsembleAccumulator:
+    """Float64 running statistics of an ensemble's predictions for a data set of ``n_rows`` rows and ``width``
+    cells per row (tasks, spectrum positions, or tasks x classes taken flat), on ``device``.
+
+    ``variance``: also hold Welford's m2.  ``keep``: also hold every model's own predictions, one ``[n_rows][width]``
+    slab per model (``n_models`` slabs: the count is then needed up front); ``individual`` and ``roundrobin_sid``
+    read them.  Nothing is zeroed: model 0's ``add`` initialises the rows it covers, so every row must get its
+    models in the order 0, 1, 2, ...; the order is checked on the host (``ValueError``), the kernel trusts it."""
+
+    def __init__(self, n_rows: int, width: int, device, variance: bool = False, keep: bool = False,
+                 n_models: Optional[int] = None):
+        if n_rows < 0 or width < 1:
+            raise ValueError(f'EnsembleAccumulator: {n_rows} rows of width {width}')
+        if keep and (n_models is None or not 1 <= n_models <= _native.ENSEMBLE_MAX_MODELS):
+            raise ValueError(f'EnsembleAccumulator(keep=True) needs n_models in 1 .. {_native.ENSEMBLE_MAX_MODELS} '
+                             f'(got {n_models})')
+        self.n_rows, self.width, self.device = int(n_rows), int(width), torch.device(device)
+        self.n_models = n_models
+
+        def buf(*shape):
+            return torch.empty(shape, dtype=torch.float64, device=self.device)
+        self._mean = buf(n_rows, width)
+        self._m2 = buf(n_rows, width) if variance else None
+        self._slabs = buf(n_models, n_rows, width) if keep else None
+        self._count = np.zeros(n_rows, dtype=np.int64)  # models folded into each row so far (host bookkeeping)
+        self._scales = {}
+
+    def _scale(self, scaler):
+        """(means, stds) of ``scaler`` as float64 device tensors, uploaded once per scaler."""
+        hit = self._scales.get(id(scaler))
+        if hit is None:
+            means = np.ascontiguousarray(np.asarray(scaler.means, dtype=np.float64).reshape(-1))
+            stds = np.ascontiguousarray(np.asarray(scaler.stds, dtype=np.float64).reshape(-1))
+            if means.shape != (self.width,) or stds.shape != (self.width,):
+                raise ValueError(f'a scaler of {means.shape[0]} means and {stds.shape[0]} stds for predictions of '
+                                 f'width {self.width}')
+            hit = (scaler, torch.from_numpy(means).to(self.device), torch.from_numpy(stds).to(self.device))
+            self._scales[id(scaler)] = hit
+        return hit[1], hit[2]
+
+    def add(self, pred: torch.Tensor, row0: int, k: int, scaler=None) -> None:
+        """Fold model ``k``'s predictions ``pred`` (float32 on the device, ``[B][width]`` or ``[B][tasks][classes]``)
+        for rows ``row0 .. row0 + B`` into the statistics: one launch, no host sync.  ``scaler``: the model's
+        target scaler (``means`` / ``stds`` of length ``width``); the predictions are inverse-scaled in double."""
+        if not torch.is_tensor(pred) or pred.dtype != torch.float32 or pred.device != self._mean.device or \
+                pred.dim() < 2:
+            raise ValueError('EnsembleAccumulator.add expects float32 predictions [B][width] on the accumulator\'s '
+                             'device')
+        pred = pred.detach().reshape(pred.shape[0], -1).contiguous()
+        B = int(pred.shape[0])
+        if pred.shape[1] != self.width:
+            raise ValueError(f'predictions of width {pred.shape[1]} for an accumulator of width {self.width}')
+        if row0 < 0 or row0 + B > self.n_rows:
+            raise ValueError(f'rows {row0} .. {row0 + B} outside the accumulator\'s {self.n_rows} rows')
+        if not 0 <= k < _native.ENSEMBLE_MAX_MODELS or (self._slabs is not None and k >= self.n_models):
+            raise ValueError(f'model {k} of an ensemble of at most '
+                             f'{self.n_models if self._slabs is not None else _native.ENSEMBLE_MAX_MODELS}')
+        seen = self._count[row0:row0 + B]
+        if B and not (seen == k).all():
+            raise ValueError(f'model {k} for rows {row0} .. {row0 + B}, which hold {int(seen.min())} to '
+                             f'{int(seen.max())} models: every row takes its models once each, in order')
+        e = _native.WdEnsembleAdd()
+        e.pred, e.ld_pred, e.B, e.W, e.k, e.row0 = pred.data_ptr(), self.width, B, self.width, k, row0
+        if scaler is not None:
+            means, stds = self._scale(scaler)
+            e.scale_mean, e.scale_std = means.data_ptr(), stds.data_ptr()
+        e.mean, e.m2, e.ld_acc = self._mean.data_ptr(), _native.ptr(self._m2), self.width
+        e.keep = self._slabs[k].data_ptr() if self._slabs is not None else None
+        _native.check(_native.lib().wdmpnn_ensemble_add(ctypes.byref(e), _native.current_stream(self.device)),
+                      'ensemble add')
+        self._count[row0:row0 + B] = k + 1
+
+    def models(self) -> int:
+        """The number of models every row holds (``ValueError`` while the rows differ or hold none)."""
+        if self.n_rows == 0:
+            return int(self.n_models or 0)
+        lo, hi = int(self._count.min()), int(self._count.max())
+        if lo != hi or lo < 1:
+            raise ValueError(f'the rows hold between {lo} and {hi} models: finish every model over every row first')
+        return lo
+
+    def mean(self) -> torch.Tensor:
+        self.models()
+        return self._mean
+
+    def variance(self) -> torch.Tensor:
+        """``m2 / M``: the population variance, as ``np.var`` over the models."""
+        if self._m2 is None:
+            raise ValueError('EnsembleAccumulator(variance=True) holds the variance')
+        return self._m2 / max(self.models(), 1)
+
+    def individual(self) -> torch.Tensor:
+        """Every model's own predictions, ``[M][n_rows][width]``."""
+        if self._slabs is None:
+            raise ValueError('EnsembleAccumulator(keep=True) holds the individual predictions')
+        return self._slabs[:self.models()] if self.n_rows else self._slabs
+
+    def roundrobin_sid(self, threshold: Optional[float] = None) -> torch.Tensor:
+        """The pairwise SID of the kept spectra per row (``wdmpnn_ensemble_sid``), float64 ``[n_rows]``; NaN for
+        an ensemble of one model."""
+        if self._slabs is None:
+            raise ValueError('EnsembleAccumulator(keep=True) holds the spectra the pairwise SID compares')
+        M = self.models()
+        out = torch.empty(self.n_rows, dtype=torch.float64, device=self.device)
+        if self.n_rows == 0:
+            return out
+        s = _native.WdEnsembleSid()
+        s.preds, s.model_stride, s.ld = self._slabs.data_ptr(), self.n_rows * self.width, self.width
+        s.M, s.N, s.T = M, self.n_rows, self.width
+        s.threshold, s.out = 0.0 if threshold is None else float(threshold), out.data_ptr()
+        _native.check(_native.lib().wdmpnn_ensemble_sid(ctypes.byref(s), _native.current_stream(self.device)),
+                      'ensemble sid')
+        return out
+
+
+def make_batches(graphs: Sequence, batch_size: int) -> list:
+    """The data set as ``BatchMolGraph`` s of ``batch_size`` molecules, in order."""
+    if batch_size < 1:
+        raise ValueError('batch_size must be at least 1')
+    return [BatchMolGraph(list(graphs[s:s + batch_size])) for s in range(0, len(graphs), batch_size)]
+
+
+def _fallback_predict(model, batch, feats, mask) -> torch.Tensor:
+    """A model whose FFN the native prediction heads refuse: its own forward (a spectra model's output
+    normalised per row with torch ops, as ``head_predict(normalize=True)`` does it natively)."""
+    out = model([batch], feats)
+    if getattr(model, 'spectra', False):
+        m = torch.ones_like(out, dtype=torch.bool) if mask is None else mask.bool()
+        s = torch.where(m, out, torch.zeros_like(out))
+        out = torch.where(m, s / s.sum(dim=1, keepdim=True), torch.full_like(out, float('nan')))
+    return out
+
+
+def accumulate_model(acc: EnsembleAccumulator, k: int, model, batches: Sequence[BatchMolGraph], scaler=None,
+                     table: Optional[FeatureTable] = None, row_mask: Optional[torch.Tensor] = None) -> None:
+    """Model ``k``'s predictions of ``batches`` (row order = batch order) into ``acc``.  ``table``: the model's
+    input features of every row, as the model sees them; ``row_mask``: a spectra model's included positions,
+    bool or uint8 ``[rows][T]`` on the device.  No host sync: the batches run in groups of up to eight through
+    ``forward_many``, then per batch ``join_features``, the native prediction head and ``acc.add``."""
+    from .train import _predict_head, head_predict
+    model.eval()
+    mpn = model.encoder
+    needs = bool(getattr(mpn, 'use_input_features', False))
+    if needs and table is None:
+        raise ValueError(f'model {k} takes input features and none were given')
+    if not needs and table is not None:
+        raise ValueError(f'model {k} takes no input features, but features were given')
+    sizes = [len(b.a_scope) for b in batches]
+    starts = np.cumsum([0] + sizes).tolist()
+    if starts[-1] != acc.n_rows or (table is not None and len(table) != acc.n_rows):
+        raise ValueError(f'{starts[-1]} molecules and {None if table is None else len(table)} feature rows for an '
+                         f'accumulator of {acc.n_rows} rows')
+    findex = table.index(range(acc.n_rows)) if table is not None and acc.n_rows else None
+    spectra = bool(getattr(model, 'spectra', False))
+    head = _predict_head(model)
+    many = head is not None and not mpn.features_only and len(mpn.encoder) == 1 and mpn.atom_descriptors is None
+    with torch.no_grad():
+        for g0 in range(0, len(batches), 8):
+            group = batches[g0:g0 + 8]
+            embs = mpn.encoder[0].forward_many(group) if many else [None] * len(group)
+            for j, emb in enumerate(embs):
+                r0, r1 = starts[g0 + j], starts[g0 + j + 1]
+                feats = None if findex is None else findex[r0:r1]
+                mask = None if row_mask is None or not spectra else row_mask[r0:r1]
+                if head is None:
+                    out = _fallback_predict(model, group[j], feats, mask)
+                else:
+                    if emb is None:
+                        x = mpn([group[j]], feats)
+                    else:
+                        x = emb if feats is None else join_features(emb, feats)
+                    out = head_predict(model, x, head, normalize=True, mask=mask) if spectra else \
+                        head_predict(model, x, head)
+                acc.add(out, r0, k, scaler)
+
+
+def _open_model(item, device):
+    """(model, data scaler, features scaler) of an ensemble member: a checkpoint path, a
+    ``(model, data_scaler, features_scaler)`` tuple, or a model alone (no scalers)."""
+    from . import cli
+    if isinstance(item, (str, bytes)) or hasattr(item, '__fspath__'):
+        path = str(item)
+        scalers = cli.load_scalers(path)
+        return cli.load_checkpoint(path, device), scalers[0], scalers[1]
+    if isinstance(item, (tuple, list)):
+        model, data_scaler, features_scaler = item
+        return model, data_scaler, features_scaler
+    return item, None, None
+
+
+def model_features(model, features, features_scaler, phase_features, k: int = 0) -> Optional[np.ndarray]:
+    """The input feature rows as model ``k`` sees them: the raw ``features`` through that model's own
+    ``features_scaler`` (NaN -> 0; as they are without one), then the phase features, unscaled, as
+    ``cli.run_training`` feeds them.  ``ValueError`` when the model needs features and gets none, gets features it
+    does not take, or gets another width than it was trained on."""
+    parts = []
+    if features is not None:
+        f = np.asarray(features, dtype=np.float64)
+        parts.append(features_scaler.transform(f) if features_scaler is not None else f)
+    if phase_features is not None:
+        parts.append(np.asarray(phase_features, dtype=np.float64))
+    needs = bool(getattr(model.encoder, 'use_input_features', False))
+    if not parts:
+        if needs:
+            raise ValueError(f'model {k} was trained with input features: give the same feature files to predict')
+        return None
+    if not needs:
+        raise ValueError(f'model {k} was trained without input features, but features were given')
+    rows = np.concatenate(parts, axis=1)
+    lin = next(m for m in model.ffn if isinstance(m, torch.nn.Linear))
+    width = lin.in_features - sum(e.hidden_size for e in getattr(model.encoder, 'encoder', ()))
+    if rows.shape[1] != width:
+        raise ValueError(f'model {k} was trained with {width} input features and {rows.shape[1]} were given')
+    return rows
+
+
+def predict_ensemble(checkpoints_or_models, graphs: Sequence, batch_size: int, features=None, phase_features=None,
+                     phase_mask=None, variance: bool = False, individual: bool = False, device=None,
+                     n_models: Optional[int] = None, features_scaling: bool = True):
+    """The ensemble's predictions of ``graphs`` (``MolGraph`` records, one per row): ``(mean, variance,
+    individual)`` as float64 numpy arrays, ``[N][W]``, ``[N][W]`` (for spectra models the per-row pairwise SID
+    ``[N]``; None without ``variance``) and ``[M][N][W]`` (None without ``individual``).  W is the flat output width:
+    tasks, spectrum positions, or tasks x classes.
+
+    ``checkpoints_or_models``: checkpoint paths, ``(model, data_scaler, features_scaler)`` tuples or models, handled
+    one after the other (a generator works; ``n_models`` is then needed when per-model slabs are kept).  Every
+    model is put in eval mode and sees its own feature table: the raw ``features`` ``[N][Ff]`` through its own
+    ``features_scaler`` (``features_scaling=False``: as they are), ``phase_features`` ``[N][phases]`` appended
+    unscaled.  Spectra predictions are normalised per row under the row's phase mask (``phase_mask``
+    ``[phases][T]``); excluded positions are NaN.  The predictions leave the device once, after the last model."""
+    device = torch.device('cuda', 0) if device is None else torch.device(device)
+    if n_models is None and hasattr(checkpoints_or_models, '__len__'):
+        n_models = len(checkpoints_or_models)
+    batches = make_batches(graphs, batch_size)
+    n = len(graphs)
+    acc = spectra = None
+    row_mask = None
+    k = -1
+    for k, item in enumerate(checkpoints_or_models):
+        model, data_scaler, features_scaler = _open_model(item, device)
+        model.eval()
+        is_spectra = bool(getattr(model, 'spectra', False))
+        width = int([m for m in model.ffn if isinstance(m, torch.nn.Linear)][-1].out_features)
+        if acc is None:
+            spectra = is_spectra
+            keep = individual or (variance and spectra)
+            if keep and n_models is None:
+                raise ValueError('predict_ensemble: pass n_models with a generator of models when the individual '
+                                 'predictions (or a spectra ensemble\'s spread) are wanted')
+            acc = EnsembleAccumulator(n, width, device, variance=variance and not spectra, keep=keep,
+                                      n_models=n_models)
+            if spectra and phase_features is not None and phase_mask is not None:
+                row_mask = torch.from_numpy(np.ascontiguousarray(phase_row_mask(phase_features, phase_mask))).to(device)
+                if tuple(row_mask.shape) != (n, width):
+                    raise ValueError(f'a phase mask of shape {tuple(row_mask.shape)} for {n} rows of {width} '
+                                     'spectrum positions')
+        elif is_spectra != spectra or width != acc.width:
+            raise ValueError(f'model {k} predicts {"spectra" if is_spectra else "values"} of width {width}; the '
+                             f'ensemble\'s first model {"spectra" if spectra else "values"} of width {acc.width}')
+        rows = model_features(model, features, features_scaler if features_scaling else None, phase_features, k)
+        table = None if rows is None else FeatureTable(rows, device)
+        accumulate_model(acc, k, model, batches, data_scaler, table, row_mask)
+        del model, table
+    if acc is None:
+        raise ValueError('predict_ensemble: no model given')
+    if n == 0:
+        return np.zeros((0, acc.width)), None, None
+    mean = acc.mean().cpu().numpy()
+    spread = None
+    if variance:
+        spread = (acc.roundrobin_sid() if spectra else acc.variance()).cpu().numpy()
+    return mean, spread, acc.individual().cpu().numpy() if individual else None

@@ -37,6 +37,7 @@
 #include "selfcheck.hpp"
 #include "small_fwd.hpp"
 #include "wdmpnn.h"
+#include "ensemble.hpp"
 
 using namespace wd;
 
@@ -1748,6 +1749,66 @@ int wdmpnn_join_rows(const WdJoin *j, void *stream) {
     A.units = units;
     hipLaunchKernelGGL(join_rows_kernel, dim3(ew_blocks((size_t)j->B * units)), dim3(256), 0, (hipStream_t)stream, A);
     WD_CHECK_LAUNCH("join_rows");
+    return 0;
+}
+
+int wdmpnn_ensemble_add(const WdEnsembleAdd *e, void *stream) {
+    WD_KERNELS_OK();
+    if (!e) return fail(WD_ERR_ARG, "ensemble_add: null struct");
+    if (e->B < 0 || e->W <= 0 || e->ld_pred < e->W || e->ld_acc < e->W || e->row0 < 0 || e->k < 0)
+        return fail(WD_ERR_SHAPE, "ensemble_add: needs B >= 0, W > 0, ld_pred >= W, ld_acc >= W, row0 >= 0, k >= 0 "
+                    "(got B %d W %d ld_pred %d ld_acc %d row0 %lld k %d)", e->B, e->W, e->ld_pred, e->ld_acc,
+                    (long long)e->row0, e->k);
+    if (!e->scale_mean != !e->scale_std)
+        return fail(WD_ERR_SHAPE, "ensemble_add: scale_mean and scale_std come together or not at all");
+    if (e->k >= WD_ENSEMBLE_MAX_MODELS)
+        return fail(WD_ERR_UNSUPPORTED, "ensemble_add: model %d (at most %d models)", e->k, WD_ENSEMBLE_MAX_MODELS);
+    if (e->B == 0) return 0;
+    if (!e->pred || !e->mean) return fail(WD_ERR_ARG, "ensemble_add: null %s", !e->pred ? "pred" : "mean");
+    EnsembleAddArgs A{};
+    A.pred = e->pred;
+    A.scale_mean = e->scale_mean;
+    A.scale_std = e->scale_std;
+    A.mean = e->mean;
+    A.m2 = e->m2;
+    A.keep = e->keep;
+    A.row0 = e->row0;
+    A.B = e->B;
+    A.W = e->W;
+    A.ld_pred = e->ld_pred;
+    A.ld_acc = e->ld_acc;
+    A.k = e->k;
+    hipLaunchKernelGGL(ensemble_add_kernel, dim3(ew_blocks((size_t)e->B * e->W)), dim3(256), 0, (hipStream_t)stream, A);
+    WD_CHECK_LAUNCH("ensemble_add");
+    return 0;
+}
+
+int wdmpnn_ensemble_sid(const WdEnsembleSid *e, void *stream) {
+    WD_KERNELS_OK();
+    if (!e) return fail(WD_ERR_ARG, "ensemble_sid: null struct");
+    if (e->M < 1 || e->T < 1 || e->N < 0 || e->ld < e->T || e->model_stride < (int64_t)e->N * e->ld)
+        return fail(WD_ERR_SHAPE, "ensemble_sid: needs M >= 1, T >= 1, N >= 0, ld >= T, model_stride >= N ld "
+                    "(got M %d T %d N %d ld %d model_stride %lld)", e->M, e->T, e->N, e->ld, (long long)e->model_stride);
+    if (e->M > WD_ENSEMBLE_MAX_MODELS)
+        return fail(WD_ERR_UNSUPPORTED, "ensemble_sid: %d models (at most %d)", e->M, WD_ENSEMBLE_MAX_MODELS);
+    if (e->N == 0) return 0;
+    if (!e->preds || !e->out) return fail(WD_ERR_ARG, "ensemble_sid: null %s", !e->preds ? "preds" : "out");
+    EnsembleSidArgs A{};
+    A.preds = e->preds;
+    A.out = e->out;
+    A.model_stride = e->model_stride;
+    A.threshold = e->threshold;
+    A.ld = e->ld;
+    A.M = e->M;
+    A.T = e->T;
+    const dim3 grid(e->N), block(256);
+    const hipStream_t st = (hipStream_t)stream;
+    // the smallest unrolled model bound that holds M: the per-position values and logs stay in registers
+    if (e->M <= 4) hipLaunchKernelGGL(ensemble_sid_kernel<4>, grid, block, 0, st, A);
+    else if (e->M <= 8) hipLaunchKernelGGL(ensemble_sid_kernel<8>, grid, block, 0, st, A);
+    else if (e->M <= 16) hipLaunchKernelGGL(ensemble_sid_kernel<16>, grid, block, 0, st, A);
+    else hipLaunchKernelGGL(ensemble_sid_kernel<ENSEMBLE_MAX_MODELS>, grid, block, 0, st, A);
+    WD_CHECK_LAUNCH("ensemble_sid");
     return 0;
 }
 
