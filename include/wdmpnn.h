@@ -450,6 +450,91 @@ typedef struct WdEnsembleSid {
 } WdEnsembleSid;
 int wdmpnn_ensemble_sid(const WdEnsembleSid *e, void *stream);
 
+/* Scoring a split on the device (evaluate.py:11-77 over predict.py:10-68): the sums behind rmse, mse, mae, r2,
+ * cross_entropy and accuracy, the per-row SID / Wasserstein terms of spectra, and ROC AUC by counting, from the fp32
+ * predictions of the native prediction heads against a target table that stays on the device: double
+ * targets[N][ld_targets], NaN = missing, a multiclass entry = the class index.  Double precision throughout, every
+ * operation rounded on its own where the host code it replaces rounds; no atomics, fixed thread-to-element maps and
+ * reduction orders, plain vector stores.
+ *
+ * Add: folds the batch pred[B][tasks * classes] (rows row0 .. row0 + B of the split) into partials[tasks][WD_EVAL_SLOTS],
+ * which the caller zeroes once; one workgroup per task, a batch's terms reduced over a fixed tree and then added to
+ * the running partials, so launches on one stream are sequenced.  With `keep`, also stores the value v of every cell
+ * (present target or not) at keep[row0 + b][c], as float (keep_f32 != 0) or double.  Per present target t:
+ *   WD_EVAL_REGRESSION      v = (double)pred * scale_std[task] + scale_mean[task] (a rounded product, then a rounded
+ *                           sum; v = (double)pred without the scale pointers); e = v - t;
+ *                           slot 0 += e e, slot 1 += |e|
+ *   WD_EVAL_CLASSIFICATION  p = (double)pred, eps = 2^-52;
+ *                           slot 0 += -log(clip(p, eps, 1 - eps)) for t == 1, -log(clip(1 - p, eps, 1 - eps)) otherwise
+ *                           (sklearn's log_loss); slot 1 += [(p > 0.5) == (t == 1)]; slot 2 += [p == 0];
+ *                           slot 3 += [p == 1]
+ *   WD_EVAL_MULTICLASS      the task's `classes` probabilities p[.]: slot 0 += -log(clip(p[t], eps, 1 - eps));
+ *                           slot 1 += [first maximum of p[.] == t].  A present t must be an integer in
+ *                           [0, classes): the caller checks the table when it builds it.
+ * Refused before any launch: a NULL struct (WD_ERR_ARG); an unknown kind, B < 0, tasks < 1, classes < 1, classes != 1
+ * unless multiclass, ld_pred < tasks * classes, ld_targets < tasks, a keep with ld_keep < tasks * classes, row0 < 0,
+ * row0 + B > N, exactly one of the scale pointers, scale pointers for another kind than regression (WD_ERR_SHAPE);
+ * pred, targets or partials NULL with B > 0 (WD_ERR_ARG).  B == 0 is a no-op. */
+#define WD_EVAL_SLOTS 4
+#define WD_EVAL_REGRESSION 0
+#define WD_EVAL_CLASSIFICATION 1
+#define WD_EVAL_MULTICLASS 2
+typedef struct WdEvalAdd {
+    const float *pred;        /* [B][ld_pred], tasks * classes columns used          */
+    int32_t ld_pred, B, tasks, classes;
+    int32_t kind;             /* WD_EVAL_*                                           */
+    int32_t ld_targets;
+    int64_t row0, N;          /* the batch's first row; the rows of the split        */
+    const double *targets;    /* [N][ld_targets]                                     */
+    const double *scale_mean; /* [tasks] the target scaler (regression), or both NULL */
+    const double *scale_std;
+    double *partials;         /* [tasks][WD_EVAL_SLOTS]                              */
+    void *keep;               /* [N][ld_keep] float or double, or NULL               */
+    int32_t ld_keep, keep_f32;
+} WdEvalAdd;
+int wdmpnn_eval_add(const WdEvalAdd *e, void *stream);
+
+/* Spectra: one workgroup per row of the batch writes sid[row0 + b] and / or wasserstein[row0 + b] (either may be
+ * NULL), spectra_utils.py:42-83 / 117-159 per row.  pred arrives normalised, NaN where the row's phase excludes the
+ * position; a position counts where its target is present.  z = pred where present and not NaN, else 0; p = z / sum z;
+ *     sid         = sum over the present positions of p log(p / y) + y log(y / p)
+ *     wasserstein = sum over all positions t of |cumsum(y)_t - cumsum(p)_t|, a missing y as 0
+ * Each of the 256 threads takes a contiguous chunk of ceil(T / 256) positions; the chunk sums of p and y are scanned
+ * over LDS in index order, and a second pass forms the terms.  With `keep`, stores pred as it came.
+ * Refused before any launch: a NULL struct (WD_ERR_ARG); B < 0, T < 1, ld_pred < T, ld_targets < T, a keep with
+ * ld_keep < T, row0 < 0, row0 + B > N (WD_ERR_SHAPE); T > WD_HEAD_MAX_SPECTRUM (WD_ERR_UNSUPPORTED); pred or targets
+ * NULL, or both outputs NULL, with B > 0 (WD_ERR_ARG).  B == 0 is a no-op. */
+typedef struct WdEvalSpectra {
+    const float *pred;        /* [B][ld_pred]                                        */
+    int32_t ld_pred, B, T, ld_targets;
+    int64_t row0, N;
+    const double *targets;    /* [N][ld_targets]                                     */
+    double *sid;              /* [N], or NULL                                        */
+    double *wasserstein;      /* [N], or NULL                                        */
+    void *keep;               /* [N][ld_keep] float or double, or NULL               */
+    int32_t ld_keep, keep_f32;
+} WdEvalSpectra;
+int wdmpnn_eval_spectra(const WdEvalSpectra *e, void *stream);
+
+/* ROC AUC by counting, from the kept predictions preds[N][ld_preds] (float when preds_f32, else double; column =
+ * task) and the target table.  Grid (task, block of 256 rows): a thread holds one row i with t_i == 1 and streams
+ * every row j through LDS in tiles of 256, counting 2 [t_j == 0 and p_j < p_i] + [t_j == 0 and p_j == p_i]; a block
+ * reduction writes counts[task][block], blocks = ceil(N / 256).  The caller sums a task's integers and divides by
+ * 2 P Nneg (P rows with t == 1, Nneg with t == 0): a tie counts one half, as the trapezoid rule gives it, and
+ * integer sums do not depend on any order.
+ * Refused before any launch: a NULL struct (WD_ERR_ARG); N < 0, tasks < 1, ld_preds < tasks, ld_targets < tasks
+ * (WD_ERR_SHAPE); N > WD_EVAL_AUC_MAX_ROWS (WD_ERR_UNSUPPORTED: a count must fit 64 bits, and the work is
+ * quadratic) or tasks > 65535 (the grid's second dimension); preds, targets or counts NULL with N > 0 (WD_ERR_ARG).  N == 0 is a no-op. */
+#define WD_EVAL_AUC_MAX_ROWS (1 << 24)
+typedef struct WdEvalAuc {
+    const void *preds;        /* [N][ld_preds]                                       */
+    const double *targets;    /* [N][ld_targets]                                     */
+    int64_t N;
+    int32_t tasks, ld_preds, ld_targets, preds_f32;
+    int64_t *counts;          /* [tasks][ceil(N / 256)]                              */
+} WdEvalAuc;
+int wdmpnn_eval_auc(const WdEvalAuc *e, void *stream);
+
 /* One Adam / AdamW optimizer step (torch.optim.Adam / AdamW semantics without amsgrad: the optimizer
  * step of train/train.py:84, built by utils.py:295-310) over n tensors in one launch per 16 tensors.
  * Replaces torch's multi-tensor / fused Adam kernels; per element: g += wd p (AdamW: p -= lr wd p),

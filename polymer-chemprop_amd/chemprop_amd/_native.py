@@ -47,13 +47,16 @@ EXPORTED_SYMBOLS = ('wdmpnn_abi_version', 'wdmpnn_last_error', 'wdmpnn_workspace
                     'wdmpnn_head_stack_scratch_bytes', 'wdmpnn_head_stack', 'wdmpnn_head_stack_predict',
                     'wdmpnn_head_stack_partial', 'wdmpnn_head_spectra_scratch_bytes', 'wdmpnn_head_spectra',
                     'wdmpnn_head_spectra_predict', 'wdmpnn_join_rows', 'wdmpnn_ensemble_add',
-                    'wdmpnn_ensemble_sid')
+                    'wdmpnn_ensemble_sid', 'wdmpnn_eval_add', 'wdmpnn_eval_spectra', 'wdmpnn_eval_auc')
 HEAD_MAX_LAYERS = 6  # WD_HEAD_MAX_LAYERS
 HEAD_MAX_SPECTRUM = 8192  # WD_HEAD_MAX_SPECTRUM
 SPECTRA_ACTIVATIONS = {'exp': 0, 'softplus': 1}  # WdHeadSpectra.spectra_act
 SPECTRA_LOSSES = {'sid': 0, 'wasserstein': 1}  # WdHeadSpectra.loss_kind
 JOIN_MAX_SEGMENTS = 4  # WD_JOIN_MAX_SEGMENTS
 ENSEMBLE_MAX_MODELS = 32  # WD_ENSEMBLE_MAX_MODELS
+EVAL_SLOTS = 4  # WD_EVAL_SLOTS
+EVAL_KINDS = {'regression': 0, 'classification': 1, 'multiclass': 2}  # WD_EVAL_*
+EVAL_AUC_MAX_ROWS = 1 << 24  # WD_EVAL_AUC_MAX_ROWS
 
 
 class WdCsr(Structure):
@@ -195,6 +198,24 @@ class WdEnsembleSid(Structure):
                 ('T', c_int32), ('threshold', c_double), ('out', c_void_p)]
 
 
+class WdEvalAdd(Structure):
+    _fields_ = [('pred', c_void_p), ('ld_pred', c_int32), ('B', c_int32), ('tasks', c_int32), ('classes', c_int32),
+                ('kind', c_int32), ('ld_targets', c_int32), ('row0', c_int64), ('N', c_int64), ('targets', c_void_p),
+                ('scale_mean', c_void_p), ('scale_std', c_void_p), ('partials', c_void_p), ('keep', c_void_p),
+                ('ld_keep', c_int32), ('keep_f32', c_int32)]
+
+
+class WdEvalSpectra(Structure):
+    _fields_ = [('pred', c_void_p), ('ld_pred', c_int32), ('B', c_int32), ('T', c_int32), ('ld_targets', c_int32),
+                ('row0', c_int64), ('N', c_int64), ('targets', c_void_p), ('sid', c_void_p), ('wasserstein', c_void_p),
+                ('keep', c_void_p), ('ld_keep', c_int32), ('keep_f32', c_int32)]
+
+
+class WdEvalAuc(Structure):
+    _fields_ = [('preds', c_void_p), ('targets', c_void_p), ('N', c_int64), ('tasks', c_int32), ('ld_preds', c_int32),
+                ('ld_targets', c_int32), ('preds_f32', c_int32), ('counts', c_void_p)]
+
+
 def join_rows(out, segments, stream: int) -> None:
     """wdmpnn_join_rows into ``out`` (float32 device tensor ``[B][ld_out]``, row-major): ``segments`` are
     ``(src data pointer, ld, c0, w, index data pointer or 0)``.  Every index must have been range-checked by the
@@ -280,6 +301,9 @@ def lib() -> ctypes.CDLL:
     L.wdmpnn_join_rows.argtypes = [POINTER(WdJoin), c_void_p]
     L.wdmpnn_ensemble_add.argtypes = [POINTER(WdEnsembleAdd), c_void_p]
     L.wdmpnn_ensemble_sid.argtypes = [POINTER(WdEnsembleSid), c_void_p]
+    L.wdmpnn_eval_add.argtypes = [POINTER(WdEvalAdd), c_void_p]
+    L.wdmpnn_eval_spectra.argtypes = [POINTER(WdEvalSpectra), c_void_p]
+    L.wdmpnn_eval_auc.argtypes = [POINTER(WdEvalAuc), c_void_p]
     L.wdmpnn_forward_many.argtypes = [c_int32, POINTER(WdGraph), POINTER(WdParams), POINTER(WdConfig),
                                       POINTER(c_void_p), POINTER(c_size_t), POINTER(c_void_p), c_void_p]
     L.wdmpnn_feed_slot_bytes.argtypes = [c_int32, c_int32, c_int32, c_int32, POINTER(c_size_t), POINTER(c_size_t)]
@@ -308,7 +332,8 @@ def lib() -> ctypes.CDLL:
              'wdmpnn_feed_destroy', 'wdmpnn_adam_step_repack', 'wdmpnn_head_predict',
              'wdmpnn_head_stack_scratch_bytes', 'wdmpnn_head_stack', 'wdmpnn_head_stack_predict',
              'wdmpnn_head_stack_partial', 'wdmpnn_head_spectra_scratch_bytes', 'wdmpnn_head_spectra',
-             'wdmpnn_head_spectra_predict', 'wdmpnn_join_rows', 'wdmpnn_ensemble_add', 'wdmpnn_ensemble_sid'):
+             'wdmpnn_head_spectra_predict', 'wdmpnn_join_rows', 'wdmpnn_ensemble_add', 'wdmpnn_ensemble_sid',
+             'wdmpnn_eval_add', 'wdmpnn_eval_spectra', 'wdmpnn_eval_auc'):
         getattr(L, fn).restype = c_int
     v = L.wdmpnn_abi_version()
     if v != ABI_VERSION:

@@ -52,6 +52,7 @@ class TrainArgs:
     polymer: bool = False
     ensemble_size: int = 1                           # args.py:299 (models trained by one chemprop_train run)
     task_names: Optional[List[str]] = None           # args.py:439 (the target columns; chemprop_predict's header)
+    device_metrics: bool = False                     # (chemprop_train --device_metrics: evaluate.evaluate per epoch)
     # optimizer (args.py:397-407, utils.py:295-310)
     init_lr: float = 1e-4
     optimizer: str = 'adam'

@@ -42,7 +42,10 @@ restated here:
 * ``--ensemble_size M`` (run_training.py:208-499): M models, one after the other, each into ``save_dir/model_<k>/``
   with its own ``test_scores.json``; the seeds are set once, so model 0 is the model of a run without the flag and
   the later ones continue the random streams; every model's test predictions are folded into one
-  ``ensemble.EnsembleAccumulator`` on the device, and the top-level scores and ``test_preds.csv`` are the ensemble's.
+  ``ensemble.EnsembleAccumulator`` on the device, and the top-level scores and ``test_preds.csv`` are the ensemble's;
+* ``--device_metrics``: the per-epoch validation and training scores and a single model's test scores come from
+  ``evaluate.evaluate`` (resident targets, partial sums on the device) instead of ``predict`` +
+  ``evaluate_predictions``; the same files are written.
 
 ``chemprop_predict`` (``python -m chemprop_amd.cli predict --test_path CSV --graphs_path NPZ --preds_path OUT
 --checkpoint_dir D | --checkpoint_path P | --checkpoint_paths P ...``) is make_predictions.py's counterpart: the
@@ -515,6 +518,9 @@ def parse_args(argv=None, spectra: bool = False) -> argparse.Namespace:
     ap.add_argument('--ensemble_size', type=int, default=1,
                     help='train this many models, one after the other, into save_dir/model_<k>/; the test '
                          'predictions and scores are the ensemble\'s')
+    ap.add_argument('--device_metrics', action='store_true',
+                    help='score the validation, training and test splits on the device (evaluate.evaluate): the '
+                         'targets stay resident, the predictions are not copied to the host per batch')
     a = ap.parse_args(argv)
     if not 1 <= a.ensemble_size <= ENSEMBLE_MAX_MODELS:
         raise ValueError(f'--ensemble_size must be in 1 .. {ENSEMBLE_MAX_MODELS}')
@@ -586,7 +592,8 @@ def run_training(a: argparse.Namespace) -> Dict[str, list]:
                      no_features_scaling=bool(a.no_features_scaling),
                      use_input_features=features is not None,
                      features_size=0 if features is None else int(features.shape[1]),
-                     polymer=bool(a.polymer), ensemble_size=a.ensemble_size, task_names=list(header[1:]))
+                     polymer=bool(a.polymer), ensemble_size=a.ensemble_size, task_names=list(header[1:]),
+                     device_metrics=bool(getattr(a, 'device_metrics', False)))
     torch.manual_seed(a.pytorch_seed)
     scaler = None
     train_targets = [targets[i] for i in train_idx]
@@ -610,6 +617,32 @@ def run_training(a: argparse.Namespace) -> Dict[str, list]:
     def run_predict(model, enc_cache, name, idx):
         return predict(model, graphs, idx, a.batch_size, scaler, enc_cache and enc_cache[name],
                        tables and tables[name], None if row_mask is None else row_mask[idx])
+    # --device_metrics: every split's target table and phase mask go to the device once per run, its
+    # BatchMolGraphs are built once (on first use: a run on cached encodings never needs them), and a split is
+    # scored by evaluate.evaluate without a host copy per batch
+    device_metrics = bool(getattr(a, 'device_metrics', False))
+    if device_metrics:
+        from .ensemble import make_batches
+        from .evaluate import Evaluator, TargetTable, evaluate
+        split_idx = dict(splits)
+        split_targets = {name: TargetTable([targets[i] for i in idx], a.dataset_type, device,
+                                           a.multiclass_num_classes, num_tasks=num_tasks) for name, idx in splits}
+        split_masks = {name: None if row_mask is None or not len(idx) else
+                       torch.from_numpy(np.ascontiguousarray(row_mask[idx])).to(device) for name, idx in splits}
+        split_batches = {}
+
+    def score_on_device(model, enc_cache, name, keep=False):
+        """(scores, evaluator) of ``model`` on the split ``name``; ``keep``: the evaluator holds the predictions."""
+        table = split_targets[name]
+        ev = Evaluator(table, metrics, a.dataset_type, scaler, keep=keep)
+        if enc_cache is not None:
+            batches = a.batch_size
+        else:
+            if name not in split_batches:
+                split_batches[name] = make_batches([graphs[i] for i in split_idx[name]], a.batch_size)
+            batches = split_batches[name]
+        return evaluate(model, batches, table, metrics, scaler, tables and tables[name], split_masks[name],
+                        enc_cache and enc_cache[name], evaluator=ev), ev
     sampler = Random(a.seed)  # (one stream of shuffles for the run: an ensemble's later models continue it)
 
     def train_model(save_dir):
@@ -658,11 +691,16 @@ def run_training(a: argparse.Namespace) -> Dict[str, list]:
                         loss = train_step(model, [g], batch_targets(pos), loss_func, optimizer, scheduler,
                                           a.dataset_type, features_batch=feats, grad_clip=a.grad_clip)
                     losses.append(float(loss))
-                val_scores = evaluate_predictions(run_predict(model, enc_cache, 'val', val_idx),
-                                                  [targets[i] for i in val_idx], num_tasks, metrics, a.dataset_type)
-                tr_scores = evaluate_predictions(run_predict(model, enc_cache, 'train', train_idx),
-                                                 [targets[i] for i in train_idx], num_tasks, metrics,
-                                                 a.dataset_type)
+                if device_metrics:
+                    val_scores = score_on_device(model, enc_cache, 'val')[0]
+                    tr_scores = score_on_device(model, enc_cache, 'train')[0]
+                else:
+                    val_scores = evaluate_predictions(run_predict(model, enc_cache, 'val', val_idx),
+                                                      [targets[i] for i in val_idx], num_tasks, metrics,
+                                                      a.dataset_type)
+                    tr_scores = evaluate_predictions(run_predict(model, enc_cache, 'train', train_idx),
+                                                     [targets[i] for i in train_idx], num_tasks, metrics,
+                                                     a.dataset_type)
                 w.writerow([epoch, float(np.mean(losses)) if losses else float('nan')] +
                            [float(np.nanmean(tr_scores[m])) if tr_scores[m] else float('nan') for m in metrics] +
                            [float(np.nanmean(val_scores[m])) if val_scores[m] else float('nan') for m in metrics])
@@ -676,9 +714,15 @@ def run_training(a: argparse.Namespace) -> Dict[str, list]:
         return model, enc_cache, best_epoch
 
     test_targets = [targets[i] for i in test_idx]
+    device_scores = None
     if a.ensemble_size == 1:
         model, enc_cache, best_epoch = train_model(a.save_dir)
-        test_preds = run_predict(model, enc_cache, 'test', test_idx)
+        if device_metrics:  # the scores from the device; the written predictions from one copy of the kept ones
+            device_scores, ev = score_on_device(model, enc_cache, 'test', keep=True)
+            test_preds = prediction_rows(ev.predictions().cpu().numpy(), a.dataset_type,
+                                         a.multiclass_num_classes) if len(test_idx) else []
+        else:
+            test_preds = run_predict(model, enc_cache, 'test', test_idx)
     else:
         # run_training.py:208-499: model k trains into save_dir/model_k; every model's test predictions are folded
         # into one accumulator on the device, and the top-level scores and predictions are the ensemble's
@@ -705,7 +749,8 @@ def run_training(a: argparse.Namespace) -> Dict[str, list]:
             with open(os.path.join(a.save_dir, f'model_{k}', 'test_scores.json'), 'w') as f:
                 json.dump(own, f, indent=4, sort_keys=True)
         test_preds = prediction_rows(mean, a.dataset_type, a.multiclass_num_classes)
-    scores = evaluate_predictions(test_preds, test_targets, num_tasks, metrics, a.dataset_type)
+    scores = device_scores if device_scores is not None else \
+        evaluate_predictions(test_preds, test_targets, num_tasks, metrics, a.dataset_type)
     with open(os.path.join(a.save_dir, 'test_scores.json'), 'w') as f:
         json.dump(scores, f, indent=4, sort_keys=True)
     with open(os.path.join(a.save_dir, 'test_scores.csv'), 'w', newline='') as f:

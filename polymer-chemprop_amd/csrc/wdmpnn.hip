@@ -38,6 +38,7 @@
 #include "small_fwd.hpp"
 #include "wdmpnn.h"
 #include "ensemble.hpp"
+#include "evaluate.hpp"
 
 using namespace wd;
 
@@ -1809,6 +1810,117 @@ int wdmpnn_ensemble_sid(const WdEnsembleSid *e, void *stream) {
     else if (e->M <= 16) hipLaunchKernelGGL(ensemble_sid_kernel<16>, grid, block, 0, st, A);
     else hipLaunchKernelGGL(ensemble_sid_kernel<ENSEMBLE_MAX_MODELS>, grid, block, 0, st, A);
     WD_CHECK_LAUNCH("ensemble_sid");
+    return 0;
+}
+
+int wdmpnn_eval_add(const WdEvalAdd *e, void *stream) {
+    WD_KERNELS_OK();
+    if (!e) return fail(WD_ERR_ARG, "eval_add: null struct");
+    if (e->kind != WD_EVAL_REGRESSION && e->kind != WD_EVAL_CLASSIFICATION && e->kind != WD_EVAL_MULTICLASS)
+        return fail(WD_ERR_SHAPE, "eval_add: kind %d (0 regression, 1 classification, 2 multiclass)", e->kind);
+    if (e->B < 0 || e->tasks < 1 || e->classes < 1 || e->row0 < 0 || e->N < 0)
+        return fail(WD_ERR_SHAPE, "eval_add: needs B >= 0, tasks >= 1, classes >= 1, row0 >= 0, N >= 0 (got B %d tasks %d "
+                    "classes %d row0 %lld N %lld)", e->B, e->tasks, e->classes, (long long)e->row0, (long long)e->N);
+    if (e->classes != 1 && e->kind != WD_EVAL_MULTICLASS)
+        return fail(WD_ERR_SHAPE, "eval_add: %d classes per task for kind %d (multiclass only)", e->classes, e->kind);
+    const int64_t W = (int64_t)e->tasks * e->classes;
+    if (e->ld_pred < W) return fail(WD_ERR_SHAPE, "eval_add: ld_pred %d for %lld columns", e->ld_pred, (long long)W);
+    if (e->ld_targets < e->tasks)
+        return fail(WD_ERR_SHAPE, "eval_add: ld_targets %d for %d tasks", e->ld_targets, e->tasks);
+    if (e->keep && e->ld_keep < W)
+        return fail(WD_ERR_SHAPE, "eval_add: ld_keep %d for %lld columns", e->ld_keep, (long long)W);
+    if (e->row0 + e->B > e->N)
+        return fail(WD_ERR_SHAPE, "eval_add: rows %lld .. %lld of a split of %lld rows", (long long)e->row0,
+                    (long long)(e->row0 + e->B), (long long)e->N);
+    if (!e->scale_mean != !e->scale_std)
+        return fail(WD_ERR_SHAPE, "eval_add: scale_mean and scale_std come together or not at all");
+    if (e->scale_std && e->kind != WD_EVAL_REGRESSION)
+        return fail(WD_ERR_SHAPE, "eval_add: a target scaler for kind %d (regression only)", e->kind);
+    if (e->B == 0) return 0;
+    if (!e->pred || !e->targets || !e->partials)
+        return fail(WD_ERR_ARG, "eval_add: null %s", !e->pred ? "pred" : !e->targets ? "targets" : "partials");
+    EvalAddArgs A{};
+    A.pred = e->pred;
+    A.targets = e->targets;
+    A.scale_mean = e->scale_mean;
+    A.scale_std = e->scale_std;
+    A.partials = e->partials;
+    A.keep_f = e->keep && e->keep_f32 ? reinterpret_cast<float *>(e->keep) : nullptr;
+    A.keep_d = e->keep && !e->keep_f32 ? reinterpret_cast<double *>(e->keep) : nullptr;
+    A.row0 = e->row0;
+    A.B = e->B;
+    A.tasks = e->tasks;
+    A.classes = e->classes;
+    A.kind = e->kind;
+    A.ld_pred = e->ld_pred;
+    A.ld_targets = e->ld_targets;
+    A.ld_keep = e->ld_keep;
+    hipLaunchKernelGGL(eval_add_kernel, dim3(e->tasks), dim3(256), 0, (hipStream_t)stream, A);
+    WD_CHECK_LAUNCH("eval_add");
+    return 0;
+}
+
+int wdmpnn_eval_spectra(const WdEvalSpectra *e, void *stream) {
+    WD_KERNELS_OK();
+    if (!e) return fail(WD_ERR_ARG, "eval_spectra: null struct");
+    if (e->B < 0 || e->T < 1 || e->row0 < 0 || e->N < 0)
+        return fail(WD_ERR_SHAPE, "eval_spectra: needs B >= 0, T >= 1, row0 >= 0, N >= 0 (got B %d T %d row0 %lld N %lld)",
+                    e->B, e->T, (long long)e->row0, (long long)e->N);
+    if (e->T > WD_HEAD_MAX_SPECTRUM)
+        return fail(WD_ERR_UNSUPPORTED, "eval_spectra: T %d (at most %d positions)", e->T, WD_HEAD_MAX_SPECTRUM);
+    if (e->ld_pred < e->T) return fail(WD_ERR_SHAPE, "eval_spectra: ld_pred %d for T %d", e->ld_pred, e->T);
+    if (e->ld_targets < e->T) return fail(WD_ERR_SHAPE, "eval_spectra: ld_targets %d for T %d", e->ld_targets, e->T);
+    if (e->keep && e->ld_keep < e->T) return fail(WD_ERR_SHAPE, "eval_spectra: ld_keep %d for T %d", e->ld_keep, e->T);
+    if (e->row0 + e->B > e->N)
+        return fail(WD_ERR_SHAPE, "eval_spectra: rows %lld .. %lld of a split of %lld rows", (long long)e->row0,
+                    (long long)(e->row0 + e->B), (long long)e->N);
+    if (e->B == 0) return 0;
+    if (!e->pred || !e->targets)
+        return fail(WD_ERR_ARG, "eval_spectra: null %s", !e->pred ? "pred" : "targets");
+    if (!e->sid && !e->wasserstein) return fail(WD_ERR_ARG, "eval_spectra: null sid and wasserstein (one is needed)");
+    EvalSpectraArgs A{};
+    A.pred = e->pred;
+    A.targets = e->targets;
+    A.sid = e->sid;
+    A.wass = e->wasserstein;
+    A.keep_f = e->keep && e->keep_f32 ? reinterpret_cast<float *>(e->keep) : nullptr;
+    A.keep_d = e->keep && !e->keep_f32 ? reinterpret_cast<double *>(e->keep) : nullptr;
+    A.row0 = e->row0;
+    A.T = e->T;
+    A.ld_pred = e->ld_pred;
+    A.ld_targets = e->ld_targets;
+    A.ld_keep = e->ld_keep;
+    hipLaunchKernelGGL(eval_spectra_kernel, dim3(e->B), dim3(256), 0, (hipStream_t)stream, A);
+    WD_CHECK_LAUNCH("eval_spectra");
+    return 0;
+}
+
+int wdmpnn_eval_auc(const WdEvalAuc *e, void *stream) {
+    WD_KERNELS_OK();
+    if (!e) return fail(WD_ERR_ARG, "eval_auc: null struct");
+    if (e->N < 0 || e->tasks < 1)
+        return fail(WD_ERR_SHAPE, "eval_auc: needs N >= 0, tasks >= 1 (got N %lld tasks %d)", (long long)e->N, e->tasks);
+    if (e->ld_preds < e->tasks) return fail(WD_ERR_SHAPE, "eval_auc: ld_preds %d for %d tasks", e->ld_preds, e->tasks);
+    if (e->ld_targets < e->tasks)
+        return fail(WD_ERR_SHAPE, "eval_auc: ld_targets %d for %d tasks", e->ld_targets, e->tasks);
+    if (e->N > WD_EVAL_AUC_MAX_ROWS)
+        return fail(WD_ERR_UNSUPPORTED, "eval_auc: %lld rows (at most %d: the pair counts are quadratic)",
+                    (long long)e->N, WD_EVAL_AUC_MAX_ROWS);
+    if (e->tasks > 65535) return fail(WD_ERR_UNSUPPORTED, "eval_auc: %d tasks (at most 65535)", e->tasks);
+    if (e->N == 0) return 0;
+    if (!e->preds || !e->targets || !e->counts)
+        return fail(WD_ERR_ARG, "eval_auc: null %s", !e->preds ? "preds" : !e->targets ? "targets" : "counts");
+    EvalAucArgs A{};
+    A.preds_f = e->preds_f32 ? reinterpret_cast<const float *>(e->preds) : nullptr;
+    A.preds_d = e->preds_f32 ? nullptr : reinterpret_cast<const double *>(e->preds);
+    A.targets = e->targets;
+    A.counts = reinterpret_cast<long long *>(e->counts);
+    A.N = e->N;
+    A.ld_preds = e->ld_preds;
+    A.ld_targets = e->ld_targets;
+    A.blocks = (int)((e->N + 255) / 256);
+    hipLaunchKernelGGL(eval_auc_kernel, dim3(A.blocks, e->tasks), dim3(256), 0, (hipStream_t)stream, A);
+    WD_CHECK_LAUNCH("eval_auc");
     return 0;
 }
 

@@ -1,0 +1,403 @@
+"""Scoring on the device, on the GPU: ``wdmpnn_eval_add``, ``wdmpnn_eval_spectra`` and ``wdmpnn_eval_auc`` through
+``Evaluator``, ``evaluate`` on models of every dataset type, and ``chemprop_train --device_metrics`` end to end.
+
+The yardstick is the CLI's own ``evaluate_predictions`` (so sklearn) on the same fp32 predictions copied back, after
+``scaler.inverse_transform`` for regression; tests/evaluate_cases.py holds the cases and derives the 1e-11 bound.
+Where the predictions come through other launches (``evaluate`` against ``cli.predict``) the bound is the project's
+1e-5 parity bound."""
+import csv
+import ctypes
+import json
+import os
+
+import numpy as np
+import pytest
+import torch
+
+import evaluate_cases as ec
+from chemprop_amd import Evaluator, FeatureTable, TargetTable, TrainArgs, _native, cli, evaluate, polymer
+from chemprop_amd.ensemble import make_batches
+from chemprop_amd.model import MoleculeModel
+from chemprop_amd.nn_utils import initialize_weights
+from chemprop_amd.train import frozen_encodings
+
+pytestmark = pytest.mark.gpu
+DEV = torch.device('cuda:0')
+HERE = os.path.dirname(os.path.abspath(__file__))
+CSV = os.path.join(HERE, 'data', 'polymer10.csv')
+NPZ = os.path.join(HERE, 'data', 'polymer10_graphs.npz')
+SENTINEL = -12345.678
+
+
+def _bits(a):
+    return np.ascontiguousarray(a, dtype=np.float64).view(np.int64)
+
+
+def _run(case, batch, keep=True, metrics=None):
+    """``case`` through an Evaluator in batches of ``batch`` rows: (scores, evaluator)."""
+    table = TargetTable(case.target_rows(), case.dataset_type, DEV, case.num_classes)
+    ev = Evaluator(table, metrics or case.metrics, case.dataset_type, case.scaler, keep=keep)
+    pred = torch.from_numpy(case.preds).to(DEV)
+    if case.dataset_type == 'multiclass':
+        pred = pred.view(case.n, case.num_tasks, case.num_classes)
+    for r0 in range(0, case.n, batch):
+        ev.add(pred[r0:r0 + batch], r0)
+    return ev.scores(), ev
+
+
+# ---------------------------------------------------------------------------------------------------
+# the kernels, through Evaluator
+# ---------------------------------------------------------------------------------------------------
+def test_regression_partials_and_kept_predictions():
+    """N = 37 in batches of 16 (the last one ragged): rmse, mse, mae, r2 at 1e-11; the task without targets is
+    skipped, the task with one target has no r2; the kept slab is ``scaler.inverse_transform`` bit for bit."""
+    case = ec.regression_case()
+    got, ev = _run(case, 16)
+    ec.assert_scores_close(got, case.want(), what='regression')
+    assert [len(v) for v in got.values()] == [2] * 4 and np.isnan(got['r2'][1])
+    kept = ev.predictions()
+    assert kept.dtype == torch.float64 and tuple(kept.shape) == (37, 3)
+    assert np.array_equal(_bits(kept.cpu().numpy()), _bits(case.values()))
+    # without a scaler: the fp32 values as doubles
+    plain = ec.Case('regression', case.preds, case.targets, case.metrics)
+    got, ev = _run(plain, 16)
+    ec.assert_scores_close(got, plain.want(), what='regression, no scaler')
+    assert np.array_equal(_bits(ev.predictions().cpu().numpy()), _bits(case.preds.astype(np.float64)))
+
+
+def test_classification_partials_and_auc_counts():
+    """N = 300 (two AUC row blocks, the second tile ragged), exact ties, 0.0 / 1.0 / 0.5: auc, cross_entropy at 1e-11,
+    accuracy exactly; all-1 targets and all-0 predictions give NaN; one task has a single positive row."""
+    case = ec.classification_case()
+    want = case.want()
+    got, ev = _run(case, 64)
+    ec.assert_scores_close(got, want, what='classification')
+    for m in case.metrics:
+        assert np.isnan(got[m]).tolist() == [False, True, True, False]
+    kept = ev.predictions()
+    assert kept.dtype == torch.float32 and np.array_equal(kept.cpu().numpy(), case.preds)
+    # the counts themselves are the integers the numpy restatement gives
+    _, counts = ec.numpy_partials(case)
+    assert tuple(ev._auc_counts.shape) == (8,)
+    assert np.array_equal(ev._auc_counts.cpu().numpy().reshape(4, 2).sum(axis=1), counts[:, 0])
+    # without auc nothing is kept unless asked for
+    got, ev = _run(case, 300, keep=False, metrics=['accuracy', 'cross_entropy'])
+    ec.assert_scores_close(got, {m: want[m] for m in ('accuracy', 'cross_entropy')}, what='classification, one batch')
+    with pytest.raises(ValueError):
+        ev.predictions()
+
+
+def test_multiclass_partials():
+    """N = 37, two tasks of three classes: an absent class, two equal maxima (the first wins), a probability of
+    exactly 0 at the true class (clipped to 2^-52)."""
+    case = ec.multiclass_case()
+    got, ev = _run(case, 16)
+    ec.assert_scores_close(got, case.want(), what='multiclass')
+    assert [len(v) for v in got.values()] == [2, 2]
+    assert np.array_equal(ev.predictions().cpu().numpy(), case.preds)
+
+
+@pytest.mark.parametrize('n,T,batch', [(9, 70, 4), (9, 300, 4), (2, 8192, 2)])
+def test_spectra_rows(n, T, batch):
+    """T = 70 (no multiple of 64), T = 300 (chunks of two positions), T = 8192 (the cap: chunks of 32): missing
+    targets, phase-excluded NaN predictions, a row with a single present target."""
+    case = ec.spectra_case(n, T)
+    got, ev = _run(case, batch)
+    ec.assert_scores_close(got, case.want(), what=f'spectra T={T}')
+    kept = ev.predictions().cpu().numpy()
+    assert kept.dtype == np.float32 and np.array_equal(kept, case.preds, equal_nan=True)
+    # one metric alone
+    for m in case.metrics:
+        one, _ = _run(case, n, keep=False, metrics=[m])
+        ec.assert_scores_close(one, {m: got[m]}, what=f'spectra T={T}, {m} alone')
+
+
+@pytest.mark.parametrize('make', [ec.regression_case, ec.classification_case, ec.multiclass_case, ec.spectra_case])
+def test_one_batch_and_batches_of_one_agree(make):
+    """Stream order sequences the batches: the same data as one batch and as N batches of one row."""
+    case = make()
+    want = case.want()
+    whole, _ = _run(case, case.n)
+    single, ev = _run(case, 1)
+    ec.assert_scores_close(whole, want, what=f'{case.dataset_type}, one batch')
+    ec.assert_scores_close(single, want, what=f'{case.dataset_type}, batches of one')
+    ec.assert_scores_close(single, whole, what=f'{case.dataset_type}, one batch vs batches of one')
+    assert np.array_equal(_bits(ev.predictions().cpu().numpy()), _bits(case.values()))
+
+
+def test_leading_dimensions_and_untouched_padding():
+    """wdmpnn_eval_add with ld_pred, ld_targets and ld_keep beyond the widths: the padding of the kept slab and
+    the partials of no other task are written."""
+    case = ec.regression_case()
+    n, T = case.n, 3
+    pred = torch.full((n, T + 2), 777.0, dtype=torch.float32)
+    pred[:, :T] = torch.from_numpy(case.preds)
+    tg = torch.full((n, T + 1), 555.0, dtype=torch.float64)
+    tg[:, :T] = torch.from_numpy(case.targets)
+    pred, tg = pred.to(DEV), tg.to(DEV)
+    keep = torch.full((n, T + 3), SENTINEL, dtype=torch.float64, device=DEV)
+    part = torch.zeros((T + 1, 4), dtype=torch.float64, device=DEV)
+    part[T] = SENTINEL
+    sm, ss = (torch.from_numpy(np.asarray(v, dtype=np.float64)).to(DEV) for v in (case.scaler.means, case.scaler.stds))
+    for r0 in range(0, n, 16):
+        B = min(16, n - r0)
+        e = _native.WdEvalAdd()
+        e.pred, e.ld_pred, e.B, e.tasks, e.classes, e.kind = pred[r0:].data_ptr(), T + 2, B, T, 1, 0
+        e.ld_targets, e.row0, e.N, e.targets = T + 1, r0, n, tg.data_ptr()
+        e.scale_mean, e.scale_std, e.partials = sm.data_ptr(), ss.data_ptr(), part.data_ptr()
+        e.keep, e.ld_keep, e.keep_f32 = keep.data_ptr(), T + 3, 0
+        _native.check(_native.lib().wdmpnn_eval_add(ctypes.byref(e), _native.current_stream(DEV)), 'eval add')
+    torch.cuda.synchronize()
+    keep, part = keep.cpu().numpy(), part.cpu().numpy()
+    assert np.array_equal(_bits(keep[:, :T]), _bits(case.values())) and np.all(keep[:, T:] == SENTINEL)
+    assert np.all(part[T] == SENTINEL) and np.all(part[:T, 2:] == 0)
+    want, _ = ec.numpy_partials(case)
+    assert np.allclose(part[:T, :2], want[:, :2], rtol=ec.TIGHT, atol=0)
+
+
+def test_metrics_outside_the_partials_take_the_kept_predictions():
+    """A metric the CLI accepts but no kernel computes (rmse of a classifier) comes from cli.metric_value on the
+    kept predictions, in the same dict."""
+    case = ec.classification_case()
+    metrics = ['auc', 'rmse', 'accuracy']
+    got, _ = _run(case, 64, keep=False, metrics=metrics)
+    wide = ec.Case('classification', case.preds, case.targets, metrics)
+    want = wide.want()
+    assert list(got) == metrics and got['rmse'] == pytest.approx(want['rmse'], rel=0, abs=0, nan_ok=True)
+    ec.assert_scores_close({m: got[m] for m in ('auc', 'accuracy')}, {m: want[m] for m in ('auc', 'accuracy')})
+
+
+def test_evaluator_refuses_what_does_not_fit():
+    case = ec.regression_case()
+    table = TargetTable(case.target_rows(), 'regression', DEV)
+    ev = Evaluator(table, ['rmse'], 'regression', case.scaler)
+    pred = torch.from_numpy(case.preds).to(DEV)
+    ev.add(pred[:16], 0)
+    for bad in (lambda: ev.add(pred[:16], 0),                      # the same rows again
+                lambda: ev.add(pred[16:], 30),                     # beyond the split
+                lambda: ev.add(pred[16:, :2], 16),                 # another width
+                lambda: ev.add(pred[16:].double(), 16),            # another dtype
+                lambda: ev.add(pred[16:].cpu(), 16),               # another device
+                lambda: ev.add(pred[16:], 16, 1),                  # a second model
+                lambda: ev.scores()):                              # rows still missing
+        with pytest.raises(ValueError):
+            bad()
+    ev.add(pred[16:], 16)
+    assert np.isfinite(ev.scores()['rmse'][0])
+
+
+# ---------------------------------------------------------------------------------------------------
+# evaluate() on a model
+# ---------------------------------------------------------------------------------------------------
+N_MOLS, BATCH, T_SPEC = 21, 8, 12
+
+
+def _polymers(n, rng):
+    graphs = []
+    for k in range(n):
+        fa = float(rng.choice([0.25, 0.5, 0.75]))
+        s = f'[*:1]c1ccc([*:2])cc1.[*:3]CC[*:4]|{fa}|{1 - fa}|<1-3:0.5:0.5<2-4:0.5:0.5<1-2:0.5:0.5~{10:g}'
+        graphs.append(polymer.synthetic_polymer_graph(s, seed=k))
+    return graphs
+
+
+@pytest.fixture(scope='module')
+def world():
+    """The graphs, feature rows and per-type targets shared by the model tests below."""
+    rng = np.random.default_rng(21)
+    graphs = _polymers(N_MOLS, rng)
+    feats = rng.standard_normal((N_MOLS, 3))
+    missing = rng.random((N_MOLS, 2)) < 0.2
+    reg = np.where(missing, np.nan, rng.standard_normal((N_MOLS, 2)) * 2 + 1)
+    cls = np.where(missing, np.nan, rng.integers(0, 2, (N_MOLS, 2)).astype(np.float64))
+    mul = np.where(missing, np.nan, rng.integers(0, 3, (N_MOLS, 2)).astype(np.float64))
+    included = np.ones((N_MOLS, T_SPEC), dtype=bool)
+    included[::3, T_SPEC - 3:] = False
+    spec = np.where(included, np.exp(rng.standard_normal((N_MOLS, T_SPEC))), 0.0)
+    spec = np.where(included, spec / spec.sum(axis=1, keepdims=True), np.nan)
+    return dict(graphs=graphs, feats=feats, included=included,
+                targets={'regression': reg, 'classification': cls, 'multiclass': mul, 'spectra': spec},
+                batches=make_batches(graphs, BATCH))
+
+
+METRICS = {'regression': ['rmse', 'mse', 'mae', 'r2'], 'classification': ['auc', 'cross_entropy', 'accuracy'],
+           'multiclass': ['cross_entropy', 'accuracy'], 'spectra': ['sid', 'wasserstein']}
+
+
+@pytest.mark.parametrize('variant', ['plain', 'features', 'encodings'])
+@pytest.mark.parametrize('kind', ['regression', 'classification', 'multiclass', 'spectra'])
+def test_evaluate_against_the_host_loop(world, kind, variant):
+    """``evaluate`` (forward_many, join_features, the native head, the evaluator) against
+    ``cli.evaluate_predictions(cli.predict(...))`` on the same model: other launches, so the 1e-5 parity bound."""
+    torch.manual_seed(5)
+    use_f = variant == 'features'
+    args = TrainArgs(hidden_size=32, depth=2, dataset_type=kind, num_tasks=T_SPEC if kind == 'spectra' else 2,
+                     multiclass_num_classes=3, use_input_features=use_f, features_size=3 if use_f else 0, device=DEV)
+    model = MoleculeModel(args)
+    initialize_weights(model)
+    if variant == 'encodings':
+        cli.apply_freezing(model, frzn_encoder=True)
+    model = model.to(DEV).eval()
+    targets = world['targets'][kind]
+    rows = [[None if np.isnan(v) else (int(v) if kind == 'multiclass' else float(v)) for v in r] for r in targets]
+    scaler = cli.StandardScaler(np.array([1.0, -0.5]), np.array([2.0, 0.75])) if kind == 'regression' else None
+    table = TargetTable(rows, kind, DEV, 3)
+    ftable = FeatureTable(world['feats'], DEV) if use_f else None
+    mask = world['included'] if kind == 'spectra' else None
+    row_mask = None if mask is None else torch.from_numpy(mask).to(DEV)
+    enc = frozen_encodings(model, world['graphs'], BATCH) if variant == 'encodings' else None
+    idx = list(range(N_MOLS))
+    preds = cli.predict(model, world['graphs'], idx, BATCH, scaler, enc, ftable, mask)
+    want = cli.evaluate_predictions(preds, rows, table.num_tasks, METRICS[kind], kind)
+    ev = Evaluator(table, METRICS[kind], kind, scaler, keep=True)
+    got = evaluate(model, BATCH if variant == 'encodings' else world['batches'], table, METRICS[kind], scaler, ftable,
+                   row_mask, enc, evaluator=ev)
+    ec.assert_scores_close(got, want, tol=ec.PARITY, what=f'{kind} / {variant}')
+    # and at the tight bound against the yardstick on the evaluator's own predictions
+    kept = ev.predictions().cpu().numpy().astype(np.float64)
+    own = cli.evaluate_predictions(cli.prediction_rows(kept, kind, 3), rows, table.num_tasks, METRICS[kind], kind)
+    ec.assert_scores_close(got, own, what=f'{kind} / {variant}, own predictions')
+    again = evaluate(model, BATCH if variant == 'encodings' else world['batches'], table, METRICS[kind], scaler,
+                     ftable, row_mask, enc)
+    assert json.dumps(again) == json.dumps(got)                        # a fresh evaluator, the same numbers
+
+
+def test_evaluate_refuses_mismatched_inputs(world):
+    torch.manual_seed(5)
+    model = MoleculeModel(TrainArgs(hidden_size=32, depth=2, num_tasks=2, device=DEV)).to(DEV).eval()
+    table = TargetTable(world['targets']['regression'], 'regression', DEV)
+    with pytest.raises(ValueError):
+        evaluate(model, world['batches'][:-1], table, ['rmse'])                      # rows missing
+    with pytest.raises(ValueError):
+        evaluate(model, world['batches'], table, ['rmse'], features=FeatureTable(world['feats'], DEV))
+    other = TargetTable(world['targets']['regression'], 'regression', DEV)
+    with pytest.raises(ValueError):
+        evaluate(model, world['batches'], table, ['rmse'], evaluator=Evaluator(other, ['rmse']))
+
+
+def test_a_model_the_native_head_refuses_takes_its_own_forward(world):
+    """70 outputs are beyond the native heads: ``evaluate`` runs the model's own forward into the same evaluator."""
+    from chemprop_amd import train
+    torch.manual_seed(1)
+    model = MoleculeModel(TrainArgs(hidden_size=32, depth=2, num_tasks=70, device=DEV)).to(DEV).eval()
+    assert train._predict_head(model) is None
+    targets = np.random.default_rng(0).standard_normal((N_MOLS, 70))
+    table = TargetTable(targets, 'regression', DEV)
+    got = evaluate(model, world['batches'], table, ['rmse', 'mae'])
+    preds = cli.predict(model, world['graphs'], list(range(N_MOLS)), BATCH, None)
+    want = cli.evaluate_predictions(preds, table.rows(), 70, ['rmse', 'mae'], 'regression')
+    ec.assert_scores_close(got, want, tol=ec.PARITY, what='fallback forward')
+
+
+# ---------------------------------------------------------------------------------------------------
+# chemprop_train --device_metrics
+# ---------------------------------------------------------------------------------------------------
+def _read(path):
+    with open(path) as f:
+        return list(csv.reader(f))
+
+
+def test_cli_device_metrics(tmp_path):
+    """The 10-row polymer fixture: two runs with the flag agree byte for byte, write the files a run without it
+    writes, and ``test_scores.json`` is ``cli.evaluate_predictions`` of the written ``test_preds.csv``."""
+    argv = ['--data_path', CSV, '--graphs_path', NPZ, '--dataset_type', 'regression', '--polymer', '--epochs', '3',
+            '--extra_metrics', 'mae', 'r2', '--split_sizes', '0.5', '0.25', '0.25', '--batch_size', '4', '--save_dir']
+    s0 = cli.chemprop_train(argv + [str(tmp_path / 'host')])
+    s1 = cli.chemprop_train(argv + [str(tmp_path / 'a'), '--device_metrics'])
+    s2 = cli.chemprop_train(argv + [str(tmp_path / 'b'), '--device_metrics'])
+    files = sorted(os.listdir(tmp_path / 'host'))
+    assert sorted(os.listdir(tmp_path / 'a')) == files == sorted(os.listdir(tmp_path / 'b'))
+    assert json.dumps(s1) == json.dumps(s2)
+    for name in ('test_preds.csv', 'test_scores.json', 'test_scores.csv', 'train_val_loss_log.csv',
+                 'split_indices.json'):
+        assert open(tmp_path / 'a' / name, 'rb').read() == open(tmp_path / 'b' / name, 'rb').read(), name
+    assert torch.load(str(tmp_path / 'a' / 'best_model.pt'), weights_only=True)['args']['device_metrics'] is True
+    assert torch.load(str(tmp_path / 'host' / 'best_model.pt'), weights_only=True)['args']['device_metrics'] is False
+    # the written scores are the yardstick's scores of the written predictions
+    split = json.load(open(tmp_path / 'a' / 'split_indices.json'))
+    assert len(split['test']) == 3
+    _, _, targets = cli.read_csv(CSV)
+    written = _read(tmp_path / 'a' / 'test_preds.csv')
+    preds = [[float(c) for c in r[1:]] for r in written[1:]]
+    metrics = ['rmse', 'mae', 'r2']
+    want = cli.evaluate_predictions(preds, [targets[i] for i in split['test']], 1, metrics, 'regression')
+    got = json.load(open(tmp_path / 'a' / 'test_scores.json'))
+    ec.assert_scores_close({m: got[m] for m in metrics}, want, what='test_scores.json')
+    assert json.dumps(got, sort_keys=True) == json.dumps(s1, sort_keys=True)
+    # the same training either way: the host loop's scores and log differ by the launch path alone
+    # (r2 = 1 - SS_res / SS_tot carries the relative error of SS_res / SS_tot = 1 - r2, far from 0 on three rows)
+    for m in metrics:
+        scale = abs(1 - s0[m][0]) if m == 'r2' else abs(s0[m][0])
+        print(f'device vs host {m}: {s1[m][0]!r} {s0[m][0]!r}')
+        assert len(s1[m]) == len(s0[m]) == 1 and abs(s1[m][0] - s0[m][0]) <= ec.PARITY * scale
+    log_h, log_d = _read(tmp_path / 'host' / 'train_val_loss_log.csv'), _read(tmp_path / 'a' / 'train_val_loss_log.csv')
+    assert log_h[0] == log_d[0] and len(log_h) == len(log_d) == 4
+    h, d = (np.array([[float(c) for c in r] for r in log[1:]]) for log in (log_h, log_d))
+    assert np.array_equal(h[:, :2], d[:, :2])                       # epoch, train loss
+    assert np.allclose(d, h, rtol=ec.PARITY, atol=ec.PARITY, equal_nan=True)
+    assert np.array_equal(_read(tmp_path / 'host' / 'test_preds.csv')[0], written[0])
+
+
+def _write(path, rows):
+    with open(path, 'w', newline='') as f:
+        csv.writer(f).writerows(rows)
+
+
+@pytest.mark.parametrize('kind', ['multiclass', 'spectra', 'frozen_features'])
+def test_cli_device_metrics_on_the_other_model_families(tmp_path, kind):
+    """Multiclass, spectra under a phase mask, and a frozen encoder with a features file (cached encodings joined
+    to the feature table): the written scores are the yardstick's scores of the written ``test_preds.csv``."""
+    rng = np.random.default_rng(13)
+    n = 16
+    fas = [float(rng.choice([0.25, 0.5, 0.75])) for _ in range(n)]
+    smiles = [f'[*:1]c1ccc([*:2])cc1.[*:3]CC[*:4]|{fa}|{1 - fa}|<1-3:0.5:0.5<2-4:0.5:0.5<1-2:0.5:0.5~{10:g}' for fa in fas]
+    graphs = [polymer.synthetic_polymer_graph(s, seed=k) for k, s in enumerate(smiles)]
+    paths = {k: str(tmp_path / v) for k, v in (('csv', 'd.csv'), ('npz', 'd.npz'), ('phase', 'ph.csv'),
+                                                ('mask', 'm.csv'), ('feat', 'f.csv'))}
+    from chemprop_amd.graph_io import save_graphs
+    save_graphs(paths['npz'], graphs)
+    argv = ['--data_path', paths['csv'], '--graphs_path', paths['npz'], '--polymer', '--epochs', '2', '--warmup_epochs',
+            '1', '--batch_size', '4', '--hidden_size', '32', '--split_sizes', '0.5', '0.25', '0.25', '--device_metrics',
+            '--save_dir', str(tmp_path / 'o')]
+    classes = 1
+    if kind == 'multiclass':
+        _write(paths['csv'], [['smiles', 'kind']] + [[s, str(int(4 * fa) - 1)] for s, fa in zip(smiles, fas)])
+        argv += ['--dataset_type', 'multiclass', '--multiclass_num_classes', '3', '--extra_metrics', 'accuracy']
+        metrics, classes = ['cross_entropy', 'accuracy'], 3
+        targets = cli.read_class_targets(paths['csv'], 3)
+    elif kind == 'spectra':
+        T = 12
+        names = [f'b{t}' for t in range(T)]
+        spec = np.exp(rng.standard_normal((n, T)))
+        phases = [k % 2 for k in range(n)]
+        _write(paths['csv'], [['smiles'] + names] + [[s] + [f'{v:.6g}' for v in r] for s, r in zip(smiles, spec)])
+        _write(paths['phase'], [['p0', 'p1']] + [[int(p == 0), int(p == 1)] for p in phases])
+        _write(paths['mask'], [['phase'] + names, ['p0'] + [1] * T, ['p1'] + [1] * (T - 3) + [0] * 3])
+        argv += ['--dataset_type', 'spectra', '--phase_features_path', paths['phase'], '--spectra_phase_mask_path',
+                 paths['mask'], '--extra_metrics', 'wasserstein']
+        metrics = ['sid', 'wasserstein']
+        _, _, raw = cli.read_csv(paths['csv'])
+        targets = cli.normalize_spectra(raw, cli.load_phase_features(paths['phase'], n),
+                                        cli.load_phase_mask(paths['mask']), excluded_sub_value=None, threshold=1e-8)
+    else:
+        _write(paths['csv'], [['smiles', 'y']] + [[s, f'{2 * fa + 0.1 * rng.normal():.6g}'] for s, fa in zip(smiles, fas)])
+        _write(paths['feat'], [['f0', 'f1']] + [[repr(float(v)) for v in r] for r in rng.standard_normal((n, 2))])
+        argv += ['--features_path', paths['feat'], '--frzn_encoder', '--extra_metrics', 'mae']
+        metrics = ['rmse', 'mae']
+        _, _, targets = cli.read_csv(paths['csv'])
+    scores = cli.chemprop_train(argv)
+    split = json.load(open(tmp_path / 'o' / 'split_indices.json'))
+    written = _read(tmp_path / 'o' / 'test_preds.csv')[1:]
+    assert len(written) == len(split['test']) == 4
+    vals = np.array([[np.nan if c == '' else float(c) for c in r[1:]] for r in written])
+    if kind == 'spectra':
+        assert np.isnan(vals).any() and np.array_equal(np.isnan(vals), np.array(
+            [[targets[i][t] is None for t in range(12)] for i in split['test']]))
+    want = cli.evaluate_predictions(cli.prediction_rows(vals, 'regression' if kind == 'frozen_features' else kind, classes),
+                                    [targets[i] for i in split['test']], 1 if kind != 'spectra' else 12, metrics,
+                                    'regression' if kind == 'frozen_features' else kind)
+    got = json.load(open(tmp_path / 'o' / 'test_scores.json'))
+    ec.assert_scores_close({m: got[m] for m in metrics}, want, what=f'{kind} test_scores.json')
+    assert json.dumps(got, sort_keys=True) == json.dumps(scores, sort_keys=True)
+    log = _read(tmp_path / 'o' / 'train_val_loss_log.csv')
+    assert len(log) == 3 and all(np.isfinite(float(c)) for r in log[1:] for c in r)
