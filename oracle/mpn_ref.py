@@ -71,15 +71,29 @@ def _linear(p: Dict[str, torch.Tensor], name: str, x: torch.Tensor) -> torch.Ten
 
 def encoder_forward(p: Dict[str, torch.Tensor], graph, args,
                     atom_descriptors_batch: Optional[List[np.ndarray]] = None, dtype=None,
-                    masks: Optional[dict] = None) -> torch.Tensor:
-    """mpn.py:66-173 with dropout = 0.  ``p`` keys: W_i.weight, [W_i.bias], W_h.weight, [W_h.bias],
-    W_o.weight, W_o.bias, cached_zero_vector, [act_func.weight], [atom_descriptors_layer.*].
+                    masks: Optional[dict] = None, drop: Optional[dict] = None) -> torch.Tensor:
+    """mpn.py:66-173, with dropout = 0 unless ``drop`` is given.  ``p`` keys: W_i.weight, [W_i.bias],
+    W_h.weight, [W_h.bias], W_o.weight, W_o.bias, cached_zero_vector, [act_func.weight],
+    [atom_descriptors_layer.*].
     ``dtype=torch.float64`` evaluates the same op sequence in double precision (conditioning
     reference for the parity tests); the default keeps the reference's float32.  ``masks`` = {'Z':
     [one bool tensor per message activation, mpn.py:97 then each mpn.py:123], 'Zo': bool tensor for
-    mpn.py:133}: kink branches taken from another evaluation (``activation``'s ``mask``)."""
+    mpn.py:133}: kink branches taken from another evaluation (``activation``'s ``mask``).
+    ``drop`` = explicit dropout masks (float tensors of 0 or 1 / (1 - p), built by the caller), multiplied
+    in where the reference applies ``dropout_layer``: {'M': [one [message rows, H] mask per W_h update
+    t = 1 .. depth - 1, mpn.py:124], 'o': [n_atoms, H] (mpn.py:134), 'd': [n_atoms, H + desc] (mpn.py:143,
+    only with descriptors)}; the input layer's act(inp) (mpn.py:97) is never masked.  All rows are
+    natural rows including the pad row 0."""
     calls = iter((masks['Z'] + [masks['Zo']]) if masks is not None else [])
     act = lambda x: activation(args.activation, x, p.get('act_func.weight'), next(calls, None))  # noqa: E731
+
+    def dropout(x, m):  # mpn.py:124/134/143 with the caller's mask in place of nn.Dropout's
+        if m.shape != x.shape:
+            raise ValueError(f'dropout mask of shape {tuple(m.shape)} for a tensor of shape {tuple(x.shape)}')
+        return x * m.to(x.dtype)
+
+    if drop is not None and len(drop['M']) != args.depth - 1:
+        raise ValueError(f"{len(drop['M'])} message masks for depth {args.depth}")
     if atom_descriptors_batch is not None:  # mpn.py:77-79
         atom_descriptors_batch = [np.zeros([1, atom_descriptors_batch[0].shape[1]])] + list(atom_descriptors_batch)
         atom_descriptors_batch = torch.from_numpy(np.concatenate(atom_descriptors_batch, axis=0)).float()
@@ -95,7 +109,7 @@ def encoder_forward(p: Dict[str, torch.Tensor], graph, args,
     else:
         inp = _linear(p, 'W_i', f_bonds)  # mpn.py:95-96
     message = act(inp)  # mpn.py:97
-    for _ in range(args.depth - 1):  # mpn.py:100
+    for t in range(1, args.depth):  # mpn.py:100
         if args.undirected:
             message = (message + message[b2revb]) / 2  # mpn.py:101-102
         if args.atom_messages:  # mpn.py:104-108
@@ -111,17 +125,23 @@ def encoder_forward(p: Dict[str, torch.Tensor], graph, args,
             message = a_message[b2a] - rev_message
         message = _linear(p, 'W_h', message)  # mpn.py:122
         message = act(inp + message)  # mpn.py:123
+        if drop is not None:
+            message = dropout(message, drop['M'][t - 1])  # mpn.py:124
     a2x = a2a if args.atom_messages else a2b  # mpn.py:126-131
     nei_a_message = index_select_ND(message, a2x)
     nei_a_weight = index_select_ND(w_bonds, a2x)
     a_message = (nei_a_message * nei_a_weight[..., None]).sum(dim=1)
     a_input = torch.cat([f_atoms, a_message], dim=1)  # mpn.py:132
     atom_hiddens = act(_linear(p, 'W_o', a_input))  # mpn.py:133
+    if drop is not None:
+        atom_hiddens = dropout(atom_hiddens, drop['o'])  # mpn.py:134
     if atom_descriptors_batch is not None:  # mpn.py:137-143
         if len(atom_hiddens) != len(atom_descriptors_batch):
             raise ValueError('The number of atoms is different from the length of the extra atom features')
         atom_hiddens = torch.cat([atom_hiddens, atom_descriptors_batch], dim=1)
         atom_hiddens = _linear(p, 'atom_descriptors_layer', atom_hiddens)
+        if drop is not None:
+            atom_hiddens = dropout(atom_hiddens, drop['d'])  # mpn.py:143
     mol_vecs = []  # mpn.py:146-171
     for i, (a_start, a_size) in enumerate(a_scope):
         if a_size == 0:

@@ -74,7 +74,14 @@ def dropout_mask(seed: int, layer: int, rows: int, cols: int, p: float) -> np.nd
     ``[rows][cols]`` of 0 or 1 / (1 - p).  Element (row, col) of dropout site ``layer`` under the 64-bit ``seed``
     hashes ``seed ^ (GOLDEN * (layer + 1)) ^ (row << 32 | col)`` with the splitmix64 finaliser (uint64
     arithmetic), takes the top 24 bits as a uniform u in [0, 1) and keeps the element when
-    ``u >= float32(p)``.  The head's sites: ``layer`` l masks the input of Linear l + 1 (site 0 the encoding)."""
+    ``u >= float32(p)``.  The head's sites: ``layer`` l masks the input of Linear l + 1 (site 0 the encoding).
+
+    The encoder's sites (one seed per forward, ``mpn._dropout_seed``; mpn.py:124/134/143): ``layer`` t masks the
+    t-th W_h update, t = 1 .. depth - 1 (``rows`` = message rows: bond rows, or atom rows in atom-message mode);
+    ``layer`` depth masks the W_o output (``rows`` = atom rows); ``layer`` depth + 1 masks the atom-descriptor
+    layer's output (``cols`` = hidden + descriptor size).  ``row`` is the natural row including the pad row 0,
+    never a block-local one; ``col`` is the hidden column.  The input layer's act(W_i x) (mpn.py:97) is never
+    masked.  The backward re-derives the same elements from the same (seed, layer, row, col)."""
     p32 = np.float32(p)
     golden = np.uint64(0x9E3779B97F4A7C15)
     with np.errstate(over='ignore'):
