@@ -294,7 +294,8 @@ int wdmpnn_plane_bytes(int32_t rows, int32_t kp, size_t *bytes);
 int wdmpnn_split_planes(const float *src, int32_t ld, int32_t rows, int32_t kp, void *dst, size_t dst_bytes,
                         void *stream);
 /* The same with a row map: source row r goes to plane-tile row row_map[r] (skipped when < 0) of a
- * [out_rows, kp] plane-tile matrix whose other rows are zero-filled. */
+ * [out_rows, kp] plane-tile matrix whose other rows are zero-filled.  Every row_map[r] must be < out_rows: the
+ * device does not check it. */
 int wdmpnn_split_planes_rows(const float *src, int32_t ld, int32_t rows, int32_t kp, const int32_t *row_map,
                              int32_t out_rows, void *dst, size_t dst_bytes, void *stream);
 
