@@ -155,10 +155,48 @@ template <typename T, int NJ = WD_MULTI> struct Multi {
 };
 template <typename T, int NJ>
 __device__ __forceinline__ const T &multi_pick(const Multi<T, NJ> &M, int g, int &tile) {
-    int j = 0;
-    while (j + 1 < M.n && g >= M.t0[j + 1]) ++j;
-    tile = g - M.t0[j];
-    return M.p[j];
+    // (one batch: its range starts at grid tile 0 -- launch_multi, one_job -- so neither the search nor t0 is read)
+    if constexpr (NJ == 1) {
+        tile = g;
+        return M.p[0];
+    } else {
+        int j = 0;
+        while (j + 1 < M.n && g >= M.t0[j + 1]) ++j;
+        tile = g - M.t0[j];
+        return M.p[j];
+    }
+}
+
+// tile -> (tile / n, tile % n) without a runtime division (the compiler's is a v_rcp sequence of ~25 dependent
+// instructions at every forward kernel's entry).  The host passes m = tile_magic(n) = floor(2^32 / n) + 1 for
+// n >= 2, and 0 for n = 1 (the multiplier would need 33 bits).  With e = n - 2^32 mod n <= n,
+// tile * m / 2^32 = tile / n + tile * e / (n 2^32), whose floor is floor(tile / n) whenever tile * e < 2^32:
+// exact for every 0 <= tile < 2^32 / n.  The launch code asserts grid * n < 2^32 (tile_magic_ok).
+inline uint32_t tile_magic(int n) { return n >= 2 ? (uint32_t)((1ull << 32) / (uint32_t)n) + 1u : 0u; }
+inline bool tile_magic_ok(int64_t grid, int n) { return n >= 1 && grid >= 0 && grid * n < (1ll << 32); }
+__device__ __forceinline__ void tile_split(int tile, int n, uint32_t magic, int &q, int &r) {
+    q = magic ? (int)__umulhi((uint32_t)tile, magic) : tile;
+    r = tile - q * n;
+}
+
+// A kernel-argument value held in scalar registers from here on: the kernels' entries copy the fields they need
+// before their main loops into locals in one batch (fields adjacent in the struct: one wide scalar load, one
+// wait) and pin them, so that the compiler neither sinks the loads into the conditional blocks that use them
+// nor re-reads the argument segment there (it did both: ten scalar round trips between the embed's ten
+// up-front vector loads, profiles/entry_codegen.txt).
+template <typename V>
+__device__ __forceinline__ V pin_s(V v) {
+    asm volatile("" : "+s"(v));
+    return v;
+}
+// (pointers, all to global memory: pinned as an integer and rebuilt as a global-address-space pointer -- what
+// comes out of the asm statement has lost the address space the compiler inferred from the argument segment,
+// and loads through it became flat loads, which count on both the vector and the LDS / scalar counter)
+template <typename V>
+__device__ __forceinline__ V *pin_s(V *p) {
+    uint64_t v = (uint64_t)p;
+    asm volatile("" : "+s"(v));
+    return (V *)(__attribute__((address_space(1))) V *)v;
 }
 
 }  // namespace wd

@@ -68,6 +68,27 @@ __device__ __forceinline__ BlockRow load_block(const int32_t *blocks, int i) {
     return BlockRow{a.x, a.y, a.z, a.w, b.x, b.y};
 }
 
+// The same row through the constant address space: a scalar load whatever the compiler can prove about the
+// pointer (the pair kernels' loader waves got a vector load, whose vmcnt(0) wait also waited for every copy
+// issued before it).  `blocks` is written by an earlier launch and i is workgroup-uniform.
+__device__ __forceinline__ BlockRow load_block_s(const int32_t *blocks, int i) {
+    typedef int v4i __attribute__((ext_vector_type(4)));
+    typedef int v2i __attribute__((ext_vector_type(2)));
+    const auto *q = (const __attribute__((address_space(4))) int32_t *)(blocks + 8 * i);
+    const v4i a = *reinterpret_cast<const __attribute__((address_space(4))) v4i *>(q);
+    const v2i b = *reinterpret_cast<const __attribute__((address_space(4))) v2i *>(q + 4);
+    return BlockRow{a.x, a.y, a.z, a.w, b.x, b.y};
+}
+// ... and its atom and molecule fields alone (W_o + readout: loaded whole, the two unused registers of the
+// 16-byte load were reused at once, and the write-after-write wait for them stood ahead of the role branch)
+__device__ __forceinline__ BlockRow load_block_atoms_s(const int32_t *blocks, int i) {
+    typedef int v2i __attribute__((ext_vector_type(2)));
+    const auto *q = reinterpret_cast<const __attribute__((address_space(4))) v2i *>(
+        (const __attribute__((address_space(4))) int32_t *)(blocks + 8 * i));
+    const v2i a = q[1], b = q[2];
+    return BlockRow{0, 0, a.x, a.y, b.x, b.y};
+}
+
 // s += w * T[j][c .. c+7] (LDS tile, row stride LDC)
 template <int LDC>
 __device__ __forceinline__ void lds_term(const float *T, int j, int c, float w, float4 &s0, float4 &s1) {
@@ -76,23 +97,30 @@ __device__ __forceinline__ void lds_term(const float *T, int j, int c, float w, 
 }
 
 struct MpLayerP {
+    // The entry head: what the pair layers read before their main loop, adjacent and first, so that the entry
+    // copies it with one batch of scalar loads and one wait (mp_layer_kernel; 15 dwords).  Everything after it
+    // is first touched by the loaders' hook or the epilogue.
+    const uint8_t *ain;         // (pair-operand layers, below)
+    const uint8_t *wh;          // W_h h2 plane tiles [Hk][Hk] with BN-row blocks
+    const int32_t *blocks;
+    const uint32_t *amax_in;    // the scale words of M_{t-1} (planes.hpp h2): [nblk][amax_in_n] maxima of |M_{t-1}|,
+    const uint32_t *wh_amax;    // W_h's scale word (max |W_h|, wdmpnn_pack_params)
+    int kp;                     // Hk
+    int n_tiles;                // Hk / BN
+    uint32_t tmagic;            // tile_magic(n_tiles): tile -> (block, column tile) without a division (common.hpp)
+    int amax_in_n;              // published per (block, tile) by the embed or by layer t - 1; amax_rt > 0:
+    int ain_g;                  // (pair-operand layers, below)
     const float *zin;           // Z_{t-1}: fp32 natural bond rows [Rp][kp] (the first layer: inp, mpn.py:95); the
                                 // GEMM operand is M_{t-1} = dropout(act(Z_{t-1})) (mpn.py:97, 123-124), formed
                                 // while staging
-    const uint32_t *amax_in;    // its scale words (planes.hpp h2): [nblk][amax_in_n] maxima of |M_{t-1}|,
-    int amax_in_n;              // published per (block, tile) by the embed or by layer t - 1; amax_rt > 0:
-    int amax_rt;                //   per (amax_rt-row tile of zin, column tile) by the input GEMM (gemm_x6g's
+    int amax_rt;                // amax_in: per (amax_rt-row tile of zin, column tile) by the input GEMM (gemm_x6g's
                                 //   Epi.amax): the words of the row tiles the block's rows overlap
     int ldz, ldr;               // row strides of zin and of the residual inp (Hk, or wider for column slices)
     float p_drop_in;            // the dropout of M_{t-1} (0 for M_0: mpn.py:97 drops nothing)
     float *zout;                // Z_t, same layout (null in the last layer)
     uint32_t *amax_out;         // [nblk][n_tiles]: max |dropout(act(Z_t))| of each workgroup (not the last layer)
-    int kp;                     // Hk
-    const uint8_t *wh;          // W_h h2 plane tiles [Hk][Hk] with BN-row blocks
-    const uint32_t *wh_amax;    // their scale word (max |W_h|, wdmpnn_pack_params)
     const float *inp;           // fp32 [Rp][Hk] natural rows (mpn.py:95 input)
     const float *bias;          // b_h (padded) or null
-    const int32_t *blocks;
     const int32_t *rev;         // b2revb (natural bond ids)
     const uint8_t *src_blk;     // per natural bond row: block-local source atom (b2a)
     int undirected;             // mpn.py:101-102
@@ -100,7 +128,6 @@ struct MpLayerP {
     const int32_t *aptr, *aidx; const float *acoef;  // atom gather (natural atom rows -> natural bond rows)
     const uint8_t *aell_idx; const float *aell_coef; // its first ELLW entries per row, block-local (WdGraph)
     uint8_t *aplanes;           // A: blocked atom plane tiles [nblk * 64][kp] (the last layer)
-    int n_tiles;                // Hk / BN
     // training forward (save_for_backward) or null, the last layer only (the others' Z_t is zout): its
     // pre-activation Z_t (mpn.py:123) as fp32 natural bond rows [Rp][kp] and the atom aggregate A
     // (mpn.py:126-131) as fp32 natural atom rows [Vap][kp] (the backward's operands)
@@ -118,7 +145,7 @@ struct MpLayerP {
     // molecule blocks ([nblk][Hk / 32 chunks][2 planes][128 rows][64 B]), scaled per group of ain_g columns
     // by the words amax_in [nblk][amax_in_n] (the embed: 32-column groups; a layer: its BN-column tiles),
     // and the layer writes M_t the same way into aout (not the last layer), scaled by its tile's max
-    const uint8_t *ain; int ain_g;
+    // (ain, ain_g: in the entry head)
     uint8_t *aout;
     // ... and the last layer writes the atom aggregate A as pair tiles of the blocks' atom rows ([nblk][Hk / 32]
     // [2][64][64 B], W_o's A operand: wo_readout_kernel<..., PAIRS>), scaled by its tile's max, published in
@@ -530,9 +557,29 @@ __global__ __launch_bounds__(MP_THREADS, 4) void mp_layer_kernel(const Multi<MpL
     int tile;
     wd_stamp(0 + 8 * LAST);
     const MpLayerP &P = multi_pick(MP, xcd_tile(blockIdx.x, gridDim.x), tile);
-    const int blk = tile / P.n_tiles, nt = tile % P.n_tiles, n0 = nt * BN;
-    // (PAIRS: the block row is loaded inside the main loop, by each role where it needs it)
-    BlockRow B = PAIRS ? BlockRow{} : load_block(P.blocks, blk);
+    // The entry head by value (PAIRS: all of it, pinned in scalar registers -- one batch of loads, one wait;
+    // the register-staged kernels pin nothing and read their arguments where they did: pinned, their
+    // allocation moved from 108-110 to 118-123 VGPRs for nothing measured).
+    auto hv = [](auto v) {
+        if constexpr (PAIRS) return pin_s(v);
+        else return v;
+    };
+    const int h_nt = hv(P.n_tiles), h_kp = hv(P.kp);
+    const uint32_t h_tm = hv(P.tmagic);
+    const int32_t *h_blocks = hv(P.blocks);
+    const uint8_t *h_ain = nullptr, *h_wh = hv(P.wh);
+    const uint32_t *h_amax_in = nullptr, *h_wh_amax = nullptr;
+    int h_amax_in_n = 0, h_ain_g = 0;
+    if constexpr (PAIRS) {
+        h_ain = pin_s(P.ain); h_amax_in = pin_s(P.amax_in); h_wh_amax = pin_s(P.wh_amax);
+        h_amax_in_n = pin_s(P.amax_in_n); h_ain_g = pin_s(P.ain_g);
+    }
+    int blk, nt;
+    tile_split(tile, h_nt, h_tm, blk, nt);
+    const int n0 = nt * BN;
+    // (PAIRS: a scalar load issued here, ahead of the role branch, and waited for by each role where it first
+    // needs the row -- the loaders after their first weight copies have left, h2_mainloop_pairs)
+    BlockRow B = PAIRS ? load_block_s(h_blocks, blk) : load_block(h_blocks, blk);
     Epi_ E;
     float *Pt = reinterpret_cast<float *>(lds);
     // Two GEMM front ends.  After either, both run the same steps -- the lists into E, the scaled tile into Pt,
@@ -546,16 +593,16 @@ __global__ __launch_bounds__(MP_THREADS, 4) void mp_layer_kernel(const Multi<MpL
         // the atom sums the epilogue writes
         static_assert(EPI_BYTES + Epi_::PRE_BYTES <= STG_BYTES, "epilogue lists beside the P tile");
         uint8_t *pre = lds + STG_BYTES - Epi_::PRE_BYTES;
-        auto rows = [&]() {
-            B = load_block(P.blocks, blk);
-            return B.bn;
-        };
+        // (the row's scalar load is in flight since the entry: nothing of the loaders' waits on vector memory
+        // between the entry and their first A copy)
+        auto rows = [&]() { return B.bn; };
         // (W_h's word too: only the consumers' epilogue step needs it, and a dependent load ahead of the role
-        // branch stood between the loaders and their first copies)
+        // branch stood between the loaders and their first copies.  The consumers issue the row, the words and
+        // this word together -- all three addresses come from the head -- and wait once.)
         uint32_t whm = 0;
         auto words = [&]() {
-            whm = *P.wh_amax;
-            return lane_word(P.amax_in + (size_t)blk * P.amax_in_n, P.amax_in_n);
+            whm = *h_wh_amax;
+            return lane_word(h_amax_in + (size_t)blk * h_amax_in_n, h_amax_in_n);
         };
         wd_stamp(1 + 8 * LAST);
         floatx4 acc[BM / 64][BN / 16];
@@ -572,8 +619,8 @@ __global__ __launch_bounds__(MP_THREADS, 4) void mp_layer_kernel(const Multi<MpL
                 E.store_pre(R, pre);
             }
         } hook{E, P, B, pre, {}};
-        h2_mainloop_pairs<BM, BN>(P.ain + (size_t)blk * (P.kp >> 5) * CH, P.wh + (size_t)nt * (P.kp >> 5) * (2 * BN * 64),
-                                  P.kp >> 5, rows, words, P.ain_g, lds, acc, se, hook);
+        h2_mainloop_pairs<BM, BN, true>(h_ain + (size_t)blk * (h_kp >> 5) * CH, h_wh + (size_t)nt * (h_kp >> 5) * (2 * BN * 64),
+                                  h_kp >> 5, rows, words, h_ain_g, lds, acc, se, hook);
         wd_stamp(2 + 8 * LAST);
         __syncthreads();
         E.take_pre(B, pre);
@@ -647,15 +694,19 @@ __global__ __launch_bounds__(MP_THREADS, 4) void mp_layer_kernel(const Multi<MpL
 // waits for memory once.
 // ------------------------------------------------------------------------------------------------
 struct EmbedP {
+    // the entry head (19 dwords, adjacent: copied by value at the entry, embed_kernel): everything the up-front
+    // loads' addresses are made of
     const WdAtomCode *codes;     // natural atom rows
     const uint8_t *src_blk;      // per natural bond row: block-local source atom
     const uint16_t *tail;        // per natural bond row: bond columns as bits
     const float *wt;             // W_i^T [>= Fb][Hk] (fp32, packed)
     const float *woat;           // W_o[:, :Fa]^T [>= Fa][Hk] (fp32, packed)
-    float *eo;                   // [atom rows][Hk] (natural rows)
     const float *bias;           // b_i (padded) or null
     const int32_t *blocks;
     int Fa, Fb, Hk, n_tiles;
+    uint32_t tmagic;             // tile_magic(n_tiles) (common.hpp)
+    // ... and what the stores need
+    float *eo;                   // [atom rows][Hk] (natural rows)
     float *inp;                  // [Rp][Hk]
     const float *slope;          // PReLU slope (or null)
     uint32_t *amax;              // [nblk][n_tiles]: max |act(inp)| per workgroup (the first layer's scale, planes.hpp h2)
@@ -666,16 +717,24 @@ struct EmbedP {
 
 // s = sum_{c in code} T[c][c4 .. c4+3] + last * T[Fa - 1][c4 ..] (ascending columns, then the mass column:
 // the order of the f_atoms row's dot product terms that are not zero)
+// Straight-line: the eight slot rows and the mass row are read together and waited for once (a branch per
+// slot made nine dependent LDS round trips).  An absent slot (0xFF) reads row 0 of the tile -- staged, in
+// bounds -- and adds +0.0f in its place by a select.  Bitwise the same sum as skipping it: s starts at +0 and
+// no partial sum of this chain can be -0 (x + y is -0 only for x = y = -0 in round-to-nearest, and s is never
+// -0 by induction), so s + (+0) == s for every s, NaN and infinities included.
 template <int LDT>
 __device__ __forceinline__ float4 code_sum(const WdAtomCode &cd, const float *T, int Fa, int c) {
+    float4 w[8];
+#pragma unroll
+    for (int q = 0; q < 8; ++q) w[q] = ld4(T + (cd.col[q] == 0xFF ? 0 : (int)cd.col[q]) * LDT + c);
+    const float4 wm = ld4(T + (Fa - 1) * LDT + c);
     float4 s = f4zero();
 #pragma unroll
     for (int q = 0; q < 8; ++q) {
-        if (cd.col[q] == 0xFF) continue;
-        const float4 w = ld4(T + cd.col[q] * LDT + c);
-        s.x += w.x; s.y += w.y; s.z += w.z; s.w += w.w;
+        const bool on = cd.col[q] != 0xFF;
+        s.x += on ? w[q].x : 0.f; s.y += on ? w[q].y : 0.f; s.z += on ? w[q].z : 0.f; s.w += on ? w[q].w : 0.f;
     }
-    fma4(s, cd.last, ld4(T + (Fa - 1) * LDT + c));
+    fma4(s, cd.last, wm);
     return s;
 }
 
@@ -693,31 +752,53 @@ __global__ __launch_bounds__(512) void embed_kernel(const Multi<EmbedP, NJ> MP) 
     int tile;
     wd_estamp(0);
     const EmbedP &P = multi_pick(MP, xcd_tile(blockIdx.x, gridDim.x), tile);
-    const int blk = tile / P.n_tiles, nt = tile % P.n_tiles, n0 = nt * BN;
-    const BlockRow B = load_block(P.blocks, blk);
+    // The entry head by value, pinned in scalar registers: one batch of scalar loads and one wait, and every
+    // address below is made of registers (through the reference the compiler re-read Hk and the table pointers
+    // from the argument segment inside each load's branch: a scalar round trip in front of every vector load).
+    const WdAtomCode *h_codes = pin_s(P.codes);
+    const uint8_t *h_src = pin_s(P.src_blk);
+    const uint16_t *h_tail = pin_s(P.tail);
+    const float *h_wt = pin_s(P.wt), *h_woat = pin_s(P.woat), *h_bias = pin_s(P.bias);
+    const int32_t *h_blocks = pin_s(P.blocks);
+    const int h_Fa = pin_s(P.Fa), h_Fb = pin_s(P.Fb), h_Hk = pin_s(P.Hk), h_nt = pin_s(P.n_tiles);
+    const uint32_t h_tm = pin_s(P.tmagic);
+    int blk, nt;
+    tile_split(tile, h_nt, h_tm, blk, nt);
+    const int n0 = nt * BN;
     const int tid = threadIdx.x;
-    // every load up front, in the order their values are needed (codes and bias, the weight tile, the
-    // bonds' source atoms and tails): each wait then covers only what it needs
-    static_assert(sizeof(WdAtomCode) == 16, "codes move as one 16-byte word");
-    u32x4 cd = {0u, 0u, 0u, 0u};  // (raw words: a struct with a byte array went to scratch)
-    if (tid < B.an) cd = reinterpret_cast<const u32x4 *>(P.codes)[B.as + tid];
+    // Every load up front.  The block row (a scalar load) is the one dependent step, and only the codes, the
+    // source atoms and the tails need it: it is issued first, the bias and both weight tiles go out while it
+    // is in flight, and the three loads that use it follow, in the order their values are needed.
+    const BlockRow B = load_block_s(h_blocks, blk);
     float4 bq = f4zero();
-    if (tid >= NT - C4 && P.bias) bq = ld4(P.bias + n0 + 4 * (tid - (NT - C4)));
+    if (tid >= NT - C4 && h_bias) bq = ld4(h_bias + n0 + 4 * (tid - (NT - C4)));
+    // (The weight loads are unconditional: a thread whose row k is past the table reads the table's last row,
+    // in bounds, and never stores it.  Behind a branch each, the register allocator put a copy of a loaded
+    // register into the branch -- and with it a vmcnt(0) wait right behind the load, two memory latencies in a
+    // row at the kernel's entry.)
     float4 ro[PER], ri[PER];
 #pragma unroll
     for (int q = 0; q < PER; ++q) {
         const int v = tid + NT * q, k = v / C4, c = 4 * (v % C4);
-        ro[q] = k < P.Fa ? ld4(P.woat + (size_t)k * P.Hk + n0 + c) : f4zero();
-        ri[q] = k < P.Fb ? ld4(P.wt + (size_t)k * P.Hk + n0 + c) : f4zero();
+        ro[q] = ld4(h_woat + (size_t)min(k, h_Fa - 1) * h_Hk + n0 + c);
     }
+#pragma unroll
+    for (int q = 0; q < PER; ++q) {
+        const int v = tid + NT * q, k = v / C4, c = 4 * (v % C4);
+        ri[q] = ld4(h_wt + (size_t)min(k, h_Fb - 1) * h_Hk + n0 + c);
+    }
+    static_assert(sizeof(WdAtomCode) == 16, "codes move as one 16-byte word");
+    // (raw words: a struct with a byte array went to scratch.  Unconditional, as the weight loads: a thread
+    // past the block's atoms reads the pad atom's row 0 and never stores it.)
+    const u32x4 cd = reinterpret_cast<const u32x4 *>(h_codes)[tid < B.an ? B.as + tid : 0];
     uint32_t sa[BU], tl[BU];
 #pragma unroll
     for (int u = 0; u < BU; ++u) {
         const int v = tid + NT * u, lb = v / U8;
         sa[u] = tl[u] = 0;
         if (lb < B.bn) {
-            sa[u] = P.src_blk[B.bs + lb];
-            tl[u] = P.tail[B.bs + lb];
+            sa[u] = h_src[B.bs + lb];
+            tl[u] = h_tail[B.bs + lb];
         }
     }
     if (tid < B.an) reinterpret_cast<u32x4 *>(code)[tid] = cd;
@@ -730,13 +811,13 @@ __global__ __launch_bounds__(512) void embed_kernel(const Multi<EmbedP, NJ> MP) 
 #pragma unroll
         for (int q = 0; q < PER; ++q) {
             const int v = tid + NT * q, k = v / C4, c = 4 * (v % C4);
-            if (k < P.Fa) st4(wt + k * BN + c, ro[q]);
+            if (k < h_Fa) st4(wt + k * BN + c, ro[q]);
         }
         __syncthreads();
         // Eo[a] = sum_{c in code(a)} W_o[:, c] + last(a) W_o[:, Fa-1] (the f_atoms half of W_o)
         for (int v = tid; v < B.an * C4; v += NT) {
             const int la = v / C4, c = 4 * (v % C4);
-            st4(P.eo + (size_t)(B.as + la) * P.Hk + n0 + c, code_sum<BN>(code[la], wt, P.Fa, c));
+            st4(P.eo + (size_t)(B.as + la) * h_Hk + n0 + c, code_sum<BN>(code[la], wt, h_Fa, c));
         }
     };
     eo_half();
@@ -745,14 +826,14 @@ __global__ __launch_bounds__(512) void embed_kernel(const Multi<EmbedP, NJ> MP) 
 #pragma unroll
     for (int q = 0; q < PER; ++q) {
         const int v = tid + NT * q, k = v / C4, c = 4 * (v % C4);
-        if (k < P.Fb) st4(wt + k * BN + c, ri[q]);
+        if (k < h_Fb) st4(wt + k * BN + c, ri[q]);
     }
     __syncthreads();
     wd_estamp(3);
     // Ea[a] = sum_{c in code(a)} W_i[:, c] + last(a) W_i[:, Fa-1]
     for (int v = tid; v < B.an * C4; v += NT) {
         const int la = v / C4, c = 4 * (v % C4);
-        st4(ea + la * LDC + c, code_sum<BN>(code[la], wt, P.Fa, c));
+        st4(ea + la * LDC + c, code_sum<BN>(code[la], wt, h_Fa, c));
     }
     __syncthreads();
     wd_estamp(4);
@@ -768,7 +849,7 @@ __global__ __launch_bounds__(512) void embed_kernel(const Multi<EmbedP, NJ> MP) 
         const int s_ = (int)sa[u];
         float4 z0 = ld4(ea + s_ * LDC + c), z1 = ld4(ea + s_ * LDC + c + 4);
         for (uint32_t m = tl[u]; m; m &= m - 1) {
-            const float *w = wt + (P.Fa + __builtin_ctz(m)) * BN + c;
+            const float *w = wt + (h_Fa + __builtin_ctz(m)) * BN + c;
             const float4 w0 = ld4(w), w1 = ld4(w + 4);
             z0.x += w0.x; z0.y += w0.y; z0.z += w0.z; z0.w += w0.w;
             z1.x += w1.x; z1.y += w1.y; z1.z += w1.z; z1.w += w1.w;
@@ -776,7 +857,7 @@ __global__ __launch_bounds__(512) void embed_kernel(const Multi<EmbedP, NJ> MP) 
         const float4 b0 = ld4(bb + c), b1 = ld4(bb + c + 4);
         z0.x += b0.x; z0.y += b0.y; z0.z += b0.z; z0.w += b0.w;
         z1.x += b1.x; z1.y += b1.y; z1.z += b1.z; z1.w += b1.w;
-        float *zr = P.inp + (size_t)b * P.Hk + n0 + c;
+        float *zr = P.inp + (size_t)b * h_Hk + n0 + c;
         st4(zr, z0);
         st4(zr + 4, z1);
         float zz[8] = {z0.x, z0.y, z0.z, z0.w, z1.x, z1.y, z1.z, z1.w};
@@ -796,11 +877,11 @@ __global__ __launch_bounds__(512) void embed_kernel(const Multi<EmbedP, NJ> MP) 
     if constexpr (PAIRS) {
         // M_0 = act(inp) as fp16 pairs scaled by this tile's max (rows up to the end of the last 16-row group
         // the layer multiplies: zeros past the block)
-        const float s = h2_scale(publish_max_all(mx, P.amax + (size_t)blk * P.n_tiles + nt, red));
+        const float s = h2_scale(publish_max_all(mx, P.amax + (size_t)blk * h_nt + nt, red));
         wd_estamp(6);
         constexpr int CH = 2 * BLK_BONDS * 64;
         const __amdgpu_buffer_rsrc_t prs = __builtin_amdgcn_make_buffer_rsrc(
-            P.m0 + (size_t)blk * (P.Hk >> 5) * CH, 0, (P.Hk >> 5) * CH, 0x00020000);
+            P.m0 + (size_t)blk * (h_Hk >> 5) * CH, 0, (h_Hk >> 5) * CH, 0x00020000);
 #pragma unroll
         for (int u = 0; u < BU; ++u) {
             const int v = tid + NT * u, lb = v / U8, c = 8 * (v % U8);
@@ -809,35 +890,44 @@ __global__ __launch_bounds__(512) void embed_kernel(const Multi<EmbedP, NJ> MP) 
         }
         wd_estamp(7);
     } else {
-        publish_max(mx, P.amax + (size_t)blk * P.n_tiles + nt, red);
+        publish_max(mx, P.amax + (size_t)blk * h_nt + nt, red);
     }
 }
 
 constexpr int WO_MAXK = 160;  // f_atoms / f_bonds columns embed_kernel stages (Fa, Fb <= 160)
 
 struct WoReadoutP {
+    // The entry head: what the pair kernel reads before its main loop -- the operands, the block row, the scale
+    // words, then what the row's prefetch loads from -- adjacent and first, copied by value at the entry with one
+    // batch of scalar loads (wo_readout_kernel; 28 dwords).  The rest is first touched in the epilogue.
+    const uint8_t *apairs;                   // (the template's PAIRS, below)
+    const uint8_t *woh;
+    const int32_t *blocks;
+    const uint32_t *a_amax, *wo_amax;
+    int kp;                                  // Hk (the A operand's row length)
+    int n_tiles;
+    uint32_t tmagic;                         // tile_magic(n_tiles) (common.hpp)
+    int a_nw, a_g;
+    int ldeo;
+    const float *bias;                       // b_o (padded)
+    const float *w_atoms; const int32_t *mol_start, *mol_size; const float *xn;
+    const float *eo;                         // (kca = 0, below)
     const uint8_t *fa; int kpa; int kca;     // f_atoms: blocked atom plane tiles [nblk * 64][kpa], kca chunks used
     int kcw;                                 // f_atoms chunks in the W_o plane tiles (Fak / 32; kca = 0 or kcw)
-    const uint8_t *ag; int kp;               // A: blocked atom plane tiles [nblk * 64][kp = Hk]
+    const uint8_t *ag;                       // A: blocked atom plane tiles [nblk * 64][kp = Hk]
     const uint8_t *wo;                       // W_o plane tiles [Hk][Fak + Hk] with BN-row blocks
-    const float *bias;                       // b_o (padded)
-    const int32_t *blocks;
-    const float *w_atoms; const int32_t *mol_start, *mol_size; const float *xn;
     int agg; float norm; const float *zero_vec;
     int act; const float *slope; float p_drop; uint64_t seed; uint32_t layer;
     float *out; int ncols;                   // out [B][ncols] (ncols = H)
-    int n_tiles;
     // kca = 0: the f_atoms half of [f_atoms | A] W_o^T, precomputed per atom (by embed_kernel as sums of
     // W_o columns, or by the atom-message input GEMM): fp32 natural atom rows, row stride ldeo (null: GEMM
-    // segment)
-    const float *eo;
-    int Hk, ldeo;
+    // segment): eo, ldeo in the entry head
+    int Hk;
     float *zosave;  // training forward or null: the W_o pre-activation (mpn.py:133) as fp32 natural atom rows [Vap][Hk]
     // the template's PAIRS (round 6): A as fp16 pair tiles of the blocks' atom rows ([nblk][Hk / 32][2][64][64 B],
     // written by the last layer) with its words [nblk][a_nw] (groups of a_g columns), and W_o[:, Fa:] as fp16
     // pair tiles with BN-row blocks scaled by the word wo_amax (wdmpnn_pack_params)
-    const uint8_t *apairs; const uint32_t *a_amax; int a_nw, a_g;
-    const uint8_t *woh; const uint32_t *wo_amax;
+    // (apairs, a_amax, a_nw, a_g, woh, wo_amax: in the entry head)
 };
 
 template <int BN> struct WoWaves;
@@ -866,9 +956,28 @@ __global__ __launch_bounds__(PAIRS ? 512 : 64 * WoWaves<BN>::WM * WoWaves<BN>::W
     __shared__ __attribute__((aligned(16))) uint8_t lds[LDS_BYTES];
     int tile;
     const WoReadoutP &P = multi_pick(MP, xcd_tile(blockIdx.x, gridDim.x), tile);
-    const int blk = tile / P.n_tiles, nt = tile % P.n_tiles, n0 = nt * BN;
-    // (PAIRS: the block row is loaded inside the main loop, by each role where it needs it)
-    BlockRow B = PAIRS ? BlockRow{} : load_block(P.blocks, blk);
+    // the entry head by value (PAIRS: pinned in scalar registers, all of it; as mp_layer_kernel)
+    auto hv = [](auto v) {
+        if constexpr (PAIRS) return pin_s(v);
+        else return v;
+    };
+    const int h_nt = hv(P.n_tiles), h_kp = hv(P.kp), h_ldeo = hv(P.ldeo);
+    const uint32_t h_tm = hv(P.tmagic);
+    const int32_t *h_blocks = hv(P.blocks);
+    const float *h_bias = hv(P.bias), *h_w_atoms = hv(P.w_atoms), *h_xn = hv(P.xn), *h_eo = hv(P.eo);
+    const int32_t *h_mol_start = hv(P.mol_start), *h_mol_size = hv(P.mol_size);
+    const uint8_t *h_apairs = nullptr, *h_woh = nullptr;
+    const uint32_t *h_a_amax = nullptr, *h_wo_amax = nullptr;
+    int h_a_nw = 0, h_a_g = 0;
+    if constexpr (PAIRS) {
+        h_apairs = pin_s(P.apairs); h_woh = pin_s(P.woh); h_a_amax = pin_s(P.a_amax); h_wo_amax = pin_s(P.wo_amax);
+        h_a_nw = pin_s(P.a_nw); h_a_g = pin_s(P.a_g);
+    }
+    int blk, nt;
+    tile_split(tile, h_nt, h_tm, blk, nt);
+    const int n0 = nt * BN;
+    // (PAIRS: a scalar load issued here, waited for by each role where it needs the row: mp_layer_kernel)
+    BlockRow B = PAIRS ? load_block_atoms_s(h_blocks, blk) : load_block(h_blocks, blk);
     const int tid = threadIdx.x;
     X6Operands O{};
     O.a0 = P.fa; O.nkc0 = P.kpa >> 5; O.kc0 = P.kca;
@@ -882,8 +991,9 @@ __global__ __launch_bounds__(PAIRS ? 512 : 64 * WoWaves<BN>::WM * WoWaves<BN>::W
     // (thread a < an: w_atoms[as + a]) and its molecules' scope / Xn (thread i < nm)
     constexpr int C4 = BN / 4;
     static_assert((PAIRS || NT % C4 == 0) && BM <= NT, "one bias group per thread, one atom weight per thread");
-    int nm = min(B.mh - B.ml, BLK_MOLS);  // (the packer never exceeds BLK_MOLS)
-    if (P.zosave && blk == 0 && tid < BN / 4) st4(P.zosave + n0 + 4 * tid, f4zero());  // pad atom row 0
+    int nm = PAIRS ? 0 : min(B.mh - B.ml, BLK_MOLS);  // (the packer never exceeds BLK_MOLS; PAIRS: in rows() below)
+    // (PAIRS: the pad row's store follows the main loop -- zosave is no entry field)
+    if (!PAIRS && P.zosave && blk == 0 && tid < BN / 4) st4(P.zosave + n0 + 4 * tid, f4zero());  // pad atom row 0
     float4 bb = f4zero();
     float watom = 0.f, mxn = 0.f;
     int mstart = 0, msize = 0;
@@ -892,17 +1002,17 @@ __global__ __launch_bounds__(PAIRS ? 512 : 64 * WoWaves<BN>::WM * WoWaves<BN>::W
     float4 eo[EPU];
     auto prefetch = [&](int phase) {
         if (phase != 0) return;
-        if (!PAIRS || tid < C4) bb = ld4(P.bias + n0 + 4 * (tid % C4));  // (PAIRS: staged through LDS below)
-        if (tid < B.an) watom = P.w_atoms[B.as + tid];
+        if (!PAIRS || tid < C4) bb = ld4(h_bias + n0 + 4 * (tid % C4));  // (PAIRS: staged through LDS below)
+        if (tid < B.an) watom = h_w_atoms[B.as + tid];
 #pragma unroll
         for (int j = 0; j < EPU; ++j) {
             const int v = tid + NT * j, la = v / C4, c = 4 * (v % C4);
-            eo[j] = P.eo && v < BM * C4 && la < B.an ? ld4(P.eo + (size_t)(B.as + la) * P.ldeo + n0 + c) : f4zero();
+            eo[j] = h_eo && v < BM * C4 && la < B.an ? ld4(h_eo + (size_t)(B.as + la) * h_ldeo + n0 + c) : f4zero();
         }
         if (tid < nm) {
-            mstart = P.mol_start[B.ml + tid];
-            msize = P.mol_size[B.ml + tid];
-            mxn = P.xn[B.ml + tid];
+            mstart = h_mol_start[B.ml + tid];
+            msize = h_mol_size[B.ml + tid];
+            mxn = h_xn[B.ml + tid];
         }
     };
     float *H = reinterpret_cast<float *>(lds);
@@ -911,20 +1021,20 @@ __global__ __launch_bounds__(PAIRS ? 512 : 64 * WoWaves<BN>::WM * WoWaves<BN>::W
         // the block row and the prefetch that needs it (registers across the GEMM: 16 rows per MFMA wave leave
         // room), per role
         auto rows = [&]() {
-            B = load_block(P.blocks, blk);
             nm = min(B.mh - B.ml, BLK_MOLS);
             prefetch(0);
             return B.an;
         };
         uint32_t wom = 0;  // (W_o's word: loaded by the consumers before their loop, not after it)
         auto words = [&]() {
-            wom = *P.wo_amax;
-            return lane_word(P.a_amax + (size_t)blk * P.a_nw, P.a_nw);
+            wom = *h_wo_amax;
+            return lane_word(h_a_amax + (size_t)blk * h_a_nw, h_a_nw);
         };
         int se;
-        h2_mainloop_pairs<BM, BN>(P.apairs + (size_t)blk * (P.kp >> 5) * (2 * BM * 64),
-                                  P.woh + (size_t)nt * (P.kp >> 5) * (2 * BN * 64), P.kp >> 5, rows, words, P.a_g, lds,
+        h2_mainloop_pairs<BM, BN>(h_apairs + (size_t)blk * (h_kp >> 5) * (2 * BM * 64),
+                                  h_woh + (size_t)nt * (h_kp >> 5) * (2 * BN * 64), h_kp >> 5, rows, words, h_a_g, lds,
                                   acc, se);
+        if (P.zosave && blk == 0 && tid < BN / 4) st4(P.zosave + n0 + 4 * tid, f4zero());  // pad atom row 0
         __syncthreads();
         if (threadIdx.x < 256)
             x6_acc_to_lds<BM, BN, 4, 1, true>(acc, H, se >= 0 ? __uint_as_float((uint32_t)(254 - se) << 23) : 1.f,

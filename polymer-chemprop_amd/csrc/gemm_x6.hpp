@@ -978,6 +978,9 @@ constexpr int h2p_lds_bytes() { return H2P_STAGES * h2p_stage_bytes<BM, BN>(); }
 // "params", profiles/prologue_stamps_*.txt).  The role branch is on a readfirstlane'd wave index: a scalar
 // branch, so what rows() loads stays in scalar registers past the join.
 //
+// (Since "Kernel entry", DESIGN.md §4: the callers issue the block row's scalar load ahead of the role branch, so
+// rows() only reads its registers; with B_FIRST the loaders' first B copies leave before even that.)
+//
 // (Measured, not kept: the loaders' first copies issued before rows(), for all of A's 16-row groups: DESIGN.md
 // "Measured dead ends".  16-row groups past the block's rows are not copied; whatever their LDS rows hold is
 // never multiplied -- `na` -- which tests/test_early_copies_gpu.py checks on a 0xFF-filled workspace.)
@@ -992,7 +995,11 @@ constexpr int h2p_lds_bytes() { return H2P_STAGES * h2p_stage_bytes<BM, BN>(); }
 struct NoLoaderHook {
     __device__ void finish() {}
 };
-template <int BM, int BN, typename Rows, typename Words, typename LoaderHook = NoLoaderHook>
+// B_FIRST: the loaders' B pieces of the first NS - 1 chunks leave before rows() is called (below).  Only where
+// rows() issues no vector-memory instruction of its own (the layers: a scalar load): between an untracked copy
+// and the constant wait that covers it nothing else may be in flight (tests/test_dma_waits.py).  W_o's rows()
+// prefetches the readout's operands, so its loaders keep the order rows(), A, B.
+template <int BM, int BN, bool B_FIRST = false, typename Rows, typename Words, typename LoaderHook = NoLoaderHook>
 __device__ __forceinline__ void h2_mainloop_pairs(const uint8_t *a_src, const uint8_t *b_src, int nchunks, Rows &&rows,
                                                   Words &&words, int G, uint8_t *lds, floatx4 (&acc)[BM / 64][BN / 16],
                                                   int &se_out, LoaderHook &&lhook = LoaderHook()) {
@@ -1033,29 +1040,48 @@ __device__ __forceinline__ void h2_mainloop_pairs(const uint8_t *a_src, const ui
         bool on[APW + BPW];
 #pragma unroll
         for (int j = 0; j < BPW; ++j) on[APW + j] = BP % 4 == 0 || 4 * j + w4 < BP;
+        auto issue_a = [&](int kc) {
+            uint8_t *st = lds + ((kc + roff) % NS) * STAGE;
+            const uint8_t *ablk = a_src + (size_t)kc * (2 * APL);
+#pragma unroll
+            for (int j = 0; j < APW; ++j)
+                if (on[j]) glds16_untracked(ablk + src[j], st + dst[j]);
+        };
+        auto issue_b = [&](int kc) {
+            uint8_t *st = lds + ((kc + roff) % NS) * STAGE;
+            const uint8_t *bblk = b_src + (size_t)kc * (2 * BPL);
+#pragma unroll
+            for (int j = 0; j < BPW; ++j)
+                if (on[APW + j]) glds16_untracked(bblk + src[APW + j], st + dst[APW + j]);
+        };
+        auto issue = [&](int kc) {
+            issue_a(kc);
+            issue_b(kc);
+        };
+        // B_FIRST: the B pieces of the first NS - 1 chunks leave at once: they depend on nothing but the kernel
+        // arguments (the weight tile), not on the block row.  Then the row (rows(): a scalar load, no vector
+        // wait), then the A pieces of those chunks for the live 16-row groups.
+        if constexpr (B_FIRST)
+#pragma unroll
+            for (int c = 0; c < NS - 1; ++c)
+                if (c < nchunks) issue_b(c);
         const int a_rows = rows();
-        int mine = 0;
+        int mine = 0, mb = 0;
 #pragma unroll
         for (int j = 0; j < APW; ++j) {
             on[j] = 16 * ((4 * j + w4) % (BM / 16)) < a_rows;  // 16-row groups past the block's rows: not copied
             mine += on[j];
         }
 #pragma unroll
-        for (int j = 0; j < BPW; ++j) mine += on[APW + j];
-        mine = __builtin_amdgcn_readfirstlane(mine);  // (wave-uniform: a scalar wait below)
-        auto issue = [&](int kc) {
-            uint8_t *st = lds + ((kc + roff) % NS) * STAGE;
-            const uint8_t *ablk = a_src + (size_t)kc * (2 * APL), *bblk = b_src + (size_t)kc * (2 * BPL);
-#pragma unroll
-            for (int j = 0; j < APW; ++j)
-                if (on[j]) glds16_untracked(ablk + src[j], st + dst[j]);
-#pragma unroll
-            for (int j = 0; j < BPW; ++j)
-                if (on[APW + j]) glds16_untracked(bblk + src[APW + j], st + dst[APW + j]);
-        };
+        for (int j = 0; j < BPW; ++j) mb += on[APW + j];
+        mine = __builtin_amdgcn_readfirstlane(mine + mb);  // (wave-uniform: a scalar wait below)
+        mb = __builtin_amdgcn_readfirstlane(mb);            // (BPW, or BPW - 1 where BP % 4 != 0)
 #pragma unroll
         for (int c = 0; c < NS - 1; ++c)
-            if (c < nchunks) issue(c);
+            if (c < nchunks) {
+                if constexpr (B_FIRST) issue_a(c);
+                else issue(c);
+            }
         // the loop instantiated per copy count (its steady-state wait a constant: a wait on a runtime count
         // is a scalar branch search per chunk, ~300 cycles of the chunk period in tools/ring_probe.hip; the
         // last chunk, with nothing younger in flight, waits for zero).
@@ -1063,9 +1089,28 @@ __device__ __forceinline__ void h2_mainloop_pairs(const uint8_t *a_src, const ui
         // order.  Before chunk kc's wait the wave has issued chunks 0 .. min(kc + NS - 2, nchunks - 1), every
         // one of exactly M copies and nothing else, so "at most n * M outstanding" with n = the number of
         // chunks younger than kc means that chunk kc, and all before it, landed.
+        // B_FIRST changes the issue order of the first NS - 1 = 2 chunks to B(0), B(1), A(0), A(1); from chunk 2 on
+        // it is A(c), B(c) as before.  The old invariant holds for every kc >= 1: when chunk 1's wait runs, A(2)
+        // and B(2) have been issued behind A(1), a whole chunk of M copies, and so on.  Chunk 0 is different:
+        // behind A(0)'s last copy there are only A(1)'s copies -- B(0) and B(1) went before A(0) and have landed
+        // when it has -- so its wait allows M - mb outstanding, mb = this wave's B pieces per chunk.  mb takes
+        // two values (BPW, or BPW - 1 for the waves without a last piece), so chunk 0 is peeled off the loop
+        // with one scalar branch and every count stays a constant.  Without B_FIRST chunk 0 waits as the others.
         dispatch_upto<APW + BPW>(mine, [&](auto m_c) {
             constexpr int M = decltype(m_c)::value;
-            for (int kc = 0; kc < nchunks; ++kc) {
+            static_assert(NS == 3, "the peeled first chunk: one younger chunk's A pieces in flight");
+            if (nchunks > 0) {
+                if (WD_STAMPS && wave == 4) wd_lstamp(0, 4);
+                constexpr int W0 = M > BPW ? M - BPW : 0, W1 = M > BPW - 1 ? M - (BPW - 1) : 0;
+                if (nchunks < 2) asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+                else if (!B_FIRST) asm volatile("s_waitcnt vmcnt(%0)" ::"n"((NS - 2) * M) : "memory");
+                else if (mb == BPW) asm volatile("s_waitcnt vmcnt(%0)" ::"n"(W0) : "memory");
+                else asm volatile("s_waitcnt vmcnt(%0)" ::"n"(W1) : "memory");
+                if (WD_STAMPS && wave == 4) wd_lstamp(0, 5);
+                __builtin_amdgcn_s_barrier();
+                if (NS - 1 < nchunks) issue(NS - 1);
+            }
+            for (int kc = 1; kc < nchunks; ++kc) {
                 // chunk kc landed (chunks kc + 1 .. kc + NS - 2 may stay in flight); after the barrier every
                 // consumer is done reading stage (kc + NS - 1 + roff) % NS (chunk kc - 1's)
                 if (WD_STAMPS && wave == 4) wd_lstamp(kc, 4);

@@ -920,11 +920,12 @@ int fused_input(const FusedCtx &X) {
             E.codes = g->atom_codes; E.src_blk = g->bond_src_blk; E.tail = g->bond_tail;
             E.wt = X.W(PL.WiT); E.woat = X.W(PL.WoaT); E.eo = X.F(J, J.L.Eo); E.bias = X.p->b_i ? X.W(PL.bi) : nullptr;
             E.blocks = g->blocks;
-            E.Fa = J.D.Fa; E.Fb = J.D.Fb; E.Hk = Hk; E.n_tiles = D0.etiles;
+            E.Fa = J.D.Fa; E.Fb = J.D.Fb; E.Hk = Hk; E.n_tiles = D0.etiles; E.tmagic = tile_magic(D0.etiles);
             E.inp = X.F(J, J.L.Z[0]);
             E.slope = X.p->prelu; E.amax = X.slot(J, 0);
             E.m0 = D0.lay_pairs ? (uint8_t *)(J.ws + J.L.Mp[0]) : nullptr;
         }, M);
+        if (!tile_magic_ok(grid, D0.etiles)) return fail(WD_ERR_SHAPE, "fused forward: %d embed tiles", grid);
         host_with_act(X.c->activation, [&](auto act_c) {
             constexpr int A = decltype(act_c)::value;
             with_jobs(X.n, M, [&](const auto &Mn, auto nj) {
@@ -1008,7 +1009,7 @@ int fused_layer(const FusedCtx &X, int t) {
         Q.aptr = g->atom_gather.ptr; Q.aidx = g->atom_gather.idx; Q.acoef = g->atom_gather.coef;
         Q.aell_idx = g->atom_ell_idx; Q.aell_coef = g->atom_ell_coef;
         Q.aplanes = (uint8_t *)(J.ws + J.L.Ab);
-        Q.n_tiles = Hk / BN;
+        Q.n_tiles = Hk / BN; Q.tmagic = tile_magic(Hk / BN);
         Q.zsave = J.D.save && last ? X.F(J, J.L.Z[t]) : nullptr;
         Q.asave = J.D.save && last ? X.F(J, J.L.A) : nullptr;
         if (pairs) {  // M_{t-1} from the pair tiles of its producer (no Z_t in inference)
@@ -1022,6 +1023,8 @@ int fused_layer(const FusedCtx &X, int t) {
             Q.amax_out = X.slot(J, t);
         }
     }, M);
+    // (the kernels' division-free tile decode is exact for tile < 2^32 / n_tiles: common.hpp tile_split)
+    if (!tile_magic_ok(grid, Hk / BN)) return fail(WD_ERR_SHAPE, "fused forward: %d layer tiles", grid);
     // one instantiation per (tile width, last layer, activation, batches per launch)
     auto go = [&](auto bn_c, auto last_c) {
         constexpr int BNc = decltype(bn_c)::value;
@@ -1068,7 +1071,7 @@ int fused_wo_readout(const FusedCtx &X) {
         R.w_atoms = g->w_atoms; R.mol_start = g->mol_start; R.mol_size = g->mol_size; R.xn = g->degree_of_polym;
         R.agg = X.c->aggregation; R.norm = X.c->aggregation_norm; R.zero_vec = X.p->zero_vec;
         R.act = X.c->activation; R.slope = X.p->prelu; R.p_drop = X.c->dropout; R.seed = X.c->seed; R.layer = J.D.T;
-        R.out = J.out; R.ncols = J.D.H; R.n_tiles = Hk / BN;
+        R.out = J.out; R.ncols = J.D.H; R.n_tiles = Hk / BN; R.tmagic = tile_magic(Hk / BN);
         R.zosave = J.D.save ? X.F(J, J.L.Zo) : nullptr;
         if (D0.V.wo_dump && J.D.T == 3)  // (tools/debug_pairs.py)
             R.zosave = D0.lay_pairs ? X.F(J, J.L.Mp[1]) : X.F(J, J.L.Zb[1]);
@@ -1078,6 +1081,7 @@ int fused_wo_readout(const FusedCtx &X) {
         }
     }, M);
     if (grid <= 0) return 0;
+    if (!tile_magic_ok(grid, Hk / BN)) return fail(WD_ERR_SHAPE, "fused forward: %d W_o tiles", grid);
     with_jobs(X.n, M, [&](const auto &Mn, auto nj) {
         constexpr int NJ = decltype(nj)::value;
         // one batch: single-chunk stages (55 KB, co-resident with other streams' layers); several: two
