@@ -45,7 +45,9 @@ restated here:
   ``ensemble.EnsembleAccumulator`` on the device, and the top-level scores and ``test_preds.csv`` are the ensemble's;
 * ``--device_metrics``: the per-epoch validation and training scores and a single model's test scores come from
   ``evaluate.evaluate`` (resident targets, partial sums on the device) instead of ``predict`` +
-  ``evaluate_predictions``; the same files are written.
+  ``evaluate_predictions``; the same files are written;
+* every prediction above walks its split with ``predict.device_predictions``: ``predict`` copies the batches to the
+  host, the ensemble's accumulator and ``evaluate``'s evaluator take them where the head wrote them.
 
 ``chemprop_predict`` (``python -m chemprop_amd.cli predict --test_path CSV --graphs_path NPZ --preds_path OUT
 --checkpoint_dir D | --checkpoint_path P | --checkpoint_paths P ...``) is make_predictions.py's counterpart: the
@@ -77,13 +79,16 @@ import torch
 from ._native import ENSEMBLE_MAX_MODELS
 from .args import TrainArgs
 from .featurization import BatchMolGraph
-from .features import FeatureTable, join_features
+from .ensemble import EnsembleAccumulator, accumulate_model, make_batches, predict_ensemble
+from .evaluate import Evaluator, TargetTable, evaluate
+from .features import FeatureTable
 from .graph_io import load_graphs
 from .model import MoleculeModel
 from .nn_utils import initialize_weights
 from .polymer import split_polymer_string, parse_polymer_rules
 from .spectra_utils import load_phase_mask, normalize_spectra, phase_row_mask, sid_metric, wasserstein_metric
-from .train import NoamLR, _predict_head, build_optimizer, frozen_encodings, get_loss_func, head_predict, train_step
+from .predict import device_predictions
+from .train import NoamLR, _predict_head, build_optimizer, frozen_encodings, get_loss_func, train_step
 
 
 class StandardScaler:
@@ -306,58 +311,43 @@ def evaluate_predictions(preds, targets, num_tasks: int, metrics: List[str], dat
 
 def predict(model, graphs, idx, batch_size: int, scaler: Optional[StandardScaler],
             encodings: Optional[torch.Tensor] = None, features=None, spectra_mask=None) -> List[List[float]]:
-    """predict.py:10-68: eval, no_grad, batches in order, inverse scaling.  ``encodings``: the rows of ``idx``
-    from ``frozen_encodings`` (a frozen encoder's outputs, computed once per run): the native prediction head
-    on them in place of the model's forward.  ``features``: the input feature rows of the whole data set
-    (numpy rows, indexed by ``idx``), or the split's own ``features.FeatureTable`` (row k = ``idx[k]``'s
-    features, on the device: each batch is then a slice of one index upload, joined to the encodings by one
-    launch).  A spectra model's predictions are normalised per row on the device
-    (make_predictions.py:175-181): ``spectra_mask`` is the bool ``[len(idx)][T]`` array of the positions each
-    row's phase includes (None: all), uploaded once per batch; excluded positions come back as None."""
+    """predict.py:10-68: eval, no_grad, batches in order, inverse scaling: the batches of
+    ``predict.device_predictions`` copied to the host.  ``encodings``: the rows of ``idx`` from ``frozen_encodings``
+    (a frozen encoder's outputs, computed once per run): the native prediction head on them in place of the
+    model's forward (``NotImplementedError`` for an FFN the native heads refuse; the same for a spectra model).
+    ``features``: the input feature rows of the whole data set (numpy rows, indexed by ``idx``), or the split's
+    own ``features.FeatureTable`` (row k = ``idx[k]``'s features).  A spectra model's predictions are normalised
+    per row on the device (make_predictions.py:175-181): ``spectra_mask`` is the bool ``[len(idx)][T]`` array of
+    the positions each row's phase includes (None: all), uploaded once; excluded positions come back as None.
+    The ``BatchMolGraph`` s of the whole split are held at once."""
     model.eval()
-    preds = []
+    if not len(idx):
+        return []
+    device = next(model.parameters()).device
     spectra = bool(getattr(model, 'spectra', False))
-    findex = None
-    if isinstance(features, FeatureTable):
-        if len(features) != len(idx):
-            raise ValueError(f'a feature table of {len(features)} rows for {len(idx)} molecules')
-        findex = features.index(range(len(idx)))
-
-    def batch_features(s):
-        if features is None:
-            return None
-        return findex[s:s + batch_size] if findex is not None else [features[i] for i in idx[s:s + batch_size]]
-
-    def cached_rows(s):  # (the head's input from cached encodings: their rows, joined with the batch's features)
-        emb = encodings[s:s + batch_size]
-        f = batch_features(s)
-        if f is None:
-            return emb
-        if findex is None:
-            f = torch.from_numpy(np.stack(f)).float().to(emb.device)
-        return join_features(emb, f)
-    with torch.no_grad():
-        for s in range(0, len(idx), batch_size):
-            if spectra:
-                dev = next(model.parameters()).device
-                if encodings is not None:
-                    emb = cached_rows(s)
-                else:
-                    g = BatchMolGraph([graphs[i] for i in idx[s:s + batch_size]])
-                    emb = model.encoder([g], batch_features(s))
-                m = None if spectra_mask is None else \
-                    torch.from_numpy(np.ascontiguousarray(spectra_mask[s:s + batch_size])).to(dev)
-                out = head_predict(model, emb, normalize=True, mask=m).cpu().numpy()
-                preds.extend([[None if math.isnan(v) else v for v in row] for row in out.tolist()])
-                continue
-            if encodings is not None:
-                preds.extend(head_predict(model, cached_rows(s)).cpu().numpy().tolist())
-                continue
-            g = BatchMolGraph([graphs[i] for i in idx[s:s + batch_size]])
-            preds.extend(model([g], batch_features(s)).cpu().numpy().tolist())
-    if scaler is not None and preds:
+    if features is not None and not isinstance(features, FeatureTable):
+        features = FeatureTable(np.stack([features[i] for i in idx]), device)
+    if features is not None and len(features) != len(idx):
+        raise ValueError(f'a feature table of {len(features)} rows for {len(idx)} molecules')
+    native = spectra or encodings is not None
+    if native and _predict_head(model) is None:
+        raise NotImplementedError('predict: the model\'s FFN is not one the native prediction heads run')
+    batches = batch_size if encodings is not None else make_batches([graphs[i] for i in idx], batch_size)
+    outs = device_predictions(model, batches, features, device_mask(spectra_mask, device) if spectra else None,
+                              encodings, own_forward=not native, n_rows=len(idx))
+    preds = torch.cat([out for _, out in outs]).cpu().numpy().tolist()
+    if spectra:
+        preds = [[None if math.isnan(v) else v for v in row] for row in preds]
+    if scaler is not None:
         preds = scaler.inverse_transform(preds).tolist()
     return preds
+
+
+def device_mask(mask, device, idx=None) -> Optional[torch.Tensor]:
+    """The rows ``idx`` (None: all) of a spectra phase mask ``[N][T]`` on the device; None for no mask or no rows."""
+    if mask is None or (idx is not None and not len(idx)):
+        return None
+    return torch.from_numpy(np.ascontiguousarray(mask if idx is None else mask[idx])).to(device)
 
 
 def read_csv(path: str):
@@ -622,13 +612,10 @@ def run_training(a: argparse.Namespace) -> Dict[str, list]:
     # scored by evaluate.evaluate without a host copy per batch
     device_metrics = bool(getattr(a, 'device_metrics', False))
     if device_metrics:
-        from .ensemble import make_batches
-        from .evaluate import Evaluator, TargetTable, evaluate
         split_idx = dict(splits)
         split_targets = {name: TargetTable([targets[i] for i in idx], a.dataset_type, device,
                                            a.multiclass_num_classes, num_tasks=num_tasks) for name, idx in splits}
-        split_masks = {name: None if row_mask is None or not len(idx) else
-                       torch.from_numpy(np.ascontiguousarray(row_mask[idx])).to(device) for name, idx in splits}
+        split_masks = {name: device_mask(row_mask, device, idx) for name, idx in splits}
         split_batches = {}
 
     def score_on_device(model, enc_cache, name, keep=False):
@@ -726,12 +713,10 @@ def run_training(a: argparse.Namespace) -> Dict[str, list]:
     else:
         # run_training.py:208-499: model k trains into save_dir/model_k; every model's test predictions are folded
         # into one accumulator on the device, and the top-level scores and predictions are the ensemble's
-        from .ensemble import EnsembleAccumulator, accumulate_model, make_batches
         width = num_tasks * (a.multiclass_num_classes if multiclass else 1)
         acc = EnsembleAccumulator(len(test_idx), width, device, keep=True, n_models=a.ensemble_size)
         test_batches = make_batches([graphs[i] for i in test_idx], a.batch_size)
-        test_mask = None if row_mask is None or not len(test_idx) else \
-            torch.from_numpy(np.ascontiguousarray(row_mask[test_idx])).to(device)
+        test_mask = device_mask(row_mask, device, test_idx)
         best_epoch = []
         for k in range(a.ensemble_size):
             model_dir = os.path.join(a.save_dir, f'model_{k}')
@@ -940,7 +925,6 @@ def check_polymer_rows(smiles: List[str], graphs) -> None:
 def make_predictions(a: argparse.Namespace):
     """make_predictions.py:272-372 for this package's checkpoints: the ensemble's predictions of ``--test_path``
     written to ``--preds_path``; returns the mean predictions ``[N][W]`` (float64)."""
-    from .ensemble import predict_ensemble
     paths = checkpoint_paths_of(a)
     if len(paths) > ENSEMBLE_MAX_MODELS:
         raise ValueError(f'{len(paths)} checkpoints (an ensemble holds at most {ENSEMBLE_MAX_MODELS})')

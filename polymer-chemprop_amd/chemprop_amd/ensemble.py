@@ -5,9 +5,8 @@ The reference sums each model's fp32 predictions into a numpy float64 array on t
 and model.  Here a model's predictions stay where the head wrote them: ``EnsembleAccumulator.add`` folds a
 batch into float64 running statistics in one ``wdmpnn_ensemble_add`` launch (Welford's update, with the model's
 own inverse target scaling applied in double as ``scaler.py`` does), and the results leave the device once,
-after the last model.  ``predict_ensemble`` is the loop around it: per model, the batches in groups of eight
-through ``MPNEncoder.forward_many``, ``join_features`` for a model with input features, the native prediction
-head, the accumulator.
+after the last model.  ``predict_ensemble`` is the loop over the models; ``accumulate_model`` hands one model's
+batches from ``predict.device_predictions``, the package's one prediction loop, to the accumulator.
 """
 from __future__ import annotations
 
@@ -18,12 +17,13 @@ import numpy as np
 import torch
 
 from . import _native
-from .features import FeatureTable, join_features
+from .features import FeatureTable
 from .featurization import BatchMolGraph
+from .predict import PredictionSink, _fallback_predict, device_predictions  # noqa: F401 (_fallback_predict: as before)
 from .spectra_utils import phase_row_mask
 
 
-class EnsembleAccumulator:
+class EnsembleAccumulator(PredictionSink):
     """Float64 running statistics of an ensemble's predictions for a data set of ``n_rows`` rows and ``width``
     cells per row (tasks, spectrum positions, or tasks x classes taken flat), on ``device``.
 
@@ -31,6 +31,7 @@ class EnsembleAccumulator:
     slab per model (``n_models`` slabs: the count is then needed up front); ``individual`` and ``roundrobin_sid``
     read them.  Nothing is zeroed: model 0's ``add`` initialises the rows it covers, so every row must get its
     models in the order 0, 1, 2, ...; the order is checked on the host (``ValueError``), the kernel trusts it."""
+    _noun = 'accumulator'
 
     def __init__(self, n_rows: int, width: int, device, variance: bool = False, keep: bool = False,
                  n_models: Optional[int] = None):
@@ -39,7 +40,7 @@ class EnsembleAccumulator:
         if keep and (n_models is None or not 1 <= n_models <= _native.ENSEMBLE_MAX_MODELS):
             raise ValueError(f'EnsembleAccumulator(keep=True) needs n_models in 1 .. {_native.ENSEMBLE_MAX_MODELS} '
                              f'(got {n_models})')
-        self.n_rows, self.width, self.device = int(n_rows), int(width), torch.device(device)
+        super().__init__(n_rows, width, device)
         self.n_models = n_models
 
         def buf(*shape):
@@ -48,35 +49,12 @@ class EnsembleAccumulator:
         self._m2 = buf(n_rows, width) if variance else None
         self._slabs = buf(n_models, n_rows, width) if keep else None
         self._count = np.zeros(n_rows, dtype=np.int64)  # models folded into each row so far (host bookkeeping)
-        self._scales = {}
-
-    def _scale(self, scaler):
-        """(means, stds) of ``scaler`` as float64 device tensors, uploaded once per scaler."""
-        hit = self._scales.get(id(scaler))
-        if hit is None:
-            means = np.ascontiguousarray(np.asarray(scaler.means, dtype=np.float64).reshape(-1))
-            stds = np.ascontiguousarray(np.asarray(scaler.stds, dtype=np.float64).reshape(-1))
-            if means.shape != (self.width,) or stds.shape != (self.width,):
-                raise ValueError(f'a scaler of {means.shape[0]} means and {stds.shape[0]} stds for predictions of '
-                                 f'width {self.width}')
-            hit = (scaler, torch.from_numpy(means).to(self.device), torch.from_numpy(stds).to(self.device))
-            self._scales[id(scaler)] = hit
-        return hit[1], hit[2]
 
     def add(self, pred: torch.Tensor, row0: int, k: int, scaler=None) -> None:
         """Fold model ``k``'s predictions ``pred`` (float32 on the device, ``[B][width]`` or ``[B][tasks][classes]``)
         for rows ``row0 .. row0 + B`` into the statistics: one launch, no host sync.  ``scaler``: the model's
         target scaler (``means`` / ``stds`` of length ``width``); the predictions are inverse-scaled in double."""
-        if not torch.is_tensor(pred) or pred.dtype != torch.float32 or pred.device != self._mean.device or \
-                pred.dim() < 2:
-            raise ValueError('EnsembleAccumulator.add expects float32 predictions [B][width] on the accumulator\'s '
-                             'device')
-        pred = pred.detach().reshape(pred.shape[0], -1).contiguous()
-        B = int(pred.shape[0])
-        if pred.shape[1] != self.width:
-            raise ValueError(f'predictions of width {pred.shape[1]} for an accumulator of width {self.width}')
-        if row0 < 0 or row0 + B > self.n_rows:
-            raise ValueError(f'rows {row0} .. {row0 + B} outside the accumulator\'s {self.n_rows} rows')
+        pred, B = self._batch(pred, row0)
         if not 0 <= k < _native.ENSEMBLE_MAX_MODELS or (self._slabs is not None and k >= self.n_models):
             raise ValueError(f'model {k} of an ensemble of at most '
                              f'{self.n_models if self._slabs is not None else _native.ENSEMBLE_MAX_MODELS}')
@@ -87,7 +65,7 @@ class EnsembleAccumulator:
         e = _native.WdEnsembleAdd()
         e.pred, e.ld_pred, e.B, e.W, e.k, e.row0 = pred.data_ptr(), self.width, B, self.width, k, row0
         if scaler is not None:
-            means, stds = self._scale(scaler)
+            means, stds = self._scale(scaler, self.width)
             e.scale_mean, e.scale_std = means.data_ptr(), stds.data_ptr()
         e.mean, e.m2, e.ld_acc = self._mean.data_ptr(), _native.ptr(self._m2), self.width
         e.keep = self._slabs[k].data_ptr() if self._slabs is not None else None
@@ -145,58 +123,13 @@ def make_batches(graphs: Sequence, batch_size: int) -> list:
     return [BatchMolGraph(list(graphs[s:s + batch_size])) for s in range(0, len(graphs), batch_size)]
 
 
-def _fallback_predict(model, batch, feats, mask) -> torch.Tensor:
-    """A model whose FFN the native prediction heads refuse: its own forward (a spectra model's output
-    normalised per row with torch ops, as ``head_predict(normalize=True)`` does it natively)."""
-    out = model([batch], feats)
-    if getattr(model, 'spectra', False):
-        m = torch.ones_like(out, dtype=torch.bool) if mask is None else mask.bool()
-        s = torch.where(m, out, torch.zeros_like(out))
-        out = torch.where(m, s / s.sum(dim=1, keepdim=True), torch.full_like(out, float('nan')))
-    return out
-
-
-def accumulate_model(acc: EnsembleAccumulator, k: int, model, batches: Sequence[BatchMolGraph], scaler=None,
-                     table: Optional[FeatureTable] = None, row_mask: Optional[torch.Tensor] = None) -> None:
-    """Model ``k``'s predictions of ``batches`` (row order = batch order) into ``acc``.  ``table``: the model's
-    input features of every row, as the model sees them; ``row_mask``: a spectra model's included positions,
-    bool or uint8 ``[rows][T]`` on the device.  No host sync: the batches run in groups of up to eight through
-    ``forward_many``, then per batch ``join_features``, the native prediction head and ``acc.add``."""
-    from .train import _predict_head, head_predict
-    model.eval()
-    mpn = model.encoder
-    needs = bool(getattr(mpn, 'use_input_features', False))
-    if needs and table is None:
-        raise ValueError(f'model {k} takes input features and none were given')
-    if not needs and table is not None:
-        raise ValueError(f'model {k} takes no input features, but features were given')
-    sizes = [len(b.a_scope) for b in batches]
-    starts = np.cumsum([0] + sizes).tolist()
-    if starts[-1] != acc.n_rows or (table is not None and len(table) != acc.n_rows):
-        raise ValueError(f'{starts[-1]} molecules and {None if table is None else len(table)} feature rows for an '
-                         f'accumulator of {acc.n_rows} rows')
-    findex = table.index(range(acc.n_rows)) if table is not None and acc.n_rows else None
-    spectra = bool(getattr(model, 'spectra', False))
-    head = _predict_head(model)
-    many = head is not None and not mpn.features_only and len(mpn.encoder) == 1 and mpn.atom_descriptors is None
-    with torch.no_grad():
-        for g0 in range(0, len(batches), 8):
-            group = batches[g0:g0 + 8]
-            embs = mpn.encoder[0].forward_many(group) if many else [None] * len(group)
-            for j, emb in enumerate(embs):
-                r0, r1 = starts[g0 + j], starts[g0 + j + 1]
-                feats = None if findex is None else findex[r0:r1]
-                mask = None if row_mask is None or not spectra else row_mask[r0:r1]
-                if head is None:
-                    out = _fallback_predict(model, group[j], feats, mask)
-                else:
-                    if emb is None:
-                        x = mpn([group[j]], feats)
-                    else:
-                        x = emb if feats is None else join_features(emb, feats)
-                    out = head_predict(model, x, head, normalize=True, mask=mask) if spectra else \
-                        head_predict(model, x, head)
-                acc.add(out, r0, k, scaler)
+def accumulate_model(acc: PredictionSink, k: int, model, batches, scaler=None, table: Optional[FeatureTable] = None,
+                     row_mask: Optional[torch.Tensor] = None, encodings: Optional[torch.Tensor] = None) -> None:
+    """Model ``k``'s predictions of ``batches`` into ``acc``, an ``EnsembleAccumulator`` or an ``Evaluator``: every
+    batch of ``predict.device_predictions`` (which explains the other arguments) through ``acc.add``.  No host
+    sync."""
+    for r0, out in device_predictions(model, batches, table, row_mask, encodings, n_rows=acc.n_rows):
+        acc.add(out, r0, k, scaler)
 
 
 def _open_model(item, device):

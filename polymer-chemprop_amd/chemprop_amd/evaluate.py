@@ -4,9 +4,9 @@
 floats and call sklearn once per task and metric.  Here the targets of a split are uploaded once
 (``TargetTable``), every batch's fp32 predictions are folded where the head wrote them into float64 partial sums
 (``Evaluator.add``: one ``wdmpnn_eval_add`` or ``wdmpnn_eval_spectra`` launch, no host sync), and ``scores()``
-copies a few numbers per task back and finishes the metrics on the host in float64.  ``evaluate`` is the loop
-around it, the one of ``ensemble.accumulate_model``: the batches in groups of eight through
-``MPNEncoder.forward_many``, ``join_features``, the native prediction head, the evaluator.
+copies a few numbers per task back and finishes the metrics on the host in float64.  ``evaluate`` fills an
+evaluator through ``ensemble.accumulate_model`` from ``predict.device_predictions``, the package's one prediction
+loop, and returns its scores.
 
 The metrics computed from partials: rmse, mse, mae, r2 (regression); auc, cross_entropy, accuracy
 (classification); cross_entropy, accuracy (multiclass); sid, wasserstein (spectra).  Any other metric that
@@ -23,7 +23,8 @@ import numpy as np
 import torch
 
 from . import _native
-from .features import FeatureTable, join_features
+from .features import FeatureTable
+from .predict import PredictionSink
 
 DEVICE_METRICS = {'regression': ('rmse', 'mse', 'mae', 'r2'),
                   'classification': ('auc', 'cross_entropy', 'accuracy'),
@@ -155,29 +156,28 @@ def finish_scores(table: TargetTable, metrics: Sequence[str], partials=None, sid
     return out
 
 
-class Evaluator:
+class Evaluator(PredictionSink):
     """Running scores of one split's predictions against its ``TargetTable``.
 
     ``add(pred, row0)`` folds a batch (float32 on the table's device, ``[B][tasks]``, ``[B][tasks][classes]`` or
-    ``[B][T]`` spectra positions) for rows ``row0 .. row0 + B``: one launch, no host sync; it also takes
-    ``EnsembleAccumulator.add``'s ``(pred, row0, k, scaler)``, so ``ensemble.accumulate_model`` drives an evaluator
-    as it drives an accumulator.  ``scaler``: the regression targets' scaler (``means`` / ``stds``), applied to the
-    predictions in double as ``scaler.inverse_transform`` does.  ``keep``: also hold the (inverse-scaled)
-    predictions, ``[N][W]`` float64 for regression and float32 (exactly what the head wrote) otherwise; AUC and
-    the metrics outside ``DEVICE_METRICS`` read them, so they switch it on themselves.  Every row is added once.
-    ``scores()``: one small device-to-host copy, then ``finish_scores``."""
+    ``[B][T]`` spectra positions) for rows ``row0 .. row0 + B``: one launch, no host sync; as a ``PredictionSink``
+    it has ``EnsembleAccumulator.add``'s ``(pred, row0, k, scaler)``, of which it takes model 0 alone.  ``scaler``:
+    the regression targets' scaler (``means`` / ``stds``), applied to the predictions in double as
+    ``scaler.inverse_transform`` does.  ``keep``: also hold the (inverse-scaled) predictions, ``[N][W]`` float64
+    for regression and float32 (exactly what the head wrote) otherwise; AUC and the metrics outside
+    ``DEVICE_METRICS`` read them, so they switch it on themselves.  Every row is added once.  ``scores()``: one
+    small device-to-host copy, then ``finish_scores``."""
+    _noun = 'split'
 
     def __init__(self, table: TargetTable, metrics: Sequence[str], dataset_type: Optional[str] = None, scaler=None,
                  keep: bool = False):
         dataset_type = table.dataset_type if dataset_type is None else dataset_type
         if dataset_type != table.dataset_type:
             raise ValueError(f'an evaluator for "{dataset_type}" on a "{table.dataset_type}" target table')
-        self.table, self.metrics, self.dataset_type = table, list(metrics), dataset_type
-        self.device, self.n_rows = table.device, table.n_rows
-        self.scaler = scaler
         if scaler is not None and dataset_type != 'regression':
             raise ValueError('a target scaler belongs to regression')
-        self.width = table.num_tasks * table.num_classes
+        super().__init__(table.n_rows, table.num_tasks * table.num_classes, table.device)
+        self.table, self.metrics, self.dataset_type, self.scaler = table, list(metrics), dataset_type, scaler
         self._native_metrics = [m for m in self.metrics if m in DEVICE_METRICS[dataset_type]]
         self._host_metrics = [m for m in self.metrics if m not in DEVICE_METRICS[dataset_type]]
         self._auc = dataset_type == 'classification' and 'auc' in self.metrics
@@ -201,33 +201,11 @@ class Evaluator:
         self._wass = self._wass if n_wass else None
         self._auc_counts = auc.view(torch.int64) if n_auc else None
         self._seen = np.zeros(N, dtype=bool)  # (host bookkeeping: every row is added once)
-        self._scales = {}
-
-    def _scale(self, scaler):
-        """(means, stds) of ``scaler`` as float64 device tensors, uploaded once per scaler."""
-        hit = self._scales.get(id(scaler))
-        if hit is None:
-            means = np.ascontiguousarray(np.asarray(scaler.means, dtype=np.float64).reshape(-1))
-            stds = np.ascontiguousarray(np.asarray(scaler.stds, dtype=np.float64).reshape(-1))
-            if means.shape != (self.table.num_tasks,) or stds.shape != (self.table.num_tasks,):
-                raise ValueError(f'a scaler of {means.shape[0]} means and {stds.shape[0]} stds for '
-                                 f'{self.table.num_tasks} tasks')
-            hit = (scaler, torch.from_numpy(means).to(self.device), torch.from_numpy(stds).to(self.device))
-            self._scales[id(scaler)] = hit
-        return hit[1], hit[2]
 
     def add(self, pred: torch.Tensor, row0: int, k: int = 0, scaler=None) -> None:
-        if not torch.is_tensor(pred) or pred.dtype != torch.float32 or pred.device != self._small.device or \
-                pred.dim() < 2:
-            raise ValueError('Evaluator.add expects float32 predictions [B][width] on the target table\'s device')
+        pred, B = self._batch(pred, row0)
         if k != 0:
             raise ValueError(f'Evaluator.add scores one model\'s predictions (got model index {k})')
-        pred = pred.detach().reshape(pred.shape[0], -1).contiguous()
-        B = int(pred.shape[0])
-        if pred.shape[1] != self.width:
-            raise ValueError(f'predictions of width {pred.shape[1]} for targets of width {self.width}')
-        if row0 < 0 or row0 + B > self.n_rows:
-            raise ValueError(f'rows {row0} .. {row0 + B} outside the split\'s {self.n_rows} rows')
         if self._seen[row0:row0 + B].any():
             raise ValueError(f'rows {row0} .. {row0 + B} hold predictions already: every row is added once')
         scaler = self.scaler if scaler is None else scaler
@@ -249,7 +227,7 @@ class Evaluator:
             e.kind, e.ld_targets = _native.EVAL_KINDS[self.dataset_type], table.num_tasks
             e.row0, e.N, e.targets = row0, self.n_rows, table.data.data_ptr()
             if scaler is not None:
-                means, stds = self._scale(scaler)
+                means, stds = self._scale(scaler, table.num_tasks)
                 e.scale_mean, e.scale_std = means.data_ptr(), stds.data_ptr()
             e.partials = self._partials.data_ptr()
             e.keep, e.ld_keep, e.keep_f32 = _native.ptr(self._kept), self.width, int(self._keep_f32)
@@ -295,55 +273,15 @@ class Evaluator:
 def evaluate(model, batches, table: TargetTable, metrics: Sequence[str], scaler=None,
              features: Optional[FeatureTable] = None, row_mask: Optional[torch.Tensor] = None,
              encodings: Optional[torch.Tensor] = None, evaluator: Optional[Evaluator] = None) -> Dict[str, list]:
-    """The scores of ``model`` on one split: eval mode, ``no_grad``, the ``BatchMolGraph`` s of ``batches`` (row order
-    = batch order) in groups of eight through ``forward_many``, then ``join_features`` with the split's
-    ``features`` table, the native prediction head and ``Evaluator.add``; no host sync before ``scores()``.  A
-    model whose FFN the native heads refuse runs its own forward (``ensemble._fallback_predict``).
-
-    ``encodings``: the split's cached rows of ``train.frozen_encodings``; the head runs straight from them, in the
-    batch sizes of ``batches`` (which may then be a plain batch size as well).  ``row_mask``: a spectra model's
-    included positions, bool or uint8 ``[N][T]`` on the device.  ``evaluator``: fill this one (made by the caller,
-    say with ``keep=True`` to read ``predictions()`` afterwards) instead of a fresh one."""
+    """The scores of ``model`` on one split: its ``BatchMolGraph`` s ``batches`` (row order = batch order), the split's
+    ``features`` table, a spectra model's ``row_mask`` and the split's cached ``encodings`` (``batches`` may then be
+    a plain batch size) go through ``ensemble.accumulate_model`` into an ``Evaluator``, as
+    ``predict.device_predictions`` describes them; no host sync before ``scores()``.  ``evaluator``: fill this one
+    (made by the caller, say with ``keep=True`` to read ``predictions()`` afterwards) instead of a fresh one."""
     from .ensemble import accumulate_model
-    from .train import _predict_head, head_predict
     ev = Evaluator(table, metrics, table.dataset_type, scaler) if evaluator is None else evaluator
     if ev.table is not table:
         raise ValueError('evaluate: the evaluator given scores another target table')
-    if table.n_rows == 0:
-        return ev.scores()
-    if encodings is None:
-        accumulate_model(ev, 0, model, batches, scaler, features, row_mask)
-        return ev.scores()
-    model.eval()
-    n = table.n_rows
-    if isinstance(batches, int):
-        if batches < 1:
-            raise ValueError('batch size must be at least 1')
-        sizes = [min(batches, n - s) for s in range(0, n, batches)]
-    else:
-        sizes = [len(b.a_scope) for b in batches]
-    starts = np.cumsum([0] + sizes).tolist()
-    if starts[-1] != n or len(encodings) != n or (features is not None and len(features) != n):
-        raise ValueError(f'{starts[-1]} molecules, {len(encodings)} encodings and '
-                         f'{None if features is None else len(features)} feature rows for a split of {n} rows')
-    needs = bool(getattr(model.encoder, 'use_input_features', False))
-    if needs != (features is not None):
-        raise ValueError('the model takes input features and none were given' if needs else
-                         'the model takes no input features, but features were given')
-    head = _predict_head(model)
-    if head is None:
-        raise NotImplementedError('evaluate(encodings=...): the model\'s FFN is not one the native heads run')
-    spectra = bool(getattr(model, 'spectra', False))
-    findex = features.index(range(n)) if features is not None and n else None
-    with torch.no_grad():
-        for r0, r1 in zip(starts[:-1], starts[1:]):
-            x = encodings[r0:r1]
-            if findex is not None:
-                x = join_features(x, findex[r0:r1])
-            if spectra:
-                mask = None if row_mask is None else row_mask[r0:r1]
-                out = head_predict(model, x, head, normalize=True, mask=mask)
-            else:
-                out = head_predict(model, x, head)
-            ev.add(out, r0, 0, scaler)
+    if table.n_rows:
+        accumulate_model(ev, 0, model, batches, scaler, features, row_mask, encodings)
     return ev.scores()

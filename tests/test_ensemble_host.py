@@ -163,6 +163,47 @@ def test_accumulator_misuse_is_refused_on_the_host():
         acc.roundrobin_sid()
 
 
+def test_both_sinks_share_the_batch_check_and_the_scaler_upload():
+    """``EnsembleAccumulator`` and ``Evaluator`` refuse the same bad predictions through ``PredictionSink``'s one
+    check, before anything would launch, and upload a scaler once per object."""
+    from chemprop_amd import Evaluator, TargetTable
+    from chemprop_amd.predict import PredictionSink
+    acc = EnsembleAccumulator(4, 3, 'cpu')
+    ev = Evaluator(TargetTable(np.zeros((4, 3)), 'regression', 'cpu'), ['rmse'])
+    for sink in (acc, ev):
+        assert isinstance(sink, PredictionSink) and type(sink)._batch is PredictionSink._batch
+        assert type(sink)._scale is PredictionSink._scale
+        assert (sink.n_rows, sink.width, sink.device) == (4, 3, torch.device('cpu'))
+        for bad, word in ((torch.zeros(2, 3, dtype=torch.float64), 'float32'),     # dtype
+                          (torch.zeros(3), 'float32'),                             # rank
+                          (np.zeros((2, 3), dtype=np.float32), 'float32'),         # no tensor
+                          (torch.zeros(2, 4), 'width'),                            # width
+                          (torch.zeros(2, 2, 2), 'width')):                        # width, taken flat
+            with pytest.raises(ValueError, match=word):
+                sink.add(bad, 0, 0)
+        for row0 in (-1, 3, 4):                                                    # rows 3 .. 5 of 4
+            with pytest.raises(ValueError, match='rows'):
+                sink.add(torch.zeros(2, 3), row0, 0)
+        view, B = sink._batch(torch.zeros(2, 1, 3), 2)                             # [B][tasks][classes], flat
+        assert B == 2 and tuple(view.shape) == (2, 3) and view.is_contiguous()
+        scaler = cli.StandardScaler(np.array([1.0, -0.5, 0.25]), np.array([2.0, 0.75, 1.0]))
+        means, stds = sink._scale(scaler, 3)
+        again = sink._scale(scaler, 3)
+        assert len(sink._scales) == 1 and again[0] is means and again[1] is stds
+        assert means.dtype == stds.dtype == torch.float64
+        assert means.tolist() == [1.0, -0.5, 0.25] and stds.tolist() == [2.0, 0.75, 1.0]
+        with pytest.raises(ValueError, match='scaler'):
+            sink._scale(cli.StandardScaler(np.zeros(2), np.ones(2)), 3)
+        with pytest.raises(ValueError, match='scaler'):
+            sink._scale(cli.StandardScaler(np.zeros(3), np.ones(4)), 3)
+        assert len(sink._scales) == 1
+    with pytest.raises(ValueError, match='scaler'):                                # (through add: before the launch)
+        acc.add(torch.zeros(2, 3), 0, 0, cli.StandardScaler(np.zeros(2), np.ones(2)))
+    assert not acc._count.any() and not ev._seen.any()                             # nothing was folded
+    with pytest.raises(ValueError, match='model index 1'):
+        ev.add(torch.zeros(2, 3), 0, 1)                                            # the evaluator takes model 0 alone
+
+
 BASE_PREDICT = ['--test_path', 't.csv', '--graphs_path', 'g.npz', '--preds_path', 'p.csv']
 
 

@@ -16,7 +16,7 @@ import torch
 
 import evaluate_cases as ec
 from chemprop_amd import Evaluator, FeatureTable, TargetTable, TrainArgs, _native, cli, evaluate, polymer
-from chemprop_amd.ensemble import make_batches
+from chemprop_amd.ensemble import EnsembleAccumulator, accumulate_model, make_batches
 from chemprop_amd.model import MoleculeModel
 from chemprop_amd.nn_utils import initialize_weights
 from chemprop_amd.train import frozen_encodings
@@ -260,6 +260,74 @@ def test_evaluate_against_the_host_loop(world, kind, variant):
     again = evaluate(model, BATCH if variant == 'encodings' else world['batches'], table, METRICS[kind], scaler,
                      ftable, row_mask, enc)
     assert json.dumps(again) == json.dumps(got)                        # a fresh evaluator, the same numbers
+
+
+def _model(kind, use_f, frozen):
+    """The model of ``test_evaluate_against_the_host_loop``."""
+    torch.manual_seed(5)
+    args = TrainArgs(hidden_size=32, depth=2, dataset_type=kind, num_tasks=T_SPEC if kind == 'spectra' else 2,
+                     multiclass_num_classes=3, use_input_features=use_f, features_size=3 if use_f else 0, device=DEV)
+    model = MoleculeModel(args)
+    initialize_weights(model)
+    if frozen:
+        cli.apply_freezing(model, frzn_encoder=True)
+    return model.to(DEV).eval()
+
+
+def _flat(preds):
+    """The rows of ``cli.predict`` as float32 ``[N][W]`` (a spectrum's None = NaN)."""
+    return np.asarray([[np.nan if v is None else v for v in r] for r in preds], dtype=np.float32).reshape(N_MOLS, -1)
+
+
+@pytest.mark.parametrize('variant,kind,use_f', [('encodings', k, f) for k in METRICS for f in (False, True)] +
+                         [('plain', 'spectra', False), ('plain', 'spectra', True)])
+def test_predict_and_evaluate_share_their_bits(world, variant, kind, use_f):
+    """``cli.predict`` and ``evaluate`` walk a split with the same loop (``predict.device_predictions``): from
+    cached encodings, and for a spectra model under its phase mask, the same launches on the same batch boundaries
+    give the same float32 predictions bit for bit; numpy feature rows give what the split's ``FeatureTable`` gives."""
+    model = _model(kind, use_f, variant == 'encodings')
+    table = TargetTable(world['targets'][kind], kind, DEV, 3)
+    ftable = FeatureTable(world['feats'], DEV) if use_f else None
+    mask = world['included'] if kind == 'spectra' else None
+    row_mask = None if mask is None else torch.from_numpy(mask).to(DEV)
+    enc = frozen_encodings(model, world['graphs'], BATCH) if variant == 'encodings' else None
+    idx = list(range(N_MOLS))
+    preds = _flat(cli.predict(model, world['graphs'], idx, BATCH, None, enc, ftable, mask))
+    ev = Evaluator(table, METRICS[kind], kind, keep=True)
+    evaluate(model, BATCH if enc is not None else world['batches'], table, METRICS[kind], None, ftable, row_mask, enc,
+             evaluator=ev)
+    kept = ev.predictions().cpu().numpy().astype(np.float32)
+    assert preds.shape == kept.shape == (N_MOLS, table.num_tasks * table.num_classes)
+    assert np.array_equal(preds, kept, equal_nan=True)
+    if kind == 'spectra':
+        assert np.array_equal(np.isnan(preds), ~mask)
+    else:
+        assert np.isfinite(preds).all()
+    if use_f:
+        rows = _flat(cli.predict(model, world['graphs'], idx, BATCH, None, enc, world['feats'], mask))
+        assert np.array_equal(rows, preds, equal_nan=True)
+
+
+def test_encodings_through_accumulate_model(world):
+    """``accumulate_model(..., encodings=)`` into an accumulator: each of three models' worth of one frozen
+    classifier is, as float64, exactly the float32 predictions ``evaluate(..., encodings=)`` keeps; ``batches``
+    as a plain batch size or as the ``BatchMolGraph`` s."""
+    model = _model('classification', False, True)
+    enc = frozen_encodings(model, world['graphs'], BATCH)
+    table = TargetTable(world['targets']['classification'], 'classification', DEV)
+    ev = Evaluator(table, METRICS['classification'], keep=True)
+    evaluate(model, BATCH, table, METRICS['classification'], encodings=enc, evaluator=ev)
+    want = ev.predictions().cpu().numpy()
+    assert want.dtype == np.float32 and np.isfinite(want).all()
+    acc = EnsembleAccumulator(N_MOLS, 2, DEV, keep=True, n_models=3)
+    for k in range(3):
+        accumulate_model(acc, k, model, world['batches'] if k == 1 else BATCH, encodings=enc)
+    each = acc.individual().cpu().numpy()
+    assert each.dtype == np.float64 and each.shape == (3, N_MOLS, 2)
+    for k in range(3):
+        assert np.array_equal(each[k], want.astype(np.float64))
+    with pytest.raises(ValueError):
+        accumulate_model(EnsembleAccumulator(N_MOLS, 2, DEV), 0, model, BATCH, encodings=enc[:-1])  # a row missing
 
 
 def test_evaluate_refuses_mismatched_inputs(world):
