@@ -599,7 +599,8 @@ typedef struct WdHead {
     int32_t n_classes;                     /* classes per task: 1 for kinds 0 and 1, >= 2 for kind 2 */
 } WdHead;
 int wdmpnn_head_mse(const WdHead *h, void *stream);
-/* The same FFN at prediction time (model.py:152-194 in eval mode) in two launches: out = W2 act(W1 x +
+/* The same FFN at prediction time (model.py:152-194 in eval mode): the kernels of wdmpnn_head_stack_predict
+ * at L = 2 (a is their z_1), still two launches and the same bits: out = W2 act(W1 x +
  * b1) + b2 followed by out_kind 0: nothing (regression), 1: sigmoid (classification, model.py:186-188),
  * 2: softmax over each group of n_classes consecutive outputs (multiclass, model.py:189-192;
  * max-subtracted).  Same size limits, activations and argument checks as wdmpnn_head_mse (n_classes == 1

@@ -19,6 +19,7 @@ import torch.nn as nn
 from torch.optim import Adam, Optimizer
 from torch.optim.lr_scheduler import _LRScheduler
 
+from . import _native
 from .dp import GradBucket
 from .features import features_width, is_device_features, join_features, split_columns  # noqa: F401 (join_features: public)
 
@@ -117,7 +118,6 @@ class HipAdam(Optimizer):
 
     @torch.no_grad()
     def step(self, closure=None):
-        from . import _native
         loss = None
         if closure is not None:
             with torch.enable_grad():
@@ -218,7 +218,6 @@ def _host_table(rows: np.ndarray, dev: torch.device, zero_copy: bool = False):
     ring[0] = (i + 1) % _PINNED_RING
     ent = ring[1][i]
     if ent is None:
-        from . import _native
         if zero_copy:
             # the kernel reads the rows in place: coherent mapped memory (torch's pinned buffers are
             # non-coherent, and a rewritten slot read again at the same device address would then rely
@@ -410,21 +409,23 @@ def _fusable_head(model: nn.Module, loss_func: Callable, dataset_type: str):
         if loss_func is not sid_loss and loss_func is not wasserstein_loss:
             return None
         st = _head_structure(model)  # (always the spectra entry point: no two-layer tuple path)
-        if not isinstance(st, _StackHead) or st.spectra is None:
+        if st is None or _head_parts(st)[5] is None:
             return None
         return st.with_kind(1 if loss_func is wasserstein_loss else 0, 1)
     else:
         return None
     st = _head_structure(model)
-    if st is None or (isinstance(st, _StackHead) and st.spectra is not None):
+    if st is None:
         return None
-    l2 = st.linears[-1] if isinstance(st, _StackHead) else st[1]
-    if kind == 2 and (l2.out_features % n_classes or l2.out_features != getattr(model, 'output_size', -1)):
+    if type(st) is tuple and kind != 2:  # (the every-step case: nothing of the head to look at)
+        return st + (kind, n_classes)
+    linears, _, _, _, _, spectra = _head_parts(st)
+    if spectra is not None:
         return None
-    if isinstance(st, _StackHead):
-        return st.with_kind(kind, n_classes)
-    l1, l2, code = st
-    return l1, l2, code, kind, n_classes
+    n_out = linears[-1].out_features
+    if kind == 2 and (n_out % n_classes or n_out != getattr(model, 'output_size', -1)):
+        return None
+    return st + (kind, n_classes) if type(st) is tuple else st.with_kind(kind, n_classes)
 
 
 class _StackHead:
@@ -450,6 +451,18 @@ class _StackHead:
         return out + [self.slope]
 
 
+def _head_parts(head):
+    """(linears, act, slope, kind, n_classes, spectra) of a head in either form: the two-layer tuple of
+    ``_head_structure`` (kind None) or of ``_fusable_head`` / ``_predict_head``, or a :class:`_StackHead`.  The
+    one place that tells the two apart to read them."""
+    if isinstance(head, _StackHead):
+        return head.linears, head.act, head.slope, head.kind, head.n_classes, head.spectra
+    if len(head) == 5:
+        l1, l2, act, kind, n_classes = head
+        return (l1, l2), act, None, kind, n_classes, None
+    return head[:2], head[2], None, None, 1, None
+
+
 HEAD_MAX_WIDTH, HEAD_MAX_OUTPUTS = 4096, 64  # (wdmpnn.h: F, Hf <= 4096, T <= 64)
 
 
@@ -472,7 +485,6 @@ def _ffn_structure(ffn: nn.Module, training: bool, spectra: bool = False) -> Opt
     and dtypes are not looked at (``_head_structure`` does).  ``spectra``: the FFN of a spectra model, the same
     stack followed by its output activation (``_Exp`` or ``nn.Softplus``), with up to ``HEAD_MAX_SPECTRUM``
     outputs; without it a trailing activation is not recognised."""
-    from . import _native
     if not isinstance(ffn, nn.Sequential):
         return None
     mods = list(ffn)
@@ -560,47 +572,51 @@ def _two_layer_structure(model: nn.Module):
     return l1, l2, code
 
 
+def _run_head_two(x: torch.Tensor, head, tab_ptr: int, ld_table: int, inv_n: float, grad_of: Callable):
+    """One ``wdmpnn_head_mse`` call on the encodings x [B][F] (contiguous) for the two-layer 5-tuple:
+    (loss, dx, (dW1, db1, dW2, db2)), None for an absent bias.  ``grad_of(parameter)`` gives the buffer each
+    gradient is written into (this entry point computes them all)."""
+    l1, l2, act, kind, n_classes = head
+    W1, b1, W2, b2 = l1.weight, l1.bias, l2.weight, l2.bias
+    dev = x.device
+    B, F = x.shape
+    Hf, T = W1.shape[0], W2.shape[0]
+    scratch = torch.empty(B * (2 * Hf + T + 1), dtype=torch.float32, device=dev)
+    dx = torch.empty_like(x)
+    loss = torch.empty((), dtype=torch.float32, device=dev)
+    dW1, dW2 = grad_of(W1), grad_of(W2)
+    db1 = grad_of(b1) if b1 is not None else None
+    db2 = grad_of(b2) if b2 is not None else None
+    ptr = _native.ptr
+    sp = scratch.data_ptr()
+    h = _native.WdHead(ptr(x), F, B, F, Hf, T, ptr(W1), ptr(b1), ptr(W2), ptr(b2), tab_ptr, ld_table,
+                       float(inv_n), act, sp, sp + 4 * B * Hf, sp + 8 * B * Hf, sp + 4 * B * (2 * Hf + T),
+                       ptr(dx), ptr(dW1), ptr(db1), ptr(dW2), ptr(db2), ptr(loss), kind, n_classes)
+    _native.check(_native.lib().wdmpnn_head_mse(ctypes.byref(h), _native.current_stream(dev)), 'FFN head + loss')
+    return loss, dx, (dW1, db1, dW2, db2)
+
+
 class _HeadMSE(torch.autograd.Function):
-    """loss = sum(w (W2 act(W1 x + b1) + b2 - y)^2) / n, with every gradient computed in the forward."""
+    """loss = sum(w (W2 act(W1 x + b1) + b2 - y)^2) / n, with every gradient computed in the forward.  ``head``
+    is the two-layer 5-tuple; W1, b1, W2, b2 are its parameters: autograd needs them as inputs to hand their
+    gradients out."""
 
     @staticmethod
-    def forward(ctx, x, W1, b1, W2, b2, table, inv_n, act, kind, n_classes):
-        from . import _native
-        x = x.contiguous()
-        dev = x.device
-        B, F = x.shape
-        Hf, T = W1.shape[0], W2.shape[0]
-        scratch = torch.empty(B * (2 * Hf + T + 1), dtype=torch.float32, device=dev)
-        dx = torch.empty_like(x)
-        dW1, dW2 = torch.empty_like(W1), torch.empty_like(W2)
-        db1 = torch.empty_like(b1) if b1 is not None else None
-        db2 = torch.empty_like(b2) if b2 is not None else None
-        loss = torch.empty((), dtype=torch.float32, device=dev)
-        ptr = _native.ptr
-        sp = scratch.data_ptr()
-        h = _native.WdHead(ptr(x), F, B, F, Hf, T, ptr(W1), ptr(b1), ptr(W2), ptr(b2), ptr(table), table.shape[1],
-                           float(inv_n), act, sp, sp + 4 * B * Hf, sp + 8 * B * Hf, sp + 4 * B * (2 * Hf + T),
-                           ptr(dx), ptr(dW1), ptr(db1), ptr(dW2), ptr(db2), ptr(loss), kind, n_classes)
-        _native.check(_native.lib().wdmpnn_head_mse(ctypes.byref(h), _native.current_stream(dev)), 'FFN head + loss')
-        ctx.grads = (dx, dW1, db1, dW2, db2)
+    def forward(ctx, x, head, table, inv_n, W1, b1, W2, b2):
+        loss, dx, grads = _run_head_two(x.contiguous(), head, table.data_ptr(), table.shape[1], inv_n,
+                                        torch.empty_like)
+        ctx.grads = (dx,) + grads
         return loss
 
     @staticmethod
     def backward(ctx, gl):
-        from . import _native
         grads, ctx.grads = ctx.grads, None  # (sole owner: autograd adopts the tensors instead of copying)
-        live = [g for g in grads if g is not None]
-        gl = gl.to(torch.float32).contiguous()
-        ptrs = (ctypes.c_void_p * len(live))(*[g.data_ptr() for g in live])
-        ns = (ctypes.c_int64 * len(live))(*[g.numel() for g in live])
-        _native.check(_native.lib().wdmpnn_scale(ptrs, ns, len(live), gl.data_ptr(),
-                                                 _native.current_stream(gl.device)), 'scale')
-        return grads + (None, None, None, None, None)
+        _scale_all(grads, gl)
+        return (grads[0], None, None, None) + grads[1:]
 
 
 def _scale_all(grads, gl: torch.Tensor) -> None:
     """Every gradient times the loss's incoming gradient: wdmpnn_scale, 8 buffers per launch."""
-    from . import _native
     live = [g for g in grads if g is not None]
     gl = gl.to(torch.float32).contiguous()
     for i in range(0, len(live), 8):
@@ -611,6 +627,20 @@ def _scale_all(grads, gl: torch.Tensor) -> None:
                                                  _native.current_stream(gl.device)), 'scale')
 
 
+def _fill_ffn(h, x: torch.Tensor, linears, slope, act: int):
+    """The FFN on the encodings x [B][F] (contiguous) written into the fields the stack and spectra structs
+    share (``WdHeadStack``, ``WdHeadStackPredict``, ``WdHeadSpectra``, ``WdHeadSpectraPredict``); returns
+    (B, F, Hf, T, L) as written (Hf 0 for one layer)."""
+    B, F = x.shape
+    L, T = len(linears), linears[-1].out_features
+    Hf = linears[0].out_features if L > 1 else 0
+    h.x, h.ld_x, h.B, h.F, h.Hf, h.T, h.L = x.data_ptr(), F, B, F, Hf, T, L
+    for i, l in enumerate(linears):
+        h.W[i], h.b[i] = l.weight.data_ptr(), 0 if l.bias is None else l.bias.data_ptr()
+    h.slope, h.act = 0 if slope is None else slope.data_ptr(), act
+    return B, F, Hf, T, L
+
+
 def _run_head_stack(x: torch.Tensor, head: _StackHead, tab_ptr: int, ld_table: int, inv_n: float, seed: int,
                     grad_of: Callable, want_dx: bool = True):
     """One ``wdmpnn_head_stack`` call on the encodings x [B][F] (contiguous): (loss, dx, the gradients in the
@@ -618,40 +648,22 @@ def _run_head_stack(x: torch.Tensor, head: _StackHead, tab_ptr: int, ld_table: i
     each gradient is written into, or None for a gradient nobody wants (a frozen parameter); ``want_dx``:
     whether d loss / d x is wanted (else dx is None).  With anything left out the call is
     ``wdmpnn_head_stack_partial``: the same outputs, bitwise, and no launch or workgroup for the rest."""
-    from . import _native
     dev = x.device
-    B, F = x.shape
-    lin = head.linears
-    L, T = len(lin), lin[-1].out_features
-    Hf = lin[0].out_features if L > 1 else 0
     spectra = head.spectra is not None  # (wdmpnn_head_spectra: the same fields, NULL gradients = not wanted)
+    h = _native.WdHeadSpectra() if spectra else _native.WdHeadStack()
+    B, F, Hf, T, L = _fill_ffn(h, x, head.linears, head.slope, head.act)
     nbytes = (_native.head_spectra_scratch_bytes if spectra else _native.head_stack_scratch_bytes)(B, F, Hf, T, L)
     scratch = torch.empty(max(nbytes // 4, 4), dtype=torch.float32, device=dev)
     dx = torch.empty_like(x) if want_dx else None
     loss = torch.empty((), dtype=torch.float32, device=dev)
-    h = _native.WdHeadSpectra() if spectra else _native.WdHeadStack()
-    h.x, h.ld_x, h.B, h.F, h.Hf, h.T, h.L = x.data_ptr(), F, B, F, Hf, T, L
-    grads = []
-    partial = not want_dx
     ptr = _native.ptr
-    for i, l in enumerate(lin):
-        gw = grad_of(l.weight)
-        h.W[i], h.dW[i] = l.weight.data_ptr(), ptr(gw)
-        grads.append(gw)
-        partial = partial or gw is None
-        gb = None
-        if l.bias is not None:
-            gb = grad_of(l.bias)
-            h.b[i], h.db[i] = l.bias.data_ptr(), ptr(gb)
-            partial = partial or gb is None
-        grads.append(gb)
-    gs = None
-    if head.slope is not None:
-        gs = grad_of(head.slope)
-        h.slope, h.dslope = head.slope.data_ptr(), ptr(gs)
-        partial = partial or gs is None
-    grads.append(gs)
-    h.table, h.ld_table, h.inv_n, h.act = tab_ptr, ld_table, float(inv_n), head.act
+    params = head.params()  # (W_1, b_1, ..., W_L, b_L, the slope)
+    grads = [grad_of(t) if t is not None else None for t in params]
+    for i in range(L):
+        h.dW[i], h.db[i] = ptr(grads[2 * i]), ptr(grads[2 * i + 1])
+    h.dslope = ptr(grads[2 * L])
+    partial = not want_dx or any(g is None and t is not None for g, t in zip(grads, params))
+    h.table, h.ld_table, h.inv_n = tab_ptr, ld_table, float(inv_n)
     h.p, h.seed, h.loss_kind = head.p, seed, head.kind
     if spectra:
         h.spectra_act = head.spectra
@@ -703,23 +715,27 @@ def head_loss(emb: torch.Tensor, head, target_batch, target_weights=None, data_w
     class indices, one per task, checked on the host).  A :class:`_StackHead` (deeper or one-layer FFN, active
     dropout, PReLU) runs ``wdmpnn_head_stack``; its dropout masks follow the counter hash of
     ``nn_utils.dropout_mask`` under one seed drawn here."""
-    stack = isinstance(head, _StackHead)
-    if stack:
-        l1, l2, kind, n_classes = head.linears[0], head.linears[-1], head.kind, head.n_classes
-    else:
-        l1, l2, act, kind, n_classes = head
-    spectra = stack and head.spectra is not None
+    linears, _, _, kind, n_classes, spectra = _head_parts(head)
+    spectra = spectra is not None
     table, n_t, n_mask = _loss_table(target_batch, target_weights, data_weights, emb.device,
                                      num_classes=n_classes if kind == 2 and not spectra else 0, spectra=spectra)
+    inv_n = _check_head_batch(linears, n_classes, n_t, n_mask, table.shape[0], emb)
+    if isinstance(head, _StackHead):
+        return _HeadStack.apply(emb, head, table, inv_n, _head_seed(head), *head.params())
+    l1, l2 = linears
+    return _HeadMSE.apply(emb, head, table, inv_n, l1.weight, l1.bias, l2.weight, l2.bias)
+
+
+def _check_head_batch(linears, n_classes: int, n_t: int, n_mask, n_rows: int, x: torch.Tensor) -> float:
+    """A loss table (``_loss_table``: n_t targets per row, n_mask present targets, n_rows rows) against the
+    head and its input x (``ValueError``); returns 1 / n_mask, the loss's normalisation (inf without targets)."""
+    l1, l2 = linears[0], linears[-1]
     if n_t * n_classes != l2.out_features:
         raise ValueError(f'{n_t} targets per row for {l2.out_features} outputs')
-    if table.shape[0] != emb.shape[0] or emb.dim() != 2 or emb.shape[1] != l1.in_features:
-        raise ValueError(f'{table.shape[0]} target rows for encodings of shape {tuple(emb.shape)} '
+    if n_rows != x.shape[0] or x.dim() != 2 or x.shape[1] != l1.in_features:
+        raise ValueError(f'{n_rows} target rows for encodings of shape {tuple(x.shape)} '
                          f'(FFN input {l1.in_features})')
-    inv_n = 1.0 / n_mask if n_mask else float('inf')
-    if stack:
-        return _HeadStack.apply(emb, head, table, inv_n, _head_seed(head), *head.params())
-    return _HeadMSE.apply(emb, l1.weight, l1.bias, l2.weight, l2.bias, table, inv_n, act, kind, n_classes)
+    return 1.0 / n_mask if n_mask else float('inf')
 
 
 def _predict_head(model: nn.Module):
@@ -728,36 +744,34 @@ def _predict_head(model: nn.Module):
     st = _head_structure(model)
     if st is None:
         return None
-    stack = isinstance(st, _StackHead)
-    l2 = st.linears[-1] if stack else st[1]
+    n_out = _head_parts(st)[0][-1].out_features
     kind, c = 1 if getattr(model, 'classification', False) else 0, 1
     if getattr(model, 'multiclass', False):
         kind, c = 2, getattr(model, 'num_classes', 0)
-        if not isinstance(c, int) or c < 2 or l2.out_features % c:
+        if not isinstance(c, int) or c < 2 or n_out % c:
             return None
-    return st.with_kind(kind, c) if stack else st + (kind, c)
+    return st + (kind, c) if type(st) is tuple else st.with_kind(kind, c)
 
 
 def _head_linears(head) -> list:
     """The Linear layers of a head of ``_fusable_head`` / ``_predict_head``, first to last."""
-    return head.linears if isinstance(head, _StackHead) else [head[0], head[1]]
+    return list(_head_parts(head)[0])
 
 
 def head_predict(model: nn.Module, emb: torch.Tensor, head=None, normalize: bool = False,
                  mask: Optional[torch.Tensor] = None) -> torch.Tensor:
     """The eval-mode predictions of ``model`` from the encodings ``emb`` (model.py:152-194 after the
     encoder: ``ffn``, then nothing for regression, the sigmoid for classification, the softmax over each
-    task's classes for multiclass) as two HIP launches (``wdmpnn_head_predict``).  ``[B][T]`` for
+    task's classes for multiclass) as L HIP launches (``wdmpnn_head_stack_predict``; two for the two-layer
+    head, whose tuple fills the same struct with L = 2).  ``[B][T]`` for
     regression and classification, ``[B][tasks][classes]`` for multiclass.  No autograd graph is built.
-    The model must be in eval mode with an FFN the native heads run: the two-layer head, or any other FFN of
-    ``create_ffn`` with at most 64 outputs as L launches (``wdmpnn_head_stack_predict``);
-    ``NotImplementedError`` otherwise: there is no torch fallback here.
+    The model must be in eval mode with an FFN the native heads run: any FFN of ``create_ffn`` with at most 64
+    outputs; ``NotImplementedError`` otherwise: there is no torch fallback here.
     A spectra model (``wdmpnn_head_spectra_predict``, up to 8192 outputs) returns ``act_s(ffn)`` as its
     ``forward`` does, or with ``normalize`` every row divided by the sum of its included positions
     (``spectra_utils.normalize_spectra`` on the device): ``mask`` is a bool or uint8 ``[B][T]`` tensor on the
     device (nonzero = included; None = every position), and the excluded positions come back as NaN.
     ``normalize`` and ``mask`` are for spectra models only (``ValueError`` otherwise)."""
-    from . import _native
     if model.training:
         raise ValueError('head_predict is the eval-mode head: call model.eval() first')
     if head is None:
@@ -765,64 +779,36 @@ def head_predict(model: nn.Module, emb: torch.Tensor, head=None, normalize: bool
     if head is None:
         raise NotImplementedError('head_predict: the model\'s FFN is not one the native head runs (Dropout / Linear / '
                                   'activation stacks of create_ffn, <= 64 outputs, a single PReLU slope)')
-    l1 = _head_linears(head)[0]
+    linears, act, slope, kind, n_classes, spectra = _head_parts(head)
+    l1 = linears[0]
     if emb.dim() != 2 or emb.shape[1] != l1.in_features or emb.device != l1.weight.device or \
             emb.dtype != torch.float32:
         raise ValueError(f'encodings of shape {tuple(emb.shape)} ({emb.dtype}, {emb.device}) for an FFN input of '
                          f'{l1.in_features} on {l1.weight.device}')
     x = emb.detach().contiguous()
-    B, F = x.shape
-    spectra = isinstance(head, _StackHead) and head.spectra is not None
-    if (normalize or mask is not None) and not spectra:
+    dev = x.device
+    if (normalize or mask is not None) and spectra is None:
         raise ValueError('head_predict: normalize / mask are for spectra models')
-    if spectra:
-        lin = head.linears
-        L, T = len(lin), lin[-1].out_features
-        Hf = lin[0].out_features if L > 1 else 0
-        if mask is not None:
-            if not normalize or tuple(mask.shape) != (B, T) or mask.device != x.device or \
-                    mask.dtype not in (torch.bool, torch.uint8):
-                raise ValueError(f'head_predict: mask of shape {tuple(mask.shape)} ({mask.dtype}, {mask.device}) for '
-                                 f'normalize={normalize} and outputs of shape {(B, T)} on {x.device}')
-            mask = mask.contiguous().view(torch.uint8)
-        scratch = torch.empty(max((L - 1) * B * Hf + B * T, 4), dtype=torch.float32, device=x.device)
-        out = torch.empty((B, T), dtype=torch.float32, device=x.device)
-        h = _native.WdHeadSpectraPredict()
-        h.x, h.ld_x, h.B, h.F, h.Hf, h.T, h.L = x.data_ptr(), F, B, F, Hf, T, L
-        for i, l in enumerate(lin):
-            h.W[i], h.b[i] = l.weight.data_ptr(), _native.ptr(l.bias)
-        h.slope, h.act = _native.ptr(head.slope), head.act
-        h.scratch, h.scratch_bytes = scratch.data_ptr(), scratch.numel() * 4
-        h.out, h.spectra_act, h.normalize, h.mask = out.data_ptr(), head.spectra, int(bool(normalize)), _native.ptr(mask)
-        _native.check(_native.lib().wdmpnn_head_spectra_predict(ctypes.byref(h), _native.current_stream(x.device)),
-                      'FFN head spectra (predict)')
-        return out
-    if isinstance(head, _StackHead):
-        lin = head.linears
-        L, T = len(lin), lin[-1].out_features
-        Hf = lin[0].out_features if L > 1 else 0
-        scratch = torch.empty(max((L - 1) * B * Hf, 4), dtype=torch.float32, device=x.device)
-        out = torch.empty((B, T), dtype=torch.float32, device=x.device)
-        h = _native.WdHeadStackPredict()
-        h.x, h.ld_x, h.B, h.F, h.Hf, h.T, h.L = x.data_ptr(), F, B, F, Hf, T, L
-        for i, l in enumerate(lin):
-            h.W[i], h.b[i] = l.weight.data_ptr(), _native.ptr(l.bias)
-        h.slope, h.act = _native.ptr(head.slope), head.act
-        h.scratch, h.scratch_bytes = scratch.data_ptr(), scratch.numel() * 4
-        h.out, h.out_kind, h.n_classes = out.data_ptr(), head.kind, head.n_classes
-        _native.check(_native.lib().wdmpnn_head_stack_predict(ctypes.byref(h), _native.current_stream(x.device)),
-                      'FFN head stack (predict)')
-        return out.view(B, T // head.n_classes, head.n_classes) if head.kind == 2 else out
-    l1, l2, act, kind, n_classes = head
-    Hf, T = l1.out_features, l2.out_features
-    a = torch.empty((B, Hf), dtype=torch.float32, device=x.device)
-    out = torch.empty((B, T), dtype=torch.float32, device=x.device)
-    ptr = _native.ptr
-    h = _native.WdHeadPredict(ptr(x), F, B, F, Hf, T, ptr(l1.weight), ptr(l1.bias), ptr(l2.weight), ptr(l2.bias),
-                              act, ptr(a), ptr(out), kind, n_classes)
-    _native.check(_native.lib().wdmpnn_head_predict(ctypes.byref(h), _native.current_stream(x.device)),
-                  'FFN head (predict)')
-    return out.view(B, T // n_classes, n_classes) if kind == 2 else out
+    h = _native.WdHeadStackPredict() if spectra is None else _native.WdHeadSpectraPredict()
+    B, F, Hf, T, L = _fill_ffn(h, x, linears, slope, act)
+    if mask is not None:
+        if not normalize or tuple(mask.shape) != (B, T) or mask.device != dev or \
+                mask.dtype not in (torch.bool, torch.uint8):
+            raise ValueError(f'head_predict: mask of shape {tuple(mask.shape)} ({mask.dtype}, {mask.device}) for '
+                             f'normalize={normalize} and outputs of shape {(B, T)} on {dev}')
+        mask = mask.contiguous().view(torch.uint8)
+    # the z_l; a spectrum's z_L - b_L behind them
+    scratch = torch.empty(max((L - 1) * B * Hf + (0 if spectra is None else B * T), 4), dtype=torch.float32, device=dev)
+    out = torch.empty((B, T), dtype=torch.float32, device=dev)
+    h.scratch, h.scratch_bytes, h.out = scratch.data_ptr(), scratch.numel() * 4, out.data_ptr()
+    if spectra is None:
+        h.out_kind, h.n_classes = kind, n_classes
+        entry, what = _native.lib().wdmpnn_head_stack_predict, 'FFN head stack (predict)'
+    else:
+        h.spectra_act, h.normalize, h.mask = spectra, int(bool(normalize)), _native.ptr(mask)
+        entry, what = _native.lib().wdmpnn_head_spectra_predict, 'FFN head spectra (predict)'
+    _native.check(entry(ctypes.byref(h), _native.current_stream(dev)), what)
+    return out.view(B, T // n_classes, n_classes) if kind == 2 and spectra is None else out
 
 
 def _grad_buffer(p: torch.Tensor) -> torch.Tensor:
@@ -866,11 +852,8 @@ def _direct_encoder(model: nn.Module, mol_batch, features_batch, head):
         return None
     # the direct step skips zero_grad and overwrites only the gradients it computes: any other trainable
     # parameter (a future addition to the model) would keep a stale gradient, so it must not exist
-    if isinstance(head, _StackHead):
-        head_params = head.params()
-    else:
-        l1, l2 = head[:2]
-        head_params = (l1.weight, l1.bias, l2.weight, l2.bias)
+    linears, _, slope, _, _, _ = _head_parts(head)
+    head_params = [t for l in linears for t in (l.weight, l.bias)] + [slope]
     written = {id(t) for _, t in enc._direct_names()} | {id(t) for t in head_params if t is not None}
     # (a shared activation module sits at several places of the FFN's Sequential: its slope is met once per site)
     if set(ids) != written:
@@ -938,13 +921,13 @@ def _frozen_plan(model: nn.Module, mol_batch, features_batch, head, cached: bool
     enc = mpn.encoder[0]
     if type(enc) is not MPNEncoder or enc.depth < 2 or enc.atom_messages or hasattr(enc, 'atom_descriptors_layer'):
         return None
-    if isinstance(head, _StackHead):
-        st = head
-    else:
+    st = head
+    if not isinstance(head, _StackHead):
         st = _ffn_structure(model.ffn, model.training)
         if st is None:
             return None
-        st = st.with_kind(head[3], head[4])
+        _, _, _, kind, n_classes, _ = _head_parts(head)
+        st = st.with_kind(kind, n_classes)
     head_params = [t for t in st.params() if t is not None]  # (devices and dtypes: checked by _fusable_head)
     enc_params = [t for _, t in enc._direct_names()]
     known = {id(t) for t in enc_params} | {id(t) for t in head_params}
@@ -1005,13 +988,8 @@ def _direct_step(model, enc, graph, head, target_batch, target_weights, data_wei
     forward, the head runs on x (F = ld_x = H + Ff), and one more launch makes the encoder's slice of dx,
     dx[:, 0:H], contiguous for the encoder backward (a frozen encoder has no dx and no such launch): what
     ``torch.cat`` and its backward do on the autograd path, bitwise."""
-    from . import _native
-    stack = isinstance(head, _StackHead)
-    if stack:
-        l1, l2, kind, n_classes = head.linears[0], head.linears[-1], head.kind, head.n_classes
-    else:
-        l1, l2, act, kind, n_classes = head
-    spectra = stack and head.spectra is not None
+    linears, _, _, kind, n_classes, spectra = _head_parts(head)
+    spectra = spectra is not None
     nc = n_classes if kind == 2 and not spectra else 0  # (multiclass: _loss_table checks the class indices on the host)
     enc_frozen = plan is not None and plan.enc_frozen
     if encodings is not None:
@@ -1036,32 +1014,13 @@ def _direct_step(model, enc, graph, head, target_batch, target_weights, data_wei
         tab_ptr, tshape = table.data_ptr(), tuple(table.shape)
     else:
         tab_ptr = zc[0]
-    if n_t * n_classes != l2.out_features:
-        raise ValueError(f'{n_t} targets per row for {l2.out_features} outputs')
-    if tshape[0] != out.shape[0] or out.shape[1] != l1.in_features:
-        raise ValueError(f'{tshape[0]} target rows for encodings of shape {tuple(out.shape)} '
-                         f'(FFN input {l1.in_features})')
-    inv_n = 1.0 / n_mask if n_mask else float('inf')
+    inv_n = _check_head_batch(linears, n_classes, n_t, n_mask, tshape[0], out)
     dev = out.device
-    if stack:
+    if isinstance(head, _StackHead):
         loss, dx, _ = _run_head_stack(out, head, tab_ptr, tshape[1], inv_n, _head_seed(head),
                                       _grad_buffer if plan is None else plan.grad_of, not enc_frozen)
     else:
-        B, F = out.shape
-        Hf, T = l1.weight.shape[0], l2.weight.shape[0]
-        scratch = torch.empty(B * (2 * Hf + T + 1), dtype=torch.float32, device=dev)
-        dx = torch.empty_like(out)
-        loss = torch.empty((), dtype=torch.float32, device=dev)
-        dW1, dW2 = _grad_buffer(l1.weight), _grad_buffer(l2.weight)
-        db1 = _grad_buffer(l1.bias) if l1.bias is not None else None
-        db2 = _grad_buffer(l2.bias) if l2.bias is not None else None
-        ptr = _native.ptr
-        sp = scratch.data_ptr()
-        h = _native.WdHead(ptr(out), F, B, F, Hf, T, ptr(l1.weight), ptr(l1.bias), ptr(l2.weight), ptr(l2.bias),
-                           tab_ptr, tshape[1], float(inv_n), act, sp, sp + 4 * B * Hf, sp + 8 * B * Hf,
-                           sp + 4 * B * (2 * Hf + T), ptr(dx), ptr(dW1), ptr(db1), ptr(dW2), ptr(db2), ptr(loss), kind,
-                           n_classes)
-        _native.check(_native.lib().wdmpnn_head_mse(ctypes.byref(h), _native.current_stream(dev)), 'FFN head + loss')
+        loss, dx, _ = _run_head_two(out, head, tab_ptr, tshape[1], inv_n, _grad_buffer)
     if zc is not None:
         zc[1].record(torch.cuda.current_stream(dev))  # (the pinned buffer's last reader)
     if bucket is not None:  # the head's gradients are enqueued: their all-reduce overlaps the encoder backward

@@ -825,7 +825,8 @@ __global__ __launch_bounds__(256) void adam_kernel(AdamLaunch A) {
 // summation orders).  fp32 FMA throughout (the GEMMs are 128 x 300 x 300: latency, not FLOPs).
 // loss_kind 1 swaps in BCE on the logits, loss_kind 2 (head_rows_ce_kernel) one softmax cross-entropy per
 // task over its n_classes outputs; only the row kernel's loss terms and dout differ.  The prediction head
-// (wdmpnn_head_predict) is the same H GEMM followed by head_predict_rows_kernel.
+// (wdmpnn_head_predict) has no kernels of its own: it is the head stack's prediction at L = 2
+// (head_stack_fwd_kernel at l = 1 is head_h_kernel's tile routine, then head_stack_predict_rows_kernel).
 // Every other FFN of model.py:57-121 (1 .. 6 Linear layers, active dropout, PReLU) is the head stack at the
 // end of this file (wdmpnn_head_stack): the same tile code with the activation and the dropout mask applied
 // as operands are staged, 2 L - 1 launches.
@@ -1087,38 +1088,6 @@ __global__ __launch_bounds__(256) void head_rows_ce_kernel(WdHead P) {
             h[j] = act_fwd(ACT, z, 0.f);
         }
     });
-}
-
-// prediction head step 2 (wdmpnn_head_predict), one wave per row: out = W2 act(h) + b2 into the wave's LDS
-// row, then lane t finishes output t: identity, sigmoid, or the max-subtracted softmax over its group of
-// C outputs (model.py:186-192)
-__global__ __launch_bounds__(256) void head_predict_rows_kernel(WdHeadPredict P) {
-    __shared__ float osh[4][HEAD_MAX_T];
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6, row = blockIdx.x * 4 + wave;
-    if (row >= P.B) return;
-    const int Hf = P.Hf, T = P.T;
-    const float *h = P.a + (size_t)row * Hf;
-    float *os = osh[wave];
-    with_act(P.act, [&](auto act_c) {
-        constexpr int ACT = decltype(act_c)::value;
-        for (int t = 0; t < T; ++t) {
-            const float *w2 = P.W2 + (size_t)t * Hf;
-            float s = 0.f;
-            for (int j = lane; j < Hf; j += 64) s = fmaf(w2[j], act_fwd(ACT, h[j], 0.f), s);
-            os[t] = wave_sum(s) + (P.b2 ? P.b2[t] : 0.f);
-        }
-    });
-    if (lane >= T) return;
-    float v = os[lane];
-    if (P.out_kind == 1) {
-        v = 1.f / (1.f + expf(-v));
-    } else if (P.out_kind == 2) {
-        const int C = P.n_classes;
-        float m, e;
-        group_max_sum(os + (lane / C) * C, C, m, e);
-        v = expf(v - m) / e;
-    }
-    P.out[(size_t)row * T + lane] = v;
 }
 
 // head step 3: dX = dH W1 (tiles 0 .. n1), dW1 = dH^T X (next n2 tiles), then db1, dW2, db2 and the loss
@@ -1457,8 +1426,9 @@ __global__ __launch_bounds__(256) void head_stack_last_kernel(WdHeadStack P) {
     else if (q == n && P.dslope) P.dslope[0] = 0.f;
 }
 
-// prediction, one wave per row: out = act(z_{L-1}) W_L^T + b_L (L == 1: x W_1^T + b_1), then the output
-// kinds of head_predict_rows_kernel
+// prediction (wdmpnn_head_stack_predict, wdmpnn_head_predict), one wave per row: out = act(z_{L-1}) W_L^T + b_L
+// (L == 1: x W_1^T + b_1) into the wave's LDS row, then lane t finishes output t: identity, sigmoid, or the
+// max-subtracted softmax over its group of C outputs (model.py:186-192)
 __global__ __launch_bounds__(256) void head_stack_predict_rows_kernel(WdHeadStackPredict P) {
     __shared__ float osh[4][HEAD_MAX_T];
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6, row = blockIdx.x * 4 + wave;

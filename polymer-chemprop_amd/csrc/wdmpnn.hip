@@ -642,13 +642,7 @@ int slab_reduce_multi(const SlabReduce *jobs, int n, hipStream_t st) {
 int slab_reduce(const TnPlan &tp, const float *slab, int n_rows, std::initializer_list<std::array<int, 3>> map,
                 float *dW, int ldw, float *db, int bias_col, hipStream_t st) {
     if (!dW && !db) return 0;
-    SlabReduce R{};
-    R.slab = slab; R.nsplit = tp.nsplit; R.slab_stride = tp.slab_stride; R.ld_slab = tp.ld_slab; R.rows = n_rows;
-    for (const auto &m : map) {
-        R.c0[R.nseg] = m[0]; R.w0[R.nseg] = m[1]; R.K[R.nseg] = m[2];
-        ++R.nseg;
-    }
-    R.dW = dW; R.ldw = ldw; R.db = db; R.bias_col = bias_col;
+    const SlabReduce R = slab_job(tp, slab, n_rows, map, dW, ldw, db, bias_col);
     int cols = 0;
     if (dW)
         for (int q = 0; q < R.nseg; ++q) cols += R.K[q];
@@ -2372,6 +2366,79 @@ static int head_check(int B, int F, int Hf, int T, int ld_x, int act, int kind, 
     return 0;
 }
 
+// The host plan of the stack kernels, shared by every entry point that runs an FFN of L layers through them
+// (the stack head, its prediction, the two-layer prediction, the spectra head and its prediction).
+}  // extern "C"
+namespace {
+// the stack kernels' view of a checked head struct: the FFN and the scratch (z_l at its start), everything else
+// zero (no dropout, no gradients); Hf is unused when L == 1
+template <class H>
+WdHeadStack stack_view(const H *h) {
+    WdHeadStack P{};
+    P.x = h->x; P.ld_x = h->ld_x; P.B = h->B; P.F = h->F; P.Hf = h->L == 1 ? 1 : h->Hf; P.T = h->T; P.L = h->L;
+    for (int l = 0; l < h->L; ++l) { P.W[l] = h->W[l]; P.b[l] = h->b[l]; }
+    P.slope = h->slope; P.act = h->act; P.scratch = h->scratch;
+    return P;
+}
+// z_l for the hidden layers l = 1 .. L-1
+int stack_forward(const WdHeadStack &P, hipStream_t st) {
+    for (int l = 1; l < P.L; ++l) {
+        hipLaunchKernelGGL(head_stack_fwd_kernel, dim3(head_tiles(P.B, P.Hf, HEAD_H_TS)), dim3(256), 0, st, P, l);
+        WD_CHECK_LAUNCH("head_stack_fwd");
+    }
+    return 0;
+}
+// wdmpnn_head_stack_predict and wdmpnn_head_predict after their checks (B > 0)
+int stack_predict_run(const WdHeadStackPredict *h, hipStream_t st) {
+    WD_TRY(stack_forward(stack_view(h), st));
+    hipLaunchKernelGGL(head_stack_predict_rows_kernel, dim3((h->B + 3) / 4), dim3(256), 0, st, *h);
+    WD_CHECK_LAUNCH("head_stack_predict_rows");
+    return 0;
+}
+// the lowest level m whose dz something needs (dz_0 = dx): 0 for dx, 1 for PReLU's dslope (every site has a
+// term), else the first layer with a wanted dW or db; L when only the loss is left
+int stack_lowest_level(const WdHeadStack &P) {
+    int m = P.L;
+    for (int l = P.L; l >= 1; --l)
+        if (P.dW[l - 1] || P.db[l - 1]) m = l;
+    if (P.dslope && P.act == WD_ACT_PRELU && P.L > 1) m = 1;
+    if (P.dx) m = 0;
+    return m;
+}
+// head_stack_bwd_kernel for l = L-1 .. 1, a launch per layer something is wanted of.  slope: StackWant.slope of
+// the launch that sums dslope (1, or 2 behind head_spectra_bwd_kernel).  last: the last layer's sums ride in the
+// first launch there is; *carried: whether one took them.
+int stack_backward(const WdHeadStack &P, int m, hipStream_t st, int slope, bool last, bool *carried) {
+    *carried = false;
+    for (int l = P.L - 1; l >= 1; --l) {
+        StackWant Q{};
+        Q.dz = m <= l - 1;
+        Q.dw = P.dW[l - 1] != nullptr;
+        Q.db = P.db[l - 1] != nullptr;
+        Q.slope = l == 1 && P.dslope ? slope : 0;
+        if (!(Q.dz || Q.dw || Q.db || Q.slope)) continue;
+        Q.last = last && !*carried;
+        *carried = last;
+        hipLaunchKernelGGL(head_stack_bwd_kernel, dim3((unsigned)stack_bwd_blocks(P, l, Q)), dim3(256), 0, st, P, l, Q);
+        WD_CHECK_LAUNCH("head_stack_bwd");
+    }
+    return 0;
+}
+// who: the message prefix ("head stack" / "head spectra")
+int scratch_enough(const char *who, size_t given, size_t need) {
+    if (given < need) return fail(WD_ERR_WORKSPACE, "%s: scratch of %zu bytes, %zu needed", who, given, need);
+    return 0;
+}
+// the argument check of the two *_scratch_bytes entry points
+int scratch_sizes_check(const char *who, int B, int F, int Hf, int T, int L, const size_t *bytes) {
+    if (!bytes) return fail(WD_ERR_ARG, "null bytes");
+    if (B < 0 || F <= 0 || T <= 0 || L < 1 || L > WD_HEAD_MAX_LAYERS || (L > 1 && Hf <= 0))
+        return fail(WD_ERR_SHAPE, "%s: bad sizes", who);
+    return 0;
+}
+}  // namespace
+extern "C" {
+
 int wdmpnn_head_mse(const WdHead *h, void *stream) {
     WD_KERNELS_OK();
     if (!h) return fail(WD_ERR_ARG, "null head");
@@ -2401,15 +2468,12 @@ int wdmpnn_head_predict(const WdHeadPredict *h, void *stream) {
     WD_TRY(head_check(h->B, h->F, h->Hf, h->T, h->ld_x, h->act, h->out_kind, h->n_classes));
     if (!h->W1 || !h->W2 || (h->B && (!h->x || !h->a || !h->out))) return fail(WD_ERR_ARG, "head: null pointer");
     if (h->B == 0) return 0;
-    hipStream_t st = (hipStream_t)stream;
-    WdHead v{};  // head_h_kernel's view: H = X W1^T + b1 -> a
-    v.x = h->x; v.ld_x = h->ld_x; v.B = h->B; v.F = h->F; v.Hf = h->Hf; v.T = h->T;
-    v.W1 = h->W1; v.b1 = h->b1; v.a = h->a;
-    hipLaunchKernelGGL(head_h_kernel, dim3(head_tiles(h->B, h->Hf, HEAD_H_TS)), dim3(256), 0, st, v);
-    WD_CHECK_LAUNCH("head_h");
-    hipLaunchKernelGGL(head_predict_rows_kernel, dim3((h->B + 3) / 4), dim3(256), 0, st, *h);
-    WD_CHECK_LAUNCH("head_predict_rows");
-    return 0;
+    WdHeadStackPredict q{};  // the stack's prediction at L = 2: its z_1 is a
+    q.x = h->x; q.ld_x = h->ld_x; q.B = h->B; q.F = h->F; q.Hf = h->Hf; q.T = h->T; q.L = 2;
+    q.W[0] = h->W1; q.b[0] = h->b1; q.W[1] = h->W2; q.b[1] = h->b2;
+    q.act = h->act; q.scratch = h->a; q.scratch_bytes = sizeof(float) * (size_t)h->B * h->Hf;
+    q.out = h->out; q.out_kind = h->out_kind; q.n_classes = h->n_classes;
+    return stack_predict_run(&q, (hipStream_t)stream);
 }
 
 int wdmpnn_scale(float *const *p, const int64_t *n, int32_t k, const float *s, void *stream) {
@@ -2449,9 +2513,7 @@ static int head_stack_check(int B, int F, int Hf, int T, int L, int ld_x, int ac
 }
 
 int wdmpnn_head_stack_scratch_bytes(int32_t B, int32_t F, int32_t Hf, int32_t T, int32_t L, size_t *bytes) {
-    if (!bytes) return fail(WD_ERR_ARG, "null bytes");
-    if (B < 0 || F <= 0 || T <= 0 || L < 1 || L > WD_HEAD_MAX_LAYERS || (L > 1 && Hf <= 0))
-        return fail(WD_ERR_SHAPE, "head stack: bad sizes");
+    WD_TRY(scratch_sizes_check("head stack", B, F, Hf, T, L, bytes));
     *bytes = sizeof(float) * head_stack_floats(B, F, L == 1 ? 1 : Hf, T, L);
     return 0;
 }
@@ -2465,38 +2527,15 @@ static int head_stack_run(const WdHeadStack *h, void *stream) {
         return fail(WD_ERR_ARG, "head stack: null pointer");
     WdHeadStack P = *h;
     if (P.L == 1) P.Hf = 1;
-    if (h->scratch_bytes < sizeof(float) * head_stack_floats(P.B, P.F, P.Hf, P.T, P.L))
-        return fail(WD_ERR_WORKSPACE, "head stack: scratch of %zu bytes, %zu needed", h->scratch_bytes,
-                    sizeof(float) * head_stack_floats(P.B, P.F, P.Hf, P.T, P.L));
+    WD_TRY(scratch_enough("head stack", h->scratch_bytes, sizeof(float) * head_stack_floats(P.B, P.F, P.Hf, P.T, P.L)));
     if (P.B == 0) return 0;
     hipStream_t st = (hipStream_t)stream;
-    const int B = P.B, Hf = P.Hf, L = P.L;
-    // the lowest level m whose dz something needs (dz_0 = dx): 0 for dx, 1 for PReLU's dslope (every site has a
-    // term), else the first layer with a wanted dW or db; L when only the loss is left
-    int m = L;
-    for (int l = L; l >= 1; --l)
-        if (P.dW[l - 1] || P.db[l - 1]) m = l;
-    if (P.dslope && P.act == WD_ACT_PRELU && L > 1) m = 1;
-    if (P.dx) m = 0;
-    for (int l = 1; l < L; ++l) {
-        hipLaunchKernelGGL(head_stack_fwd_kernel, dim3(head_tiles(B, Hf, HEAD_H_TS)), dim3(256), 0, st, P, l);
-        WD_CHECK_LAUNCH("head_stack_fwd");
-    }
-    hipLaunchKernelGGL(head_stack_rows_kernel, dim3((B + 3) / 4), dim3(256), 0, st, P, m <= L - 1 ? 1 : 0);
+    const int m = stack_lowest_level(P);
+    WD_TRY(stack_forward(P, st));
+    hipLaunchKernelGGL(head_stack_rows_kernel, dim3((P.B + 3) / 4), dim3(256), 0, st, P, m <= P.L - 1 ? 1 : 0);
     WD_CHECK_LAUNCH("head_stack_rows");
-    bool last_done = false;  // (the last layer's sums ride in the first backward launch there is)
-    for (int l = L - 1; l >= 1; --l) {
-        StackWant Q{};
-        Q.dz = m <= l - 1;
-        Q.dw = P.dW[l - 1] != nullptr;
-        Q.db = P.db[l - 1] != nullptr;
-        Q.slope = l == 1 && P.dslope;
-        if (!(Q.dz || Q.dw || Q.db || Q.slope)) continue;
-        Q.last = !last_done;
-        last_done = true;
-        hipLaunchKernelGGL(head_stack_bwd_kernel, dim3((unsigned)stack_bwd_blocks(P, l, Q)), dim3(256), 0, st, P, l, Q);
-        WD_CHECK_LAUNCH("head_stack_bwd");
-    }
+    bool last_done;
+    WD_TRY(stack_backward(P, m, st, 1, true, &last_done));
     if (!last_done) {
         const long long n = stack_last_count(P) + 1;
         hipLaunchKernelGGL(head_stack_last_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, P);
@@ -2528,21 +2567,8 @@ int wdmpnn_head_stack_predict(const WdHeadStackPredict *h, void *stream) {
     WD_TRY(head_stack_check(h->B, h->F, h->Hf, h->T, h->L, h->ld_x, h->act, h->out_kind, h->n_classes, h->W, h->slope));
     if (h->B == 0) return 0;
     if (!h->x || !h->out || (h->L > 1 && !h->scratch)) return fail(WD_ERR_ARG, "head stack: null pointer");
-    if (h->L > 1 && h->scratch_bytes < sizeof(float) * (size_t)(h->L - 1) * h->B * h->Hf)
-        return fail(WD_ERR_WORKSPACE, "head stack: scratch of %zu bytes, %zu needed", h->scratch_bytes,
-                    sizeof(float) * (size_t)(h->L - 1) * h->B * h->Hf);
-    hipStream_t st = (hipStream_t)stream;
-    WdHeadStack v{};  // head_stack_fwd_kernel's view (no dropout; z_l at the start of the scratch)
-    v.x = h->x; v.ld_x = h->ld_x; v.B = h->B; v.F = h->F; v.Hf = h->Hf; v.T = h->T; v.L = h->L;
-    for (int l = 0; l < h->L; ++l) { v.W[l] = h->W[l]; v.b[l] = h->b[l]; }
-    v.slope = h->slope; v.act = h->act; v.scratch = h->scratch;
-    for (int l = 1; l < h->L; ++l) {
-        hipLaunchKernelGGL(head_stack_fwd_kernel, dim3(head_tiles(h->B, h->Hf, HEAD_H_TS)), dim3(256), 0, st, v, l);
-        WD_CHECK_LAUNCH("head_stack_fwd");
-    }
-    hipLaunchKernelGGL(head_stack_predict_rows_kernel, dim3((h->B + 3) / 4), dim3(256), 0, st, *h);
-    WD_CHECK_LAUNCH("head_stack_predict_rows");
-    return 0;
+    WD_TRY(scratch_enough("head stack", h->scratch_bytes, sizeof(float) * (size_t)(h->L - 1) * h->B * h->Hf));
+    return stack_predict_run(h, (hipStream_t)stream);
 }
 
 // the checks wdmpnn_head_spectra and wdmpnn_head_spectra_predict share: head_stack_check's (with one output in
@@ -2557,9 +2583,7 @@ static int head_spectra_check(int B, int F, int Hf, int T, int L, int ld_x, int 
 }
 
 int wdmpnn_head_spectra_scratch_bytes(int32_t B, int32_t F, int32_t Hf, int32_t T, int32_t L, size_t *bytes) {
-    if (!bytes) return fail(WD_ERR_ARG, "null bytes");
-    if (B < 0 || F <= 0 || T <= 0 || L < 1 || L > WD_HEAD_MAX_LAYERS || (L > 1 && Hf <= 0))
-        return fail(WD_ERR_SHAPE, "head spectra: bad sizes");
+    WD_TRY(scratch_sizes_check("head spectra", B, F, Hf, T, L, bytes));
     *bytes = sizeof(float) * head_spectra_floats(B, F, L == 1 ? 1 : Hf, T, L);
     return 0;
 }
@@ -2573,30 +2597,19 @@ int wdmpnn_head_spectra(const WdHeadSpectra *h, void *stream) {
     if (h->ld_table < 2 * h->T) return fail(WD_ERR_SHAPE, "head spectra: bad sizes (ld_table)");
     if (!h->loss || !h->scratch || (h->B && (!h->x || !h->table)))
         return fail(WD_ERR_ARG, "head spectra: null pointer");
-    WdHeadStack P{};  // the stack kernels' view: the same FFN, scratch prefix and gradient outputs
-    P.x = h->x; P.ld_x = h->ld_x; P.B = h->B; P.F = h->F; P.Hf = h->L == 1 ? 1 : h->Hf; P.T = h->T; P.L = h->L;
-    for (int l = 0; l < h->L; ++l) { P.W[l] = h->W[l]; P.b[l] = h->b[l]; P.dW[l] = h->dW[l]; P.db[l] = h->db[l]; }
-    P.slope = h->slope; P.table = h->table; P.ld_table = h->ld_table; P.inv_n = h->inv_n; P.act = h->act;
-    P.p = h->p; P.seed = h->seed; P.n_classes = 1; P.scratch = h->scratch; P.scratch_bytes = h->scratch_bytes;
+    WdHeadStack P = stack_view(h);  // then the training fields: the same scratch prefix and gradient outputs
+    for (int l = 0; l < h->L; ++l) { P.dW[l] = h->dW[l]; P.db[l] = h->db[l]; }
+    P.table = h->table; P.ld_table = h->ld_table; P.inv_n = h->inv_n;
+    P.p = h->p; P.seed = h->seed; P.n_classes = 1; P.scratch_bytes = h->scratch_bytes;
     P.dx = h->dx; P.dslope = h->dslope; P.loss = h->loss;
-    const size_t need = sizeof(float) * head_spectra_floats(P.B, P.F, P.Hf, P.T, P.L);
-    if (h->scratch_bytes < need)
-        return fail(WD_ERR_WORKSPACE, "head spectra: scratch of %zu bytes, %zu needed", h->scratch_bytes, need);
+    WD_TRY(scratch_enough("head spectra", h->scratch_bytes, sizeof(float) * head_spectra_floats(P.B, P.F, P.Hf, P.T, P.L)));
     if (P.B == 0) return 0;
     hipStream_t st = (hipStream_t)stream;
-    const int B = P.B, Hf = P.Hf, T = P.T, L = P.L;
+    const int B = P.B, T = P.T, L = P.L;
     const StackLayout S = stack_layout(P);
-    float *zl = (float *)P.scratch + head_stack_floats(B, P.F, Hf, T, L);
-    // the lowest level whose dz something needs (head_stack_run)
-    int m = L;
-    for (int l = L; l >= 1; --l)
-        if (P.dW[l - 1] || P.db[l - 1]) m = l;
-    if (P.dslope && P.act == WD_ACT_PRELU && L > 1) m = 1;
-    if (P.dx) m = 0;
-    for (int l = 1; l < L; ++l) {
-        hipLaunchKernelGGL(head_stack_fwd_kernel, dim3(head_tiles(B, Hf, HEAD_H_TS)), dim3(256), 0, st, P, l);
-        WD_CHECK_LAUNCH("head_stack_fwd");
-    }
+    float *zl = (float *)P.scratch + head_stack_floats(B, P.F, P.Hf, T, L);
+    const int m = stack_lowest_level(P);
+    WD_TRY(stack_forward(P, st));
     hipLaunchKernelGGL(head_spectra_z_kernel, dim3(head_tiles(B, T, HEAD_H_TS)), dim3(256), 0, st, P, zl);
     WD_CHECK_LAUNCH("head_spectra_z");
     const SpectraRows R{zl, P.b[L - 1], P.table, P.ld_table, B, T, P.inv_n, h->spectra_act, h->loss_kind, h->out, S.dout, S.lossrow};
@@ -2610,17 +2623,8 @@ int wdmpnn_head_spectra(const WdHeadSpectra *h, void *stream) {
         hipLaunchKernelGGL(head_spectra_bwd_kernel, dim3((unsigned)spectra_bwd_blocks(P, Q)), dim3(256), 0, st, P, Q);
         WD_CHECK_LAUNCH("head_spectra_bwd");
     }
-    for (int l = L - 1; l >= 1; --l) {
-        StackWant Q{};
-        Q.dz = m <= l - 1;
-        Q.dw = P.dW[l - 1] != nullptr;
-        Q.db = P.db[l - 1] != nullptr;
-        Q.slope = l == 1 && P.dslope ? 2 : 0;
-        if (!(Q.dz || Q.dw || Q.db || Q.slope)) continue;
-        hipLaunchKernelGGL(head_stack_bwd_kernel, dim3((unsigned)stack_bwd_blocks(P, l, Q)), dim3(256), 0, st, P, l, Q);
-        WD_CHECK_LAUNCH("head_stack_bwd");
-    }
-    return 0;
+    bool carried;  // (never: head_spectra_bwd_kernel has the last layer's sums)
+    return stack_backward(P, m, st, 2, false, &carried);
 }
 
 int wdmpnn_head_spectra_predict(const WdHeadSpectraPredict *h, void *stream) {
@@ -2630,20 +2634,11 @@ int wdmpnn_head_spectra_predict(const WdHeadSpectraPredict *h, void *stream) {
     if (h->normalize < 0 || h->normalize > 1) return fail(WD_ERR_UNSUPPORTED, "head spectra: normalize %d", h->normalize);
     if (h->B == 0) return 0;
     if (!h->x || !h->out || !h->scratch) return fail(WD_ERR_ARG, "head spectra: null pointer");
-    const int Hf = h->L == 1 ? 1 : h->Hf;
-    const size_t need = sizeof(float) * head_spectra_predict_floats(h->B, Hf, h->T, h->L);
-    if (h->scratch_bytes < need)
-        return fail(WD_ERR_WORKSPACE, "head spectra: scratch of %zu bytes, %zu needed", h->scratch_bytes, need);
+    const WdHeadStack v = stack_view(h);  // (z_l at the start of the scratch, then z_L)
+    WD_TRY(scratch_enough("head spectra", h->scratch_bytes, sizeof(float) * head_spectra_predict_floats(v.B, v.Hf, v.T, v.L)));
     hipStream_t st = (hipStream_t)stream;
-    WdHeadStack v{};  // the stack kernels' view (no dropout; z_l at the start of the scratch, then z_L)
-    v.x = h->x; v.ld_x = h->ld_x; v.B = h->B; v.F = h->F; v.Hf = Hf; v.T = h->T; v.L = h->L;
-    for (int l = 0; l < h->L; ++l) { v.W[l] = h->W[l]; v.b[l] = h->b[l]; }
-    v.slope = h->slope; v.act = h->act; v.scratch = h->scratch;
-    float *zl = (float *)h->scratch + (size_t)(h->L - 1) * h->B * Hf;
-    for (int l = 1; l < h->L; ++l) {
-        hipLaunchKernelGGL(head_stack_fwd_kernel, dim3(head_tiles(h->B, Hf, HEAD_H_TS)), dim3(256), 0, st, v, l);
-        WD_CHECK_LAUNCH("head_stack_fwd");
-    }
+    float *zl = (float *)h->scratch + (size_t)(v.L - 1) * v.B * v.Hf;
+    WD_TRY(stack_forward(v, st));
     hipLaunchKernelGGL(head_spectra_z_kernel, dim3(head_tiles(h->B, h->T, HEAD_H_TS)), dim3(256), 0, st, v, zl);
     WD_CHECK_LAUNCH("head_spectra_z");
     const SpectraPredictRows R{zl, h->b[h->L - 1], h->out, h->mask, h->B, h->T, h->spectra_act, h->normalize};

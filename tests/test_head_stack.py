@@ -354,6 +354,54 @@ def test_stack_head_is_bitwise_repeatable_and_seeded():
     assert a['loss'] != c['loss']
 
 
+@pytest.mark.gpu
+@pytest.mark.parametrize('shape,kind,act,bias', [((5, 37, 19, 3, 1), 0, 'ReLU', True),
+                                                 ((5, 37, 19, 3, 1), 1, 'tanh', True),
+                                                 ((5, 37, 19, 3, 1), 0, 'tanh', False),   # b1 = b2 = NULL
+                                                 ((9, 700, 33, 6, 1), 0, 'tanh', True),
+                                                 ((9, 700, 33, 6, 1), 1, 'ReLU', True),
+                                                 ((9, 700, 33, 6, 3), 2, 'ReLU', True),
+                                                 ((9, 700, 33, 6, 3), 2, 'tanh', True)])
+def test_two_layer_predict_entry_is_the_stack_predict_at_two_layers(shape, kind, act, bias):
+    """wdmpnn_head_predict and wdmpnn_head_stack_predict with L = 2 on the same device inputs: bitwise equal
+    outputs (scratch and out NaN-filled first: nothing left from an earlier call can pass), and within 1e-5
+    normwise of an fp64 numpy evaluation.  B = 5 is a partial 4-row workgroup with partial 16 x 16 tiles;
+    F = 700 is three 320-deep K stages, the last one partial; kind 2 is two tasks of three classes."""
+    B, F, Hf, T, C = shape
+    g = torch.Generator().manual_seed(1000 * kind + F + ACT[act])
+    x = torch.randn(B, F, generator=g).to(DEV)
+    W1 = (torch.randn(Hf, F, generator=g) / math.sqrt(F)).to(DEV)
+    W2 = (torch.randn(T, Hf, generator=g) / math.sqrt(Hf)).to(DEV)
+    b1 = (0.3 * torch.randn(Hf, generator=g)).to(DEV) if bias else None
+    b2 = (0.3 * torch.randn(T, generator=g)).to(DEV) if bias else None
+    nan = lambda *s: torch.full(s, float('nan'), dtype=torch.float32, device=DEV)  # noqa: E731
+    a, scratch, out_two, out_stack = nan(B, Hf), nan(B * Hf), nan(B, T), nan(B, T)
+    ptr, stream = _native.ptr, _native.current_stream(DEV)
+    p = _native.WdHeadPredict(ptr(x), F, B, F, Hf, T, ptr(W1), ptr(b1), ptr(W2), ptr(b2), ACT[act], ptr(a),
+                              ptr(out_two), kind, C)
+    _native.check(_native.lib().wdmpnn_head_predict(ctypes.byref(p), stream), 'head predict')
+    q = _native.WdHeadStackPredict()
+    q.x, q.ld_x, q.B, q.F, q.Hf, q.T, q.L = ptr(x), F, B, F, Hf, T, 2
+    q.W[0], q.b[0], q.W[1], q.b[1] = ptr(W1), ptr(b1), ptr(W2), ptr(b2)
+    q.act, q.scratch, q.scratch_bytes = ACT[act], ptr(scratch), 4 * B * Hf
+    q.out, q.out_kind, q.n_classes = ptr(out_stack), kind, C
+    _native.check(_native.lib().wdmpnn_head_stack_predict(ctypes.byref(q), stream), 'head stack predict')
+    torch.cuda.synchronize()
+    assert torch.isfinite(out_two).all() and torch.equal(out_two, out_stack)
+    assert torch.equal(a.view(-1), scratch)  # (z_1 in either scratch)
+    f64 = lambda t: 0.0 if t is None else t.cpu().double().numpy()  # noqa: E731
+    z = f64(x) @ f64(W1).T + f64(b1)
+    ref = (np.maximum(z, 0) if act == 'ReLU' else np.tanh(z)) @ f64(W2).T + f64(b2)
+    if kind == 1:
+        ref = 1 / (1 + np.exp(-ref))
+    elif kind == 2:
+        e = np.exp(ref.reshape(B, T // C, C) - ref.reshape(B, T // C, C).max(axis=2, keepdims=True))
+        ref = (e / e.sum(axis=2, keepdims=True)).reshape(B, T)
+    err = golden_io.normwise(out_two.cpu().numpy(), ref)
+    print(f'two-layer predict vs fp64: {err:.2e}')
+    assert err <= TOL, err
+
+
 # ---------------------------------------------------------------------------------------------------
 # GPU: through chemprop_amd.train and MoleculeModel
 # ---------------------------------------------------------------------------------------------------
