@@ -1174,6 +1174,29 @@ int wdmpnn_debug_fwd_offsets(const WdGraph *g, const WdParams *p, const WdConfig
     return 0;
 }
 
+// debug (tests/test_split_bwd_gpu.py; not in the header): byte offsets in the backward scratch of dZo, dA, the two
+// dZ_t ping-pong buffers, dRes, dX (Y_t on the blocked path), Y_t's and M_{t-1}'s scale words and the total; what
+// wdmpnn_backward decides from the dims: D.blocked, ro_fused, x6_bm(D.Rp), k_per_split / nsplit of the W_o, W_h and
+// W_i weight-gradient plans; and the two saved operands of the weight gradients that wdmpnn_saved_layout leaves
+// out: the forward workspace's offsets of the atom aggregate A and (unblocked, depth >= 2) of X_1, and D.ldx
+int wdmpnn_debug_bwd_offsets(const WdGraph *g, const WdParams *p, const WdConfig *c, size_t *out) {
+    Dims D;
+    WD_TRY(get_dims(g, p, c, D));
+    const BwdLayout Bl = bwd_layout(g, D);
+    const FwdLayout L = fwd_layout(D, p->packed == nullptr);
+    const bool prelu = c->activation == WD_ACT_PRELU;
+    const bool ro_fused = !D.desc && D.Hk <= RO_ACT_MAXLD &&
+                          (!prelu || (D.B + 1) * RO_ACT_Y <= (int)Bl.prelu_floats);
+    const TnPlan to = tn_plan(D.Hk, x_o(g, D, nullptr), D.Va), th = tn_plan(D.Hk, x_h(D, nullptr), D.R),
+                 ti = tn_plan(D.Hk, x_in(g, D), D.R);
+    const size_t v[21] = {Bl.dZo, Bl.dA, Bl.dZ0, Bl.dZ1, Bl.dRes, Bl.dX, Bl.words, Bl.mwords, Bl.total,
+                          (size_t)D.blocked, (size_t)ro_fused, (size_t)x6_bm(D.Rp),
+                          (size_t)to.k_per_split, (size_t)to.nsplit, (size_t)th.k_per_split, (size_t)th.nsplit,
+                          (size_t)ti.k_per_split, (size_t)ti.nsplit, L.A, L.X.empty() ? 0 : L.X[0], (size_t)D.ldx};
+    memcpy(out, v, sizeof(v));
+    return 0;
+}
+
 // experiment builds (WD_STAMPS): copy the layer kernel's phase stamps of the last launch to the host
 int wdmpnn_debug_stamps(void *host, size_t bytes) {
 #if WD_STAMPS

@@ -1,6 +1,8 @@
 """Dense accuracy at the contract: the split-operand GEMMs promise the error of an fp32 GEMM, so the HIP
-training path (output and every parameter gradient; the backward's weight-gradient GEMMs cannot be made sparse)
-is held to a small multiple of what the fp32 oracle itself loses against float64, not to the 1e-5 parity bar.
+training path (output and every parameter gradient, on dense inputs) is held to a small multiple of what the
+fp32 oracle itself loses against float64, not to the 1e-5 parity bar.  The backward's weight-gradient GEMMs
+are held term by term as well: an output gradient whose columns are disjoint across molecules makes their
+sums a dozen products long (test_split_bwd_gpu.py).
 
 e_hip: the HIP result against the float64 oracle, normwise per tensor (max |x - ref| / max |ref|), the float64
 evaluation taking its kink decisions from the HIP forward's saved pre-activations (test_gpu_parity's recipe);

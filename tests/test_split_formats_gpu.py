@@ -119,22 +119,6 @@ def test_split_planes_rows_bytes():
 # ---------------------------------------------------------------------------------------------------
 # the graph's planes
 # ---------------------------------------------------------------------------------------------------
-def _full_mantissa_mols(kind, b, seed):
-    """A synthetic batch whose atom feature rows and bond feature tails are full-mantissa floats in every column
-    (bond rows stay source atom row + tail, as the reference lays them out)."""
-    rng = np.random.default_rng(seed)
-    mols = synthetic.make_batch(kind, b, seed)
-    for g in mols:
-        if not g.n_atoms:
-            continue
-        fa = sc.full_mantissa(rng, (g.n_atoms, len(g.f_atoms[0])), -20, 20)
-        g.f_atoms = [[float(v) for v in row] for row in fa]
-        tail_w = len(g.f_bonds[0]) - fa.shape[1] if g.n_bonds else 0
-        tails = sc.full_mantissa(rng, (g.n_bonds, tail_w), -20, 20)
-        g.f_bonds = [g.f_atoms[int(g.b2a[j])] + [float(v) for v in tails[j]] for j in range(g.n_bonds)]
-    return mols
-
-
 def _check_graph_planes(dg):
     """f_atoms_x6, f_bonds_x6 and f_atoms_blk_x6 against the fp32 rows the same device graph holds."""
     s = dg.struct
@@ -157,7 +141,7 @@ def _check_graph_planes(dg):
 
 
 def test_host_built_graph_planes_with_full_mantissa_features():
-    g = BatchMolGraph(_full_mantissa_mols('polymer', 8, 31), compact=False)
+    g = BatchMolGraph(sc.full_mantissa_mols(synthetic.make_batch('polymer', 8, 31), 31), compact=False)
     dg = g.device_graph(DEV, False, get_bond_fdim())
     assert not dg.built_on_device
     fa, fb = _check_graph_planes(dg)
@@ -179,7 +163,7 @@ def test_compact_graph_planes():
 def test_atom_message_graph_feature_sum_planes():
     """atom_feat_sum_x6: per atom the sum of its in-bonds' feature rows, added in fp32 in the order the packer's
     list emits them, as bf16x3 planes."""
-    g = BatchMolGraph(_full_mantissa_mols('polymer', 8, 33), compact=False)
+    g = BatchMolGraph(sc.full_mantissa_mols(synthetic.make_batch('polymer', 8, 33), 33), compact=False)
     Fb = get_bond_fdim(atom_messages=True)
     dg = g.device_graph(DEV, True, Fb)
     s = dg.struct
