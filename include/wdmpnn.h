@@ -451,6 +451,30 @@ typedef struct WdEnsembleSid {
 } WdEnsembleSid;
 int wdmpnn_ensemble_sid(const WdEnsembleSid *e, void *stream);
 
+/* Latent vectors of an ensemble (molecule_fingerprint.py:90-117, make_predictions.py:156-195): folds model k's fp32
+ * rows into the accumulators in one launch.  Per cell (b, c), c < W, with v = src[b * ld_src + c0 + c]:
+ *     cols[((row0 + b) * W + c) * M + k] = (double)v      when cols is given: the reference's
+ *                                                          all_fingerprints[N][W][M]
+ *     sum[(row0 + b) * ld_sum + c]  = v                    when sum is given and k == 0 (no zeroing needed)
+ *     sum[(row0 + b) * ld_sum + c] += v                    when sum is given and k > 0: one fp32 add, so the sum over
+ *                                                          the models in order is bitwise numpy's fp32 running sum
+ * c0 skips leading columns of src, W drops trailing ones (the feature columns behind an encoding) without a copy.
+ * One thread per cell, a fixed thread-to-element map, no atomics, plain vector stores; a NaN stays in its own cell;
+ * columns of sum at and beyond W are not written.
+ * Refused before any launch: a NULL struct, src NULL with B > 0, cols and sum both NULL (WD_ERR_ARG); B < 0, W <= 0,
+ * c0 < 0, ld_src < c0 + W, ld_sum < W with a sum, row0 < 0, M < 1, k outside [0, M) (WD_ERR_SHAPE);
+ * M > WD_ENSEMBLE_MAX_MODELS (WD_ERR_UNSUPPORTED).  B == 0 is a no-op. */
+typedef struct WdLatentAdd {
+    const float *src;         /* [B][ld_src], columns c0 .. c0 + W used             */
+    int32_t ld_src, B, W, c0;
+    int32_t M, k;             /* models in all, 0-based index of this one           */
+    int64_t row0;             /* first row of the accumulators this block covers    */
+    double *cols;             /* [rows][W][M], or NULL                              */
+    float *sum;               /* [rows][ld_sum], or NULL                            */
+    int32_t ld_sum;
+} WdLatentAdd;
+int wdmpnn_latent_add(const WdLatentAdd *e, void *stream);
+
 /* Scoring a split on the device (evaluate.py:11-77 over predict.py:10-68): the sums behind rmse, mse, mae, r2,
  * cross_entropy and accuracy, the per-row SID / Wasserstein terms of spectra, and ROC AUC by counting, from the fp32
  * predictions of the native prediction heads against a target table that stays on the device: double
@@ -688,6 +712,28 @@ typedef struct WdHeadStackPredict {
     int32_t n_classes;                     /* 1 for kinds 0 and 1, >= 2 for kind 2                  */
 } WdHeadStackPredict;
 int wdmpnn_head_stack_predict(const WdHeadStackPredict *h, void *stream);
+/* The latent vector of the same stack (model.py:123-150, fingerprint_type 'last_FFN'): the input of the FFN's last
+ * Linear in eval mode,
+ *     z_1 = x W_1^T + b_1,  z_l = act(z_{l-1}) W_l^T + b_l (l = 2 .. L-1),  out = act(z_{L-1}),
+ * as [B][ld_out], first Hf columns.  L - 1 launches: the first L - 2 are the launches wdmpnn_head_stack_predict
+ * makes (the same tile code: their z_l in the scratch are bitwise the same), the last one is layer L-1's with the
+ * activation applied as its tile is stored, straight into out.  No dropout, no output kind, no T; W[L-1] and
+ * b[L-1] are not read.  scratch: (L - 2) B Hf floats (NULL allowed for L == 2).  Columns of out at and beyond Hf
+ * are not written.  Refused before any launch: a NULL struct (WD_ERR_ARG); L < 2: there is no latent layer
+ * (WD_ERR_SHAPE); L > WD_HEAD_MAX_LAYERS, F or Hf > 4096, an unknown activation (WD_ERR_UNSUPPORTED); B < 0,
+ * F <= 0, Hf <= 0, ld_x < F, ld_out < Hf (WD_ERR_SHAPE); PReLU without its slope, or x, out or one of W_1 ..
+ * W_{L-1} NULL with B > 0 (WD_ERR_ARG); a scratch too small (WD_ERR_WORKSPACE).  B == 0 is a no-op. */
+typedef struct WdHeadLatent {
+    const float *x; int32_t ld_x;
+    int32_t B, F, Hf, L;
+    const float *W[WD_HEAD_MAX_LAYERS];
+    const float *b[WD_HEAD_MAX_LAYERS];
+    const float *slope;
+    int32_t act;
+    void *scratch; size_t scratch_bytes;
+    float *out; int32_t ld_out;            /* [B][ld_out], Hf columns written                       */
+} WdHeadLatent;
+int wdmpnn_head_stack_latent(const WdHeadLatent *h, void *stream);
 
 /* The spectra head (dataset_type spectra, model.py:102-113, train.py:70-74, spectra_utils.py): the FFN of
  * WdHeadStack (same x, layers, activation, slope, dropout hash, seed, scratch contract and gradient outputs)

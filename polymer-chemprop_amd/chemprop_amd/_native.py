@@ -47,7 +47,8 @@ EXPORTED_SYMBOLS = ('wdmpnn_abi_version', 'wdmpnn_last_error', 'wdmpnn_workspace
                     'wdmpnn_head_stack_scratch_bytes', 'wdmpnn_head_stack', 'wdmpnn_head_stack_predict',
                     'wdmpnn_head_stack_partial', 'wdmpnn_head_spectra_scratch_bytes', 'wdmpnn_head_spectra',
                     'wdmpnn_head_spectra_predict', 'wdmpnn_join_rows', 'wdmpnn_ensemble_add',
-                    'wdmpnn_ensemble_sid', 'wdmpnn_eval_add', 'wdmpnn_eval_spectra', 'wdmpnn_eval_auc')
+                    'wdmpnn_ensemble_sid', 'wdmpnn_eval_add', 'wdmpnn_eval_spectra', 'wdmpnn_eval_auc',
+                    'wdmpnn_head_stack_latent', 'wdmpnn_latent_add')
 HEAD_MAX_LAYERS = 6  # WD_HEAD_MAX_LAYERS
 HEAD_MAX_SPECTRUM = 8192  # WD_HEAD_MAX_SPECTRUM
 SPECTRA_ACTIVATIONS = {'exp': 0, 'softplus': 1}  # WdHeadSpectra.spectra_act
@@ -161,6 +162,13 @@ class WdHeadStackPredict(Structure):
                 ('out', c_void_p), ('out_kind', c_int32), ('n_classes', c_int32)]
 
 
+class WdHeadLatent(Structure):
+    _fields_ = [('x', c_void_p), ('ld_x', c_int32), ('B', c_int32), ('F', c_int32), ('Hf', c_int32), ('L', c_int32),
+                ('W', c_void_p * HEAD_MAX_LAYERS), ('b', c_void_p * HEAD_MAX_LAYERS), ('slope', c_void_p),
+                ('act', c_int32), ('scratch', c_void_p), ('scratch_bytes', c_size_t), ('out', c_void_p),
+                ('ld_out', c_int32)]
+
+
 class WdHeadSpectra(Structure):
     _fields_ = [('x', c_void_p), ('ld_x', c_int32), ('B', c_int32), ('F', c_int32), ('Hf', c_int32), ('T', c_int32),
                 ('L', c_int32), ('W', c_void_p * HEAD_MAX_LAYERS), ('b', c_void_p * HEAD_MAX_LAYERS),
@@ -196,6 +204,12 @@ class WdEnsembleAdd(Structure):
 class WdEnsembleSid(Structure):
     _fields_ = [('preds', c_void_p), ('model_stride', c_int64), ('ld', c_int32), ('M', c_int32), ('N', c_int32),
                 ('T', c_int32), ('threshold', c_double), ('out', c_void_p)]
+
+
+class WdLatentAdd(Structure):
+    _fields_ = [('src', c_void_p), ('ld_src', c_int32), ('B', c_int32), ('W', c_int32), ('c0', c_int32),
+                ('M', c_int32), ('k', c_int32), ('row0', c_int64), ('cols', c_void_p), ('sum', c_void_p),
+                ('ld_sum', c_int32)]
 
 
 class WdEvalAdd(Structure):
@@ -301,6 +315,8 @@ def lib() -> ctypes.CDLL:
     L.wdmpnn_join_rows.argtypes = [POINTER(WdJoin), c_void_p]
     L.wdmpnn_ensemble_add.argtypes = [POINTER(WdEnsembleAdd), c_void_p]
     L.wdmpnn_ensemble_sid.argtypes = [POINTER(WdEnsembleSid), c_void_p]
+    L.wdmpnn_head_stack_latent.argtypes = [POINTER(WdHeadLatent), c_void_p]
+    L.wdmpnn_latent_add.argtypes = [POINTER(WdLatentAdd), c_void_p]
     L.wdmpnn_eval_add.argtypes = [POINTER(WdEvalAdd), c_void_p]
     L.wdmpnn_eval_spectra.argtypes = [POINTER(WdEvalSpectra), c_void_p]
     L.wdmpnn_eval_auc.argtypes = [POINTER(WdEvalAuc), c_void_p]
@@ -333,7 +349,8 @@ def lib() -> ctypes.CDLL:
              'wdmpnn_head_stack_scratch_bytes', 'wdmpnn_head_stack', 'wdmpnn_head_stack_predict',
              'wdmpnn_head_stack_partial', 'wdmpnn_head_spectra_scratch_bytes', 'wdmpnn_head_spectra',
              'wdmpnn_head_spectra_predict', 'wdmpnn_join_rows', 'wdmpnn_ensemble_add', 'wdmpnn_ensemble_sid',
-             'wdmpnn_eval_add', 'wdmpnn_eval_spectra', 'wdmpnn_eval_auc'):
+             'wdmpnn_eval_add', 'wdmpnn_eval_spectra', 'wdmpnn_eval_auc', 'wdmpnn_head_stack_latent',
+             'wdmpnn_latent_add'):
         getattr(L, fn).restype = c_int
     v = L.wdmpnn_abi_version()
     if v != ABI_VERSION:

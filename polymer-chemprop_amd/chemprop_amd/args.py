@@ -53,6 +53,9 @@ class TrainArgs:
     ensemble_size: int = 1                           # args.py:299 (models trained by one chemprop_train run)
     task_names: Optional[List[str]] = None           # args.py:439 (the target columns; chemprop_predict's header)
     device_metrics: bool = False                     # (chemprop_train --device_metrics: evaluate.evaluate per epoch)
+    fingerprint_type: str = 'MPN'                    # args.py:734 ('MPN' | 'last_FFN', chemprop_fingerprint)
+    save_graph_embeddings: bool = False              # args.py:666 (chemprop_predict)
+    graph_embeddings_path: Optional[str] = None      # args.py:668 (the .npy chemprop_predict writes them to)
     # optimizer (args.py:397-407, utils.py:295-310)
     init_lr: float = 1e-4
     optimizer: str = 'adam'

@@ -52,7 +52,12 @@ restated here:
 ``chemprop_predict`` (``python -m chemprop_amd.cli predict --test_path CSV --graphs_path NPZ --preds_path OUT
 --checkpoint_dir D | --checkpoint_path P | --checkpoint_paths P ...``) is make_predictions.py's counterpart: the
 predictions of one checkpoint or the mean of an ensemble (``ensemble.predict_ensemble``), with
-``--ensemble_variance`` (spectra: the round-robin SID) and ``--individual_ensemble_predictions``.
+``--ensemble_variance`` (spectra: the round-robin SID) and ``--individual_ensemble_predictions``;
+``--save_graph_embeddings --graph_embeddings_path P`` also saves the ensemble-mean FFN inputs as a float32 ``.npy``.
+
+``chemprop_fingerprint`` (``python -m chemprop_amd.cli fingerprint ... --fingerprint_type MPN | last_FFN``, the same
+checkpoint and feature arguments) is molecule_fingerprint.py's counterpart: every checkpoint's latent vectors of
+every row (``fingerprint.molecule_fingerprint``) as ``fp_j`` / ``fp_j_model_i`` columns.
 
 The encoder runs on the HIP path (a GPU is required, like every ``chemprop_amd`` forward).  Checkpoints
 (``model.pt``, ``best_model.pt``) have the layout of the reference's ``save_checkpoint`` (utils.py:47-73):
@@ -87,7 +92,7 @@ from .model import MoleculeModel
 from .nn_utils import initialize_weights
 from .polymer import split_polymer_string, parse_polymer_rules
 from .spectra_utils import load_phase_mask, normalize_spectra, phase_row_mask, sid_metric, wasserstein_metric
-from .predict import device_predictions
+from .predict import LATENT_TYPES, device_predictions
 from .train import NoamLR, _predict_head, build_optimizer, frozen_encodings, get_loss_func, train_step
 
 
@@ -774,11 +779,9 @@ def chemprop_train(argv=None) -> Dict[str, list]:
     return run_training(parse_args(argv, spectra=True))
 
 
-def parse_predict_args(argv=None) -> argparse.Namespace:
-    """The arguments of ``chemprop_predict`` (args.py PredictArgs).  Exactly one of ``--checkpoint_dir``,
-    ``--checkpoint_path`` and ``--checkpoint_paths`` names the models (``ValueError`` otherwise)."""
-    ap = argparse.ArgumentParser(prog='chemprop_predict',
-                                 description='Predictions of a checkpoint, or of an ensemble of checkpoints.')
+def _prediction_parser(prog: str, description: str) -> argparse.ArgumentParser:
+    """The arguments ``chemprop_predict`` and ``chemprop_fingerprint`` share (args.py PredictArgs)."""
+    ap = argparse.ArgumentParser(prog=prog, description=description)
     ap.add_argument('--test_path', required=True, help='CSV with a header; the first column holds the SMILES')
     ap.add_argument('--graphs_path', required=True, help='pre-featurised MolGraph records, one per CSV row')
     ap.add_argument('--preds_path', required=True, help='the CSV to write')
@@ -793,19 +796,47 @@ def parse_predict_args(argv=None) -> argparse.Namespace:
                     help='feed the features as they are instead of through each checkpoint\'s features scaler')
     ap.add_argument('--batch_size', type=int, default=50)
     ap.add_argument('--gpu', type=int, default=0)
-    ap.add_argument('--ensemble_variance', action='store_true',
-                    help='also write the spread of the ensemble: the variance per task, the pairwise SID for spectra')
-    ap.add_argument('--individual_ensemble_predictions', action='store_true',
-                    help='also write every model\'s own predictions')
-    ap.add_argument('--drop_extra_columns', action='store_true',
-                    help='keep only the SMILES column of the input next to the predictions')
-    a = ap.parse_args(argv)
+    return ap
+
+
+def _check_prediction_args(a: argparse.Namespace) -> argparse.Namespace:
     given = [x is not None for x in (a.checkpoint_dir, a.checkpoint_path, a.checkpoint_paths)]
     if sum(given) != 1:
         raise ValueError('give exactly one of --checkpoint_dir, --checkpoint_path and --checkpoint_paths')
     if a.batch_size < 1:
         raise ValueError('--batch_size must be at least 1')
     return a
+
+
+def parse_predict_args(argv=None) -> argparse.Namespace:
+    """The arguments of ``chemprop_predict`` (args.py PredictArgs).  Exactly one of ``--checkpoint_dir``,
+    ``--checkpoint_path`` and ``--checkpoint_paths`` names the models, and ``--save_graph_embeddings`` comes with
+    ``--graph_embeddings_path`` (``ValueError`` otherwise)."""
+    ap = _prediction_parser('chemprop_predict', 'Predictions of a checkpoint, or of an ensemble of checkpoints.')
+    ap.add_argument('--ensemble_variance', action='store_true',
+                    help='also write the spread of the ensemble: the variance per task, the pairwise SID for spectra')
+    ap.add_argument('--individual_ensemble_predictions', action='store_true',
+                    help='also write every model\'s own predictions')
+    ap.add_argument('--drop_extra_columns', action='store_true',
+                    help='keep only the SMILES column of the input next to the predictions')
+    ap.add_argument('--save_graph_embeddings', action='store_true',
+                    help='also save the ensemble-mean graph embeddings (the FFN input of every row), float32 .npy')
+    ap.add_argument('--graph_embeddings_path', default=None, help='the .npy file --save_graph_embeddings writes')
+    a = _check_prediction_args(ap.parse_args(argv))
+    if a.save_graph_embeddings and not a.graph_embeddings_path:
+        raise ValueError('--save_graph_embeddings needs --graph_embeddings_path')
+    return a
+
+
+def parse_fingerprint_args(argv=None) -> argparse.Namespace:
+    """The arguments of ``chemprop_fingerprint`` (args.py FingerprintArgs): those the prediction run shares, and
+    ``--fingerprint_type``."""
+    ap = _prediction_parser('chemprop_fingerprint', 'Latent vectors of a checkpoint, or of every checkpoint of an '
+                                                    'ensemble.')
+    ap.add_argument('--fingerprint_type', choices=LATENT_TYPES, default='MPN',
+                    help='MPN: the encoder\'s output without the molecule features; last_FFN: the input of the '
+                         'FFN\'s last layer')
+    return _check_prediction_args(ap.parse_args(argv))
 
 
 def find_checkpoints(checkpoint_dir: str) -> List[str]:
@@ -925,6 +956,9 @@ def check_polymer_rows(smiles: List[str], graphs) -> None:
 def make_predictions(a: argparse.Namespace):
     """make_predictions.py:272-372 for this package's checkpoints: the ensemble's predictions of ``--test_path``
     written to ``--preds_path``; returns the mean predictions ``[N][W]`` (float64)."""
+    save_embeddings = bool(getattr(a, 'save_graph_embeddings', False))
+    if save_embeddings and not getattr(a, 'graph_embeddings_path', None):  # (before anything is loaded)
+        raise ValueError('--save_graph_embeddings needs --graph_embeddings_path')
     paths = checkpoint_paths_of(a)
     if len(paths) > ENSEMBLE_MAX_MODELS:
         raise ValueError(f'{len(paths)} checkpoints (an ensemble holds at most {ENSEMBLE_MAX_MODELS})')
@@ -943,10 +977,15 @@ def make_predictions(a: argparse.Namespace):
         phase_features = load_phase_features(a.phase_features_path, len(rows))
     if info['dataset_type'] == 'spectra' and info['spectra_phase_mask_path'] is not None:
         phase_mask = load_phase_mask(info['spectra_phase_mask_path'])
-    mean, spread, individual = predict_ensemble(
+    mean, spread, individual, *embeddings = predict_ensemble(
         paths, graphs, a.batch_size, features=features, phase_features=phase_features, phase_mask=phase_mask,
         variance=a.ensemble_variance, individual=a.individual_ensemble_predictions,
-        device=torch.device('cuda', a.gpu), features_scaling=not a.no_features_scaling)
+        device=torch.device('cuda', a.gpu), features_scaling=not a.no_features_scaling, embeddings=save_embeddings)
+    if save_embeddings:  # (make_predictions.py:191-195: averaged across the ensemble, next to the predictions)
+        parent = os.path.dirname(a.graph_embeddings_path)
+        if parent:
+            os.makedirs(parent, exist_ok=True)
+        np.save(a.graph_embeddings_path, embeddings[0])
     write_predictions(a.preds_path, header, rows, info['task_names'], mean, info['dataset_type'],
                       info['multiclass_num_classes'], spread, individual, a.drop_extra_columns)
     return mean
@@ -957,8 +996,62 @@ def chemprop_predict(argv=None):
     return make_predictions(parse_predict_args(argv))
 
 
+def write_fingerprints(path: str, smiles_header: str, smiles: List[str], fingerprints: np.ndarray) -> List[str]:
+    """The fingerprint CSV (molecule_fingerprint.py:124-147); returns its header: the SMILES column, then ``fp_j``
+    for one model, ``fp_j_model_i`` (j outer, i inner) for several.  ``fingerprints``: float64 ``[N][fp][M]``; every
+    value is written as ``str()`` of the float64, as ``csv.DictWriter`` writes the reference's."""
+    from .fingerprint import fingerprint_columns
+    fp = np.asarray(fingerprints, dtype=np.float64)
+    if fp.ndim != 3 or len(fp) != len(smiles):
+        raise ValueError(f'fingerprints of shape {fp.shape} for {len(smiles)} rows ([N][fp][M] expected)')
+    header = [smiles_header] + fingerprint_columns(fp.shape[1], fp.shape[2])
+    parent = os.path.dirname(path)
+    if parent:
+        os.makedirs(parent, exist_ok=True)
+    with open(path, 'w', newline='') as f:
+        w = csv.writer(f)
+        w.writerow(header)
+        for s, row in zip(smiles, fp.reshape(len(fp), -1)):
+            w.writerow([s] + [str(v) for v in row])
+    return header
+
+
+def make_fingerprints(a: argparse.Namespace) -> np.ndarray:
+    """molecule_fingerprint.py:16-149 for this package's checkpoints: the latent vectors of ``--test_path`` under
+    every checkpoint, written to ``--preds_path``; returns them, float64 ``[N][fp][M]``."""
+    from .fingerprint import molecule_fingerprint
+    paths = checkpoint_paths_of(a)
+    if len(paths) > ENSEMBLE_MAX_MODELS:
+        raise ValueError(f'{len(paths)} checkpoints (an ensemble holds at most {ENSEMBLE_MAX_MODELS})')
+    info = update_prediction_args(paths)
+    with open(a.test_path) as f:
+        table = list(csv.reader(f))
+    header, rows = table[0], [r for r in table[1:] if r]
+    graphs = load_graphs(a.graphs_path)
+    if len(graphs) != len(rows):
+        raise ValueError(f'{a.graphs_path} holds {len(graphs)} graphs for {len(rows)} CSV rows')
+    if info['polymer']:
+        check_polymer_rows([r[0] for r in rows], graphs)
+    features = load_input_features(a.features_path, len(rows)) if a.features_path else None
+    phase_features = None
+    if a.phase_features_path is not None:
+        phase_features = load_phase_features(a.phase_features_path, len(rows))
+    fp = molecule_fingerprint(paths, graphs, a.batch_size, a.fingerprint_type, features=features,
+                              phase_features=phase_features, features_scaling=not a.no_features_scaling,
+                              device=torch.device('cuda', a.gpu))
+    write_fingerprints(a.preds_path, header[0], [r[0] for r in rows], fp)
+    return fp
+
+
+def chemprop_fingerprint(argv=None) -> np.ndarray:
+    """Entry point (setup.py ``chemprop_fingerprint`` in the reference)."""
+    return make_fingerprints(parse_fingerprint_args(argv))
+
+
 if __name__ == '__main__':
     if sys.argv[1:2] == ['predict']:  # python -m chemprop_amd.cli predict --test_path ...
         chemprop_predict(sys.argv[2:])
+    elif sys.argv[1:2] == ['fingerprint']:  # python -m chemprop_amd.cli fingerprint --test_path ...
+        chemprop_fingerprint(sys.argv[2:])
     else:
         print(json.dumps(chemprop_train(sys.argv[1:])))

@@ -124,12 +124,20 @@ def make_batches(graphs: Sequence, batch_size: int) -> list:
 
 
 def accumulate_model(acc: PredictionSink, k: int, model, batches, scaler=None, table: Optional[FeatureTable] = None,
-                     row_mask: Optional[torch.Tensor] = None, encodings: Optional[torch.Tensor] = None) -> None:
+                     row_mask: Optional[torch.Tensor] = None, encodings: Optional[torch.Tensor] = None,
+                     embeddings: Optional[PredictionSink] = None) -> None:
     """Model ``k``'s predictions of ``batches`` into ``acc``, an ``EnsembleAccumulator`` or an ``Evaluator``: every
-    batch of ``predict.device_predictions`` (which explains the other arguments) through ``acc.add``.  No host
-    sync."""
-    for r0, out in device_predictions(model, batches, table, row_mask, encodings, n_rows=acc.n_rows):
+    batch of ``predict.device_predictions`` (which explains the other arguments) through ``acc.add``.
+    ``embeddings``: a ``fingerprint.LatentAccumulator`` that takes, in the same pass, the FFN input of every batch
+    (``with_encodings``).  No host sync."""
+    if embeddings is None:
+        for r0, out in device_predictions(model, batches, table, row_mask, encodings, n_rows=acc.n_rows):
+            acc.add(out, r0, k, scaler)
+        return
+    for r0, out, x in device_predictions(model, batches, table, row_mask, encodings, n_rows=acc.n_rows,
+                                         with_encodings=True):
         acc.add(out, r0, k, scaler)
+        embeddings.add(x, r0, k)
 
 
 def _open_model(item, device):
@@ -174,7 +182,7 @@ def model_features(model, features, features_scaler, phase_features, k: int = 0)
 
 def predict_ensemble(checkpoints_or_models, graphs: Sequence, batch_size: int, features=None, phase_features=None,
                      phase_mask=None, variance: bool = False, individual: bool = False, device=None,
-                     n_models: Optional[int] = None, features_scaling: bool = True):
+                     n_models: Optional[int] = None, features_scaling: bool = True, embeddings: bool = False):
     """The ensemble's predictions of ``graphs`` (``MolGraph`` records, one per row): ``(mean, variance,
     individual)`` as float64 numpy arrays, ``[N][W]``, ``[N][W]`` (for spectra models the per-row pairwise SID
     ``[N]``; None without ``variance``) and ``[M][N][W]`` (None without ``individual``).  W is the flat output width:
@@ -185,13 +193,18 @@ def predict_ensemble(checkpoints_or_models, graphs: Sequence, batch_size: int, f
     model is put in eval mode and sees its own feature table: the raw ``features`` ``[N][Ff]`` through its own
     ``features_scaler`` (``features_scaling=False``: as they are), ``phase_features`` ``[N][phases]`` appended
     unscaled.  Spectra predictions are normalised per row under the row's phase mask (``phase_mask``
-    ``[phases][T]``); excluded positions are NaN.  The predictions leave the device once, after the last model."""
+    ``[phases][T]``); excluded positions are NaN.  The predictions leave the device once, after the last model.
+
+    ``embeddings``: return a fourth value as well, the ensemble-mean graph embeddings (make_predictions.py:156-195
+    with ``--save_graph_embeddings``): float32 ``[N][F]``, the fp32 sum over the models, in order, of the FFN input
+    of every row (the encoding, features joined), divided by the model count; gathered in the same pass as the
+    predictions (``n_models`` is then needed with a generator of models)."""
     device = torch.device('cuda', 0) if device is None else torch.device(device)
     if n_models is None and hasattr(checkpoints_or_models, '__len__'):
         n_models = len(checkpoints_or_models)
     batches = make_batches(graphs, batch_size)
     n = len(graphs)
-    acc = spectra = None
+    acc = spectra = emb_acc = None
     row_mask = None
     k = -1
     for k, item in enumerate(checkpoints_or_models):
@@ -207,6 +220,14 @@ def predict_ensemble(checkpoints_or_models, graphs: Sequence, batch_size: int, f
                                  'predictions (or a spectra ensemble\'s spread) are wanted')
             acc = EnsembleAccumulator(n, width, device, variance=variance and not spectra, keep=keep,
                                       n_models=n_models)
+            if embeddings:
+                from .fingerprint import LatentAccumulator
+                if n_models is None:
+                    raise ValueError('predict_ensemble: pass n_models with a generator of models when the graph '
+                                     'embeddings are wanted')
+                first = next(m for m in model.ffn if isinstance(m, torch.nn.Linear))
+                emb_acc = LatentAccumulator(n, int(first.in_features), device, n_models=n_models, columns=False,
+                                            running_sum=True)
             if spectra and phase_features is not None and phase_mask is not None:
                 row_mask = torch.from_numpy(np.ascontiguousarray(phase_row_mask(phase_features, phase_mask))).to(device)
                 if tuple(row_mask.shape) != (n, width):
@@ -217,14 +238,16 @@ def predict_ensemble(checkpoints_or_models, graphs: Sequence, batch_size: int, f
                              f'ensemble\'s first model {"spectra" if spectra else "values"} of width {acc.width}')
         rows = model_features(model, features, features_scaler if features_scaling else None, phase_features, k)
         table = None if rows is None else FeatureTable(rows, device)
-        accumulate_model(acc, k, model, batches, data_scaler, table, row_mask)
+        accumulate_model(acc, k, model, batches, data_scaler, table, row_mask, embeddings=emb_acc)
         del model, table
     if acc is None:
         raise ValueError('predict_ensemble: no model given')
     if n == 0:
-        return np.zeros((0, acc.width)), None, None
+        empty = (np.zeros((0, acc.width)), None, None)
+        return empty + (np.zeros((0, emb_acc.width), dtype=np.float32),) if embeddings else empty
     mean = acc.mean().cpu().numpy()
     spread = None
     if variance:
         spread = (acc.roundrobin_sid() if spectra else acc.variance()).cpu().numpy()
-    return mean, spread, acc.individual().cpu().numpy() if individual else None
+    out = (mean, spread, acc.individual().cpu().numpy() if individual else None)
+    return out + (emb_acc.mean32().cpu().numpy(),) if embeddings else out

@@ -1,6 +1,7 @@
 """MoleculeModel (``chemprop/models/model.py:14-194``): the encoder runs on the HIP library, the
 small FFN head stays PyTorch (~1 % of the forward) except for multiclass and
-spectra prediction, which run the native prediction heads (``train.head_predict``).  Module layout and
+spectra prediction, which run the native prediction heads (``train.head_predict``), and the ``last_FFN``
+fingerprint in eval mode (``train.head_latent``).  Module layout and
 state_dict keys (``encoder.encoder.0.*``, ``ffn.1.*``, ``ffn.4.*`` ...) match the reference."""
 from __future__ import annotations
 
@@ -78,6 +79,14 @@ class MoleculeModel(nn.Module):
         if fingerprint_type == 'MPN':
             return enc
         if fingerprint_type == 'last_FFN':
+            if not self.training and not torch.is_grad_enabled() and not getattr(self, 'spectra', False):
+                # as forward takes head_predict: the native latent head (train.head_latent, L - 1 launches) for
+                # an FFN of two or more layers the stack kernels run; the torch slice below otherwise
+                from .train import _head_linears, _predict_head, head_latent
+                head = _predict_head(self)
+                if head is not None and len(_head_linears(head)) > 1 and enc.dim() == 2 and \
+                        enc.dtype == torch.float32 and enc.device == _head_linears(head)[0].weight.device:
+                    return head_latent(self, enc, head)
             return self.ffn[:-1](enc)
         raise ValueError(f'Unsupported fingerprint type {fingerprint_type}.')
 

@@ -4,7 +4,9 @@
 through ``MPNEncoder.forward_many`` (or the split's cached ``train.frozen_encodings``), ``join_features`` for a
 model with input features, the native prediction head; no host sync.  Its callers differ in where a batch goes:
 ``cli.predict`` copies it to the host, ``ensemble.accumulate_model`` hands it to a ``PredictionSink`` -- the
-``EnsembleAccumulator`` of an ensemble, or the ``Evaluator`` of ``evaluate.evaluate``.
+``EnsembleAccumulator`` of an ensemble, or the ``Evaluator`` of ``evaluate.evaluate``.  The same loop yields a
+model's latent vectors instead (``latent``), or the FFN input next to the predictions (``with_encodings``), for the
+``fingerprint.LatentAccumulator`` of ``fingerprint.molecule_fingerprint`` and of ``predict_ensemble(embeddings=True)``.
 """
 from __future__ import annotations
 
@@ -54,44 +56,80 @@ class PredictionSink:
         return hit[1], hit[2]
 
 
-def _fallback_predict(model, batch, feats, mask) -> torch.Tensor:
+def _fallback_predict(model, batch, feats, mask, return_embeddings: bool = False):
     """A model whose FFN the native prediction heads refuse: its own forward (a spectra model's output
-    normalised per row with torch ops, as ``head_predict(normalize=True)`` does it natively)."""
-    out = model([batch], feats)
+    normalised per row with torch ops, as ``head_predict(normalize=True)`` does it natively).
+    ``return_embeddings``: (predictions, the FFN input), as the model's forward returns them."""
+    if return_embeddings:
+        out, emb = model(_molecules(batch), feats, return_embeddings=True)
+    else:
+        out, emb = model(_molecules(batch), feats), None
     if getattr(model, 'spectra', False):
         m = torch.ones_like(out, dtype=torch.bool) if mask is None else mask.bool()
         s = torch.where(m, out, torch.zeros_like(out))
         out = torch.where(m, s / s.sum(dim=1, keepdim=True), torch.full_like(out, float('nan')))
-    return out
+    return (out, emb) if return_embeddings else out
+
+
+def _molecules(batch) -> list:
+    """A batch as ``MPN.forward`` takes it: one ``BatchMolGraph`` per molecule of the model's input (a batch given
+    as a single ``BatchMolGraph`` is a model of one molecule's)."""
+    return list(batch) if isinstance(batch, (list, tuple)) else [batch]
+
+
+def _encode_alone(mpn, batch) -> torch.Tensor:
+    """The encoders' output without the input features the model was trained with (molecule_fingerprint.py:30-34:
+    the ``MPN`` fingerprint needs none)."""
+    if mpn.features_only or mpn.atom_descriptors is not None:
+        raise NotImplementedError('the MPN representation without input features: a features_only model has none, '
+                                  'and atom descriptors are not supported here')
+    return torch.cat([enc(ba) for enc, ba in zip(mpn.encoder, _molecules(batch))], dim=1)
+
+
+LATENT_TYPES = ('MPN', 'last_FFN')
 
 
 @torch.no_grad()
 def device_predictions(model, batches, features: Optional[FeatureTable] = None,
                        row_mask: Optional[torch.Tensor] = None, encodings: Optional[torch.Tensor] = None,
-                       own_forward: bool = False, n_rows: Optional[int] = None
-                       ) -> Iterator[Tuple[int, torch.Tensor]]:
+                       own_forward: bool = False, n_rows: Optional[int] = None, latent: Optional[str] = None,
+                       with_encodings: bool = False) -> Iterator[Tuple]:
     """``(row0, predictions)`` of ``model`` for every ``BatchMolGraph`` of ``batches`` (row order = batch order):
     eval mode, ``no_grad``, float32 on the device, no host sync.  ``features``: the model's input features of
     every row, as the model sees them; ``row_mask``: a spectra model's included positions, bool or uint8
     ``[rows][T]`` on the device (ignored for other models): its predictions are normalised per row, the excluded
     positions NaN.  The batches run in groups of up to eight through ``forward_many``, then per batch
     ``join_features`` and the native prediction head; a model whose FFN the native heads refuse runs its own
-    forward (``_fallback_predict``).
+    forward (``_fallback_predict``).  A batch of a model of several molecules is the list of its ``BatchMolGraph`` s.
 
     ``encodings``: the rows' cached ``train.frozen_encodings``; the head runs straight from them, in the batch
     sizes of ``batches`` (which may then be a plain batch size as well; ``NotImplementedError`` without a native
     head).  ``own_forward``: every batch through ``model([batch], feats)`` and nothing else.  ``n_rows``: the rows
     the caller expects.  Molecules, feature rows and encodings that do not cover the same rows, or features for a
-    model that takes none (or the reverse), are a ``ValueError`` before anything is launched."""
-    from .train import _predict_head, head_predict  # (here: importing the package does not import the training code)
+    model that takes none (or the reverse), are a ``ValueError`` before anything is launched.
+
+    ``latent``: yield ``(row0, vectors)``, the model's representation (model.py:123-150) instead of its
+    predictions.  ``'MPN'``: the FFN's input, the encoding with the features joined, and no prediction head runs;
+    the features may then be left out for a model trained with them, and the encoders alone run.  ``'last_FFN'``:
+    ``train.head_latent`` of that input, ``[B][ffn_hidden_size]`` (``MoleculeModel.fingerprint``'s torch slice for an
+    FFN the native stack does not run).  ``with_encodings``: yield ``(row0, predictions, x)``, ``x`` being the FFN
+    input the same pass holds, as ``model.encoder(...)`` returns it."""
+    # (here: importing the package does not import the training code)
+    from .train import NO_LATENT_LAYER, _head_linears, _predict_head, head_latent, head_predict
     model.eval()
     mpn = model.encoder
+    if latent is not None and latent not in LATENT_TYPES:
+        raise ValueError(f'Fingerprint type {latent} not supported')
+    if latent is not None and (with_encodings or own_forward):
+        raise ValueError('latent vectors come instead of predictions: no with_encodings, no own_forward')
+    if with_encodings and own_forward:
+        raise ValueError('own_forward yields the model\'s output alone: no with_encodings')
     if isinstance(batches, int):
         if batches < 1 or encodings is None:
             raise ValueError('a plain batch size must be at least 1 and needs encodings')
         sizes = [min(batches, len(encodings) - s) for s in range(0, len(encodings), batches)]
     else:
-        sizes = [len(b.a_scope) for b in batches]
+        sizes = [len(_molecules(b)[0].a_scope) for b in batches]
     starts = np.cumsum([0] + sizes).tolist()
     n = starts[-1] if n_rows is None else n_rows
     if starts[-1] != n or (features is not None and len(features) != n) or \
@@ -99,35 +137,56 @@ def device_predictions(model, batches, features: Optional[FeatureTable] = None,
         raise ValueError(f'{starts[-1]} molecules, {None if features is None else len(features)} feature rows and '
                          f'{None if encodings is None else len(encodings)} encodings for {n} rows')
     needs = bool(getattr(mpn, 'use_input_features', False))
-    if needs != (features is not None):
+    alone = latent == 'MPN' and needs and features is None  # (the encoders without the features)
+    if needs != (features is not None) and not alone:
         raise ValueError('the model takes input features and none were given' if needs else
                          'the model takes no input features, but features were given')
     if own_forward and encodings is not None:
         raise ValueError('own_forward runs the encoder: it takes no encodings')
     head = None if own_forward else _predict_head(model)
+    spectra = bool(getattr(model, 'spectra', False))
+    if latent == 'last_FFN':
+        if spectra:
+            raise ValueError('a spectra model has no last_FFN representation of width ffn_hidden_size. Use MPN '
+                             'fingerprint type instead.')
+        if sum(isinstance(m, torch.nn.Linear) for m in model.ffn) < 2:
+            raise ValueError(NO_LATENT_LAYER)
+    if latent == 'MPN' and mpn.features_only:
+        raise ValueError('With features_only models, there is no latent MPN representation. Use last_FFN '
+                         'fingerprint type instead.')
     if encodings is not None and head is None:
         raise NotImplementedError('predictions from encodings: the model\'s FFN is not one the native heads run')
     findex = features.index(range(n)) if features is not None and n else None
-    spectra = bool(getattr(model, 'spectra', False))
-    many = encodings is None and head is not None and not mpn.features_only and len(mpn.encoder) == 1 and \
-        mpn.atom_descriptors is None
+    many = encodings is None and (head is not None or latent == 'MPN') and not mpn.features_only and \
+        len(mpn.encoder) == 1 and mpn.atom_descriptors is None
     for g0 in range(0, len(sizes), 8):
-        embs = mpn.encoder[0].forward_many(batches[g0:g0 + 8]) if many else [None] * len(sizes[g0:g0 + 8])
+        embs = mpn.encoder[0].forward_many([_molecules(b)[0] for b in batches[g0:g0 + 8]]) if many else \
+            [None] * len(sizes[g0:g0 + 8])
         for j, emb in enumerate(embs, g0):
             r0, r1 = starts[j], starts[j + 1]
             feats = None if findex is None else findex[r0:r1]
             mask = None if row_mask is None or not spectra else row_mask[r0:r1]
             if own_forward:
-                out = model([batches[j]], feats)
-            elif head is None:
-                out = _fallback_predict(model, batches[j], feats, mask)
+                yield r0, model(_molecules(batches[j]), feats)
+                continue
+            if head is None and latent is None:
+                out = _fallback_predict(model, batches[j], feats, mask, with_encodings)
+                yield (r0,) + tuple(out) if with_encodings else (r0, out)
+                continue
+            if encodings is not None:
+                emb = encodings[r0:r1]
+            if emb is None:
+                x = _encode_alone(mpn, batches[j]) if alone else mpn(_molecules(batches[j]), feats)
             else:
-                if encodings is not None:
-                    emb = encodings[r0:r1]
-                if emb is None:
-                    x = mpn([batches[j]], feats)
-                else:
-                    x = emb if feats is None else join_features(emb, feats)
-                out = head_predict(model, x, head, normalize=True, mask=mask) if spectra else \
-                    head_predict(model, x, head)
-            yield r0, out
+                x = emb if feats is None else join_features(emb, feats)
+            if latent == 'MPN':
+                yield r0, x
+                continue
+            native = head is not None and x.dim() == 2 and x.dtype == torch.float32 and \
+                x.device == _head_linears(head)[0].weight.device
+            if latent == 'last_FFN':
+                yield r0, head_latent(model, x, head) if native else model.ffn[:-1](x)
+                continue
+            out = head_predict(model, x, head, normalize=True, mask=mask) if spectra else \
+                head_predict(model, x, head)
+            yield (r0, out, x) if with_encodings else (r0, out)

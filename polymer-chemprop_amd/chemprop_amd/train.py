@@ -629,12 +629,14 @@ def _scale_all(grads, gl: torch.Tensor) -> None:
 
 def _fill_ffn(h, x: torch.Tensor, linears, slope, act: int):
     """The FFN on the encodings x [B][F] (contiguous) written into the fields the stack and spectra structs
-    share (``WdHeadStack``, ``WdHeadStackPredict``, ``WdHeadSpectra``, ``WdHeadSpectraPredict``); returns
+    share (``WdHeadStack``, ``WdHeadStackPredict``, ``WdHeadSpectra``, ``WdHeadSpectraPredict``, ``WdHeadLatent``); returns
     (B, F, Hf, T, L) as written (Hf 0 for one layer)."""
     B, F = x.shape
     L, T = len(linears), linears[-1].out_features
     Hf = linears[0].out_features if L > 1 else 0
-    h.x, h.ld_x, h.B, h.F, h.Hf, h.T, h.L = x.data_ptr(), F, B, F, Hf, T, L
+    h.x, h.ld_x, h.B, h.F, h.Hf, h.L = x.data_ptr(), F, B, F, Hf, L
+    if hasattr(h, 'T'):  # (WdHeadLatent stops below the last Linear: no outputs)
+        h.T = T
     for i, l in enumerate(linears):
         h.W[i], h.b[i] = l.weight.data_ptr(), 0 if l.bias is None else l.bias.data_ptr()
     h.slope, h.act = 0 if slope is None else slope.data_ptr(), act
@@ -758,6 +760,16 @@ def _head_linears(head) -> list:
     return list(_head_parts(head)[0])
 
 
+def _head_input(emb: torch.Tensor, l1: nn.Linear) -> torch.Tensor:
+    """The encodings ``emb`` as the eval-mode heads read them (detached, contiguous); ``ValueError`` unless they
+    are float32 ``[B][in_features]`` on the device of the FFN's first Linear ``l1``."""
+    if emb.dim() != 2 or emb.shape[1] != l1.in_features or emb.device != l1.weight.device or \
+            emb.dtype != torch.float32:
+        raise ValueError(f'encodings of shape {tuple(emb.shape)} ({emb.dtype}, {emb.device}) for an FFN input of '
+                         f'{l1.in_features} on {l1.weight.device}')
+    return emb.detach().contiguous()
+
+
 def head_predict(model: nn.Module, emb: torch.Tensor, head=None, normalize: bool = False,
                  mask: Optional[torch.Tensor] = None) -> torch.Tensor:
     """The eval-mode predictions of ``model`` from the encodings ``emb`` (model.py:152-194 after the
@@ -780,12 +792,7 @@ def head_predict(model: nn.Module, emb: torch.Tensor, head=None, normalize: bool
         raise NotImplementedError('head_predict: the model\'s FFN is not one the native head runs (Dropout / Linear / '
                                   'activation stacks of create_ffn, <= 64 outputs, a single PReLU slope)')
     linears, act, slope, kind, n_classes, spectra = _head_parts(head)
-    l1 = linears[0]
-    if emb.dim() != 2 or emb.shape[1] != l1.in_features or emb.device != l1.weight.device or \
-            emb.dtype != torch.float32:
-        raise ValueError(f'encodings of shape {tuple(emb.shape)} ({emb.dtype}, {emb.device}) for an FFN input of '
-                         f'{l1.in_features} on {l1.weight.device}')
-    x = emb.detach().contiguous()
+    x = _head_input(emb, linears[0])
     dev = x.device
     if (normalize or mask is not None) and spectra is None:
         raise ValueError('head_predict: normalize / mask are for spectra models')
@@ -809,6 +816,42 @@ def head_predict(model: nn.Module, emb: torch.Tensor, head=None, normalize: bool
         entry, what = _native.lib().wdmpnn_head_spectra_predict, 'FFN head spectra (predict)'
     _native.check(entry(ctypes.byref(h), _native.current_stream(dev)), what)
     return out.view(B, T // n_classes, n_classes) if kind == 2 and spectra is None else out
+
+
+NO_LATENT_LAYER = 'With a ffn_num_layers of 1, there is no latent FFN representation. Use MPN fingerprint type instead.'
+
+
+def head_latent(model: nn.Module, emb: torch.Tensor, head=None) -> torch.Tensor:
+    """The input of the FFN's last Linear in eval mode from the encodings ``emb`` (model.py:123-150,
+    ``fingerprint_type='last_FFN'``: ``ffn[:-1](emb)``) as ``[B][ffn_hidden_size]`` float32 on the device: L - 1 HIP
+    launches (``wdmpnn_head_stack_latent``), the first L - 2 of them those of ``head_predict``.  ``head``: the
+    model's ``_predict_head``, as ``head_predict`` takes it.  No autograd graph is built.
+    ``NotImplementedError`` for an FFN the native stack does not run; ``ValueError`` for a model in training mode,
+    for ``ffn_num_layers == 1`` (molecule_fingerprint.py:83-87) and for a spectra model: its ``ffn[:-1]`` strips
+    only the output activation, so the reference's latent array of width ``ffn_hidden_size`` cannot hold it."""
+    if model.training:
+        raise ValueError('head_latent is an eval-mode head: call model.eval() first')
+    if head is None:
+        head = _predict_head(model)
+    if head is None:
+        raise NotImplementedError('head_latent: the model\'s FFN is not one the native head runs (Dropout / Linear / '
+                                  'activation stacks of create_ffn, <= 64 outputs, a single PReLU slope)')
+    linears, act, slope, _, _, spectra = _head_parts(head)
+    if spectra is not None:
+        raise ValueError('head_latent: a spectra model has no last_FFN representation (its ffn[:-1] ends with the '
+                         'last Linear, of the spectrum\'s width, not ffn_hidden_size). Use MPN fingerprint type instead.')
+    if len(linears) < 2:
+        raise ValueError(NO_LATENT_LAYER)
+    x = _head_input(emb, linears[0])
+    dev = x.device
+    h = _native.WdHeadLatent()
+    B, _, Hf, _, L = _fill_ffn(h, x, linears, slope, act)
+    scratch = torch.empty(max((L - 2) * B * Hf, 4), dtype=torch.float32, device=dev)  # (z_1 .. z_{L-2})
+    out = torch.empty((B, Hf), dtype=torch.float32, device=dev)
+    h.scratch, h.scratch_bytes, h.out, h.ld_out = scratch.data_ptr(), scratch.numel() * 4, out.data_ptr(), Hf
+    _native.check(_native.lib().wdmpnn_head_stack_latent(ctypes.byref(h), _native.current_stream(dev)),
+                  'FFN head stack (latent)')
+    return out
 
 
 def _grad_buffer(p: torch.Tensor) -> torch.Tensor:

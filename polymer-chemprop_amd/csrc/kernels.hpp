@@ -1145,6 +1145,7 @@ __global__ __launch_bounds__(256) void scale_kernel(ScaleJobs J) {
 //                                         tile's dslope term, dW_l = dz_l^T a_{l-1}, db_l; the launch of l = L-1
 //                                         adds dW_L, db_L and the loss, the launch of l = 1 sums dslope
 //   head_stack_last_kernel (L == 1, or no backward launch left): dW_L, db_L, the loss
+//   head_stack_latent_kernel (wdmpnn_head_stack_latent): layer L-1 with the activation in its epilogue, a_{L-1}
 // 2 L - 1 launches (2 for L == 1).  wdmpnn_head_stack_partial runs the same kernels for any subset of the
 // gradients (StackWant): the dz chain stops at the lowest level something needs, ranges nobody wants take no
 // workgroups, and head_stack_last_kernel carries the last layer's sums when no backward launch remains.
@@ -1459,5 +1460,58 @@ __global__ __launch_bounds__(256) void head_stack_predict_rows_kernel(WdHeadStac
         v = expf(v - m) / e;
     }
     P.out[(size_t)row * T + lane] = v;
+}
+
+// The latent vector (wdmpnn_head_stack_latent): a_{L-1} = act(z_{L-1}), the input of the last Linear in eval
+// mode, which the prediction above never stores.  The layers below L-1 are head_stack_fwd_kernel's launches as
+// they are; this is layer L-1's: the same tile routine, A operand built as it is staged (x itself for L == 2),
+// and the activation in the output epilogue, written into out [B][ld_out] instead of the scratch.
+template <int ACT>
+struct StackAct {
+    float slope;
+    bool raw;  // (the operand is x: no activation site in front of the first layer)
+    __device__ __forceinline__ float operator()(float z, int, int) const {
+        return raw ? z : act_fwd(ACT, z, slope);
+    }
+};
+__global__ __launch_bounds__(256) void head_stack_latent_kernel(WdHeadStack P, float *out, int ld_out) {
+    __shared__ SmallGemmLds<HEAD_H_TS> L;
+    const size_t plane = (size_t)P.B * P.Hf;
+    const int l = P.L - 1, K = l == 1 ? P.F : P.Hf;
+    const float *z = (const float *)P.scratch;
+    const SmallGemm G{l == 1 ? P.x : z + (l - 2) * plane, l == 1 ? P.ld_x : P.Hf, 1, P.W[l - 1], 1, K, P.b[l - 1],
+                      out, ld_out, P.B, P.Hf, K};
+    with_act(P.act, [&](auto act_c) {
+        constexpr int ACT = decltype(act_c)::value;
+        const StackAct<ACT> in{stack_slope(P.slope, P.act), l == 1};
+        StackAct<ACT> act{in.slope, false};
+        SgIdentity id;
+        small_gemm_tile_f<HEAD_H_TS, true, false>(G, blockIdx.x, L, in, id, act);
+    });
+}
+
+// An ensemble's latent accumulators (wdmpnn_latent_add): model k's fp32 rows src [B][ld_src], columns c0 ..
+// c0 + W, into cols [rows][W][M] (double: molecule_fingerprint.py:90,117's all_fingerprints) and / or the fp32
+// running sum [rows][ld_sum] of make_predictions.py:163-166 (k == 0 stores, k > 0 adds once: numpy's fold in
+// model order).  One thread per cell, grid-stride; no atomics, plain vector stores.
+struct LatentAddArgs {
+    const float *src;
+    double *cols;
+    float *sum;
+    long long row0;
+    int B, W, c0, ld_src, ld_sum, M, k;
+};
+__global__ __launch_bounds__(256) void latent_add_kernel(const LatentAddArgs A) {
+    const size_t total = (size_t)A.B * A.W;
+    for (size_t t = (size_t)blockIdx.x * blockDim.x + threadIdx.x; t < total; t += (size_t)gridDim.x * blockDim.x) {
+        const int b = (int)(t / A.W), c = (int)(t - (size_t)b * A.W);
+        const float v = A.src[(size_t)b * A.ld_src + A.c0 + c];
+        const size_t row = (size_t)(A.row0 + b);
+        if (A.cols) A.cols[(row * A.W + c) * A.M + A.k] = (double)v;
+        if (A.sum) {
+            float *s = A.sum + row * A.ld_sum + c;
+            *s = A.k == 0 ? v : *s + v;
+        }
+    }
 }
 }  // namespace wd

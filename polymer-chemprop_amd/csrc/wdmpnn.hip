@@ -1834,6 +1834,36 @@ int wdmpnn_ensemble_sid(const WdEnsembleSid *e, void *stream) {
     return 0;
 }
 
+int wdmpnn_latent_add(const WdLatentAdd *e, void *stream) {
+    WD_KERNELS_OK();
+    if (!e) return fail(WD_ERR_ARG, "latent_add: null struct");
+    if (!e->cols && !e->sum) return fail(WD_ERR_ARG, "latent_add: neither cols nor sum");
+    if (e->B < 0 || e->W <= 0 || e->c0 < 0 || (int64_t)e->ld_src < (int64_t)e->c0 + e->W || (e->sum && e->ld_sum < e->W) ||
+        e->row0 < 0 || e->M < 1 || e->k < 0 || (e->M <= WD_ENSEMBLE_MAX_MODELS && e->k >= e->M))
+        return fail(WD_ERR_SHAPE, "latent_add: needs B >= 0, W > 0, c0 >= 0, ld_src >= c0 + W, ld_sum >= W, row0 >= 0, "
+                    "M >= 1, 0 <= k < M (got B %d W %d c0 %d ld_src %d ld_sum %d row0 %lld M %d k %d)", e->B, e->W, e->c0,
+                    e->ld_src, e->ld_sum, (long long)e->row0, e->M, e->k);
+    if (e->M > WD_ENSEMBLE_MAX_MODELS)
+        return fail(WD_ERR_UNSUPPORTED, "latent_add: %d models (at most %d)", e->M, WD_ENSEMBLE_MAX_MODELS);
+    if (e->B == 0) return 0;
+    if (!e->src) return fail(WD_ERR_ARG, "latent_add: null src");
+    LatentAddArgs A{};
+    A.src = e->src;
+    A.cols = e->cols;
+    A.sum = e->sum;
+    A.row0 = e->row0;
+    A.B = e->B;
+    A.W = e->W;
+    A.c0 = e->c0;
+    A.ld_src = e->ld_src;
+    A.ld_sum = e->ld_sum;
+    A.M = e->M;
+    A.k = e->k;
+    hipLaunchKernelGGL(latent_add_kernel, dim3(ew_blocks((size_t)e->B * e->W)), dim3(256), 0, (hipStream_t)stream, A);
+    WD_CHECK_LAUNCH("latent_add");
+    return 0;
+}
+
 int wdmpnn_eval_add(const WdEvalAdd *e, void *stream) {
     WD_KERNELS_OK();
     if (!e) return fail(WD_ERR_ARG, "eval_add: null struct");
@@ -2592,6 +2622,36 @@ int wdmpnn_head_stack_predict(const WdHeadStackPredict *h, void *stream) {
     if (!h->x || !h->out || (h->L > 1 && !h->scratch)) return fail(WD_ERR_ARG, "head stack: null pointer");
     WD_TRY(scratch_enough("head stack", h->scratch_bytes, sizeof(float) * (size_t)(h->L - 1) * h->B * h->Hf));
     return stack_predict_run(h, (hipStream_t)stream);
+}
+
+int wdmpnn_head_stack_latent(const WdHeadLatent *h, void *stream) {
+    WD_KERNELS_OK();
+    if (!h) return fail(WD_ERR_ARG, "null head");
+    if (h->L < 2) return fail(WD_ERR_SHAPE, "head latent: %d layers (an FFN of one layer has no latent layer)", h->L);
+    if (h->L > WD_HEAD_MAX_LAYERS)
+        return fail(WD_ERR_UNSUPPORTED, "head latent: %d layers (at most %d)", h->L, WD_HEAD_MAX_LAYERS);
+    if (h->act == WD_ACT_PRELU && !h->slope) return fail(WD_ERR_ARG, "head latent: PReLU without its slope");
+    // (head_check's activation test is the two-layer head's; one output and no output kind stand in for T)
+    WD_TRY(head_check(h->B, h->F, h->Hf, 1, h->ld_x, h->act == WD_ACT_PRELU ? (int)WD_ACT_RELU : h->act, 0, 1));
+    if (h->ld_out < h->Hf) return fail(WD_ERR_SHAPE, "head latent: ld_out %d for %d columns", h->ld_out, h->Hf);
+    if (h->B == 0) return 0;
+    if (!h->x || !h->out || (h->L > 2 && !h->scratch)) return fail(WD_ERR_ARG, "head latent: null pointer");
+    WdHeadStack P{};  // the stack kernels' view: the layers below the last, z_l at the start of the scratch
+    P.x = h->x; P.ld_x = h->ld_x; P.B = h->B; P.F = h->F; P.Hf = h->Hf; P.T = 1; P.L = h->L;
+    for (int l = 0; l < h->L - 1; ++l) {
+        if (!h->W[l]) return fail(WD_ERR_ARG, "head latent: null weight %d", l);
+        P.W[l] = h->W[l]; P.b[l] = h->b[l];
+    }
+    P.slope = h->slope; P.act = h->act; P.scratch = h->scratch;
+    WD_TRY(scratch_enough("head latent", h->scratch_bytes, sizeof(float) * (size_t)(h->L - 2) * h->B * h->Hf));
+    hipStream_t st = (hipStream_t)stream;
+    WdHeadStack below = P;  // z_1 .. z_{L-2}: wdmpnn_head_stack_predict's launches
+    below.L = h->L - 1;
+    WD_TRY(stack_forward(below, st));
+    hipLaunchKernelGGL(head_stack_latent_kernel, dim3(head_tiles(P.B, P.Hf, HEAD_H_TS)), dim3(256), 0, st, P, h->out,
+                       (int)h->ld_out);
+    WD_CHECK_LAUNCH("head_stack_latent");
+    return 0;
 }
 
 // the checks wdmpnn_head_spectra and wdmpnn_head_spectra_predict share: head_stack_check's (with one output in
