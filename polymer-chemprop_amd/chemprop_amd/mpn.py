@@ -191,14 +191,17 @@ class MPNEncoder(nn.Module):
         state.update(_pack_cache=None, _train_pack=None, _infer_configs={}, _plan_token=object())
         return state
 
-    def _config(self, save: bool) -> _native.WdConfig:
+    def _config(self, save: bool, infer: bool = False) -> _native.WdConfig:
+        """``infer``: the config of a cached inference plan -- never with dropout, whatever mode the encoder
+        is in when the plan is made (``prepare`` on a training-mode encoder): ``_infer`` uses a plan only
+        when no dropout applies, and the plan key carries no training flag."""
         c = _native.WdConfig()
         c.depth = self.depth
         c.undirected = int(bool(self.undirected))
         c.activation = _native.ACTIVATIONS[self.activation]
         c.aggregation = _native.AGGREGATIONS[self.aggregation]
         c.aggregation_norm = float(self.aggregation_norm)
-        p = float(self.dropout) if self.training else 0.0
+        p = float(self.dropout) if self.training and not infer else 0.0
         c.dropout = p
         if p > 0.0:
             c.seed = _dropout_seed()
@@ -285,7 +288,7 @@ class MPNEncoder(nn.Module):
         gs = self._graph_struct(dg)
         cfg = self._infer_configs.get(ckey)
         if cfg is None:
-            cfg = self._infer_configs[ckey] = self._config(False)
+            cfg = self._infer_configs[ckey] = self._config(False, infer=True)
         pstruct, _ = self._packed_params(gs, cfg, params, device, sid=sid)
         nbytes = ctypes.c_size_t()
         _native.check(_native.lib().wdmpnn_workspace_bytes(ctypes.byref(gs), ctypes.byref(pstruct),

@@ -183,6 +183,77 @@ def edge_case_batch(seed: int, star_leaves: int = 70) -> List[SynthMolGraph]:
             star_graph(rng, star_leaves), polymer_graph(rng, 3, 5)]
 
 
+def _rule_hub(rng: np.random.Generator, spokes, skeleton_leaves: int = 0) -> SynthMolGraph:
+    """Atom 0 with one leaf per entry of ``spokes``; spoke i is the RULE pair (0, i, w_out, w_in): ``w_in``
+    weighs the bond into the hub (slot i - 1 of the hub's a2b row), ``w_out`` the bond into leaf i.  The first
+    ``skeleton_leaves`` leaves also have a skeleton bond to the hub (weight 1, ahead of every rule bond)."""
+    n = len(spokes) + 1
+    pairs = {(0, i) for i in range(1, skeleton_leaves + 1)}
+    rules = [(0, i + 1, float(wo), float(wi)) for i, (wo, wi) in enumerate(spokes)]
+    return _build(rng, n, pairs, rules, [1.0] * n, 1.0)
+
+
+def weight_case_batch(seed: int) -> List[SynthMolGraph]:
+    """The special values of the weighted MPNN on small molecules: every molecule has <= 32 bond rows and
+    <= 17 atoms (the one-launch forward's domain, csrc/small_fwd.hpp), and the gather builders' branches on
+    ``w == 0`` and ``w == 1`` (csrc/compact.hpp ``plan``, csrc/packer.cpp ``gathers``, csrc/graph_build.hpp
+    ``build_structure``) and the ELL width (8 entries, then the CSR tail) all run.  In order:
+
+    0   hub, 10 rule spokes: 8 non-zero in-weights + 2 zero ones (slots 1 and 5, so "the first 8 non-zero"
+        is not "the first 8"): the hub's aggregate row fills the ELL exactly.  Spoke (w_out, w_in) pairs
+        (0, .5) (.3, 0) (1, 1) (.25, 1) (1, .75) (0, 0) and values above 1
+    1   three atoms in a chain, self-loop rules (0, 1) on atom 0 and (1, 1) on atom 1, and a (0, 0) rule pair
+        0 - 2 added LAST (deleting its two bond rows renumbers nothing)
+    2   empty molecule             3   single atom             4   two atoms joined by one rule pair
+        (molecules 0 - 4 have 32 bond rows and 17 atoms together: one full block of the one-launch forward)
+    5   hub, 8 rule spokes, every in-weight non-zero (ELL full, no tail)
+    6   hub, 9 rule spokes, every in-weight non-zero (one CSR tail entry)
+    7   hub, 11 rule spokes, in-weights 0 in slots 0 and 4: 9 non-zero (tail entry = slot 10)
+    8   hub, 12 rule spokes, zeros in slots 3 and 10
+    9   hub, 5 leaves with a skeleton bond AND a rule pair each: in-degree 10, weight-1 bonds first
+    10  hub, 16 rule spokes (32 bond rows, 17 atoms), zeros in slots 2, 7 and 12
+    11-13  ``polymer_graph(rng, 2, 4)``: 24 - 32 bond rows
+
+    Weights that are not 0, 1 or one of the values above are distinct multiples of 1/211 below 1 (never
+    exact in binary, so ``w - 1`` rounds).  ``w_atoms`` are distinct per atom over the whole batch and one
+    of them (hub 0's leaf 3) is exactly 0; ``degree_of_polym`` is distinct per molecule and never 1.
+    Deterministic in ``seed`` (features, fractions, polymers)."""
+    rng = np.random.default_rng(seed)
+    frac = iter((rng.permutation(200) + 5) / 211.0)
+
+    def spokes(n, zeros_in=(), special=()):
+        out = []
+        for i in range(n):
+            wo, wi = next(frac), next(frac)
+            if i in zeros_in:
+                wi = 0.0
+            out.append((wo, wi))
+        for i, pair in special:
+            out[i] = pair
+        return out
+
+    hub0 = [(0.0, 0.5), (0.3, 0.0), (1.0, 1.0), (0.25, 1.0), (1.0, 0.75), (0.0, 0.0), (next(frac), next(frac)),
+            (1.5, next(frac)), (next(frac), 2.0), (1.25, 1.75)]
+    tri = _build(rng, 3, {(0, 1), (1, 2)}, [(0, 0, 0.0, 1.0), (1, 1, 1.0, 1.0), (0, 2, 0.0, 0.0)], [1.0] * 3, 1.0)
+    two = _build(rng, 2, set(), [(0, 1, next(frac), 1.0)], [1.0] * 2, 1.0)
+    mols = [_rule_hub(rng, hub0), tri, empty_graph(), single_atom_graph(rng), two,
+            _rule_hub(rng, spokes(8, special=[(2, (1.0, 1.0)), (5, (0.0, next(frac))), (7, (next(frac), 1.0))])),
+            _rule_hub(rng, spokes(9, special=[(0, (1.0, 1.0)), (3, (0.0, next(frac))), (8, (1.5, 1.0))])),
+            _rule_hub(rng, spokes(11, zeros_in=(0, 4), special=[(6, (1.0, 1.0)), (10, (0.0, 2.0))])),
+            _rule_hub(rng, spokes(12, zeros_in=(3, 10), special=[(1, (0.0, 1.25)), (8, (1.0, 1.0)), (11, (0.25, 1.0))])),
+            _rule_hub(rng, spokes(5, special=[(1, (1.0, 1.0)), (3, (0.0, next(frac)))]), skeleton_leaves=5),
+            _rule_hub(rng, spokes(16, zeros_in=(2, 7, 12), special=[(5, (1.0, 1.0)), (9, (1.0, 0.75)),
+                                                                     (15, (0.0, 1.5))]))]
+    mols += [polymer_graph(rng, 2, 4) for _ in range(3)]
+    wa = iter((rng.permutation(150) + 20) / 173.0)
+    for k, g in enumerate(mols):
+        g.w_atoms = [float(next(wa)) for _ in range(g.n_atoms)]
+        g.degree_of_polym = 1.0 + (k + 1) / 7.0 + (0.5 if k % 3 == 0 else 0.0)
+        g.is_polymer = True
+    mols[0].w_atoms[3] = 0.0
+    return mols
+
+
 def synthetic_parameter(name: str, shape, seed: int) -> np.ndarray:
     """Deterministic values for one parameter, keyed by its state_dict name (golden fixtures).
 

@@ -23,10 +23,10 @@ KINDS = {'polymer': 0, 'qm9': 1, 'zinc': 2}
 def batches():
     return [('polymer', synthetic.make_batch('polymer', 64, 3)), ('qm9', synthetic.make_batch('qm9', 40, 4)),
             ('zinc', synthetic.make_batch('zinc', 24, 5)), ('edge', synthetic.edge_case_batch(9, star_leaves=20)),
-            ('polymer_small', synthetic.make_batch('polymer', 3, 11))]
+            ('polymer_small', synthetic.make_batch('polymer', 3, 11)), ('weights', synthetic.weight_case_batch(12))]
 
 
-@pytest.mark.parametrize('case', range(5))
+@pytest.mark.parametrize('case', range(6))
 @pytest.mark.parametrize('tail_mode', [False, True])
 def test_encode_decode_roundtrip(case, tail_mode):
     name, mols = batches()[case]
@@ -41,7 +41,7 @@ def test_encode_decode_roundtrip(case, tail_mode):
     assert np.array_equal(np.float32(g.degree_of_polym), np.float32(h.degree_of_polym))
 
 
-@pytest.mark.parametrize('case', range(5))
+@pytest.mark.parametrize('case', range(6))
 def test_plan_matches_host_blocks_and_entries(case):
     """compact_stage's molecule blocks = BatchMolGraph.molecule_blocks(); its per-block first entries and
     totals = the host packer's gather lists (csrc/packer.cpp ``gathers``)."""
@@ -163,7 +163,7 @@ def _arrays(dg):
 
 
 @pytest.mark.gpu
-@pytest.mark.parametrize('case', range(5))
+@pytest.mark.parametrize('case', range(6))
 @pytest.mark.parametrize('tail_mode', [False, True])
 def test_device_built_graph_equals_host_built(case, tail_mode):
     name, mols = batches()[case]

@@ -17,6 +17,7 @@ BATCHES = {
     'qm9': lambda: synthetic.make_batch('qm9', 32, 4),
     'edge': lambda: synthetic.edge_case_batch(6),
     'zinc': lambda: synthetic.make_batch('zinc', 8, 5),
+    'weights': lambda: synthetic.weight_case_batch(6),
 }
 
 

@@ -15,6 +15,7 @@ GRAPHS = {
     'qm9': lambda: synthetic.make_batch('qm9', 16, 2),
     'edge': lambda: synthetic.edge_case_batch(3),
     'zinc': lambda: synthetic.make_batch('zinc', 4, 4),
+    'weights': lambda: synthetic.weight_case_batch(5),
 }
 
 
@@ -143,6 +144,83 @@ def check_ell(csr, blk_b, bstart, idx, coef, W):
         for e in range(csr.ptr[r] + W, csr.ptr[r + 1]):
             out[r] += csr.coef[e] * S[csr.idx[e]]
     np.testing.assert_allclose(out[1:], csr.apply(S)[1:], rtol=1e-6, atol=1e-6)
+
+
+def test_weight_cases_zero_and_unit_weights_in_the_lists():
+    """synthetic.weight_case_batch, entry by entry: a zero-weight bond is in no aggregate row and no ELL
+    slot; a message row holds its source atom's non-zero in-bonds in a2b slot order, the reverse bond with
+    coefficient w - 1 -- absent at w = 1, present with -1 at w = 0; the ELL rows hold the first 8 of those
+    entries and bit 7 of the last index is set exactly on rows with 9 or more; the totals are
+    compact_stage's."""
+    from chemprop_amd.featurization import ELLW, _packer, ell_rows
+    mols = synthetic.weight_case_batch(5)
+    assert max(m.n_bonds for m in mols) == 32 and max(m.n_atoms for m in mols) == 17
+    g = BatchMolGraph(mols)
+    assert g._compact is not None, g._compact_why
+    w, rev, b2a = g.w_bonds.numpy(), g.b2revb.numpy(), g.b2a.numpy()
+    in_of = [g._in_idx[g._in_ptr[a]:g._in_ptr[a + 1]] for a in range(g.n_atoms)]
+    msg, agg = g.bond_message_gather(), g.atom_aggregate_gather()
+    zero = np.nonzero(w[1:] == 0)[0] + 1
+    assert len(zero) >= 12 and not np.isin(agg.idx, zero).any()
+    for a in range(g.n_atoms):
+        keep = in_of[a][w[in_of[a]] != 0]
+        e = slice(agg.ptr[a], agg.ptr[a + 1])
+        assert np.array_equal(agg.idx[e], keep) and np.array_equal(agg.coef[e], w[keep])
+    seen = {'rev_one': 0, 'rev_zero': 0, 'rev_other': 0}
+    for b in range(1, g.n_bonds):
+        r = rev[b]
+        e = slice(msg.ptr[b], msg.ptr[b + 1])
+        row = dict(zip(msg.idx[e].tolist(), msg.coef[e].tolist()))
+        assert len(row) == msg.ptr[b + 1] - msg.ptr[b]  # no bond twice
+        assert r in in_of[b2a[b]]
+        if w[r] == 1:
+            assert r not in row
+            seen['rev_one'] += 1
+        elif w[r] == 0:
+            assert row[r] == -1.0
+            seen['rev_zero'] += 1
+        else:
+            assert row[r] == np.float32(np.float64(w[r]) - 1.0)
+            seen['rev_other'] += 1
+        others = [j for j in in_of[b2a[b]] if j != r]
+        assert all((j in row) == (w[j] != 0) and (w[j] == 0 or row[j] == w[j]) for j in others)
+        order = [j for j in in_of[b2a[b]] if j in row]
+        assert msg.idx[e].tolist() == order  # slot order
+    assert min(seen.values()) >= 10, seen
+    # the 8 / 9 boundary, on the aggregate rows of the hubs (molecule: non-zero in-weights of atom 0) ...
+    hubs = {0: 8, 5: 8, 6: 9, 7: 9, 8: 10, 9: 10, 10: 13}
+    blocks = g.molecule_blocks()
+    assert blocks[:, 1].max() == 32 and blocks[:, 3].max() <= 32
+    assert (blocks[:, 5] - blocks[:, 4]).max() >= 3  # several molecules share a block
+    blk_a, blk_b = np.full(g.n_atoms, -1), np.full(g.n_bonds, -1)
+    for k, (bs, bn, as_, an) in enumerate(blocks[:, :4]):
+        blk_b[bs:bs + bn] = k
+        blk_a[as_:as_ + an] = k
+    bstart = np.append(blocks[:, 0], 0).astype(np.int64)
+    a_idx, a_coef = (x.reshape(-1, ELLW) for x in ell_rows(agg, agg.rows, bstart[blk_a]))
+    for m, nz in hubs.items():
+        hub = g.a_scope[m][0]
+        assert agg.ptr[hub + 1] - agg.ptr[hub] == nz
+        assert bool(a_idx[hub, ELLW - 1] & 0x80) == (nz > ELLW)
+        assert np.count_nonzero(a_coef[hub]) == min(nz, ELLW)
+    # ... and on every row of both lists; an ELL slot never names a zero-weight bond
+    m_idx, m_coef = (x.reshape(-1, ELLW) for x in ell_rows(msg, msg.rows, bstart[blk_b]))
+    counts = set()
+    for c, idx, coef, blk in ((agg, a_idx, a_coef, blk_a), (msg, m_idx, m_coef, blk_b)):
+        n = np.diff(c.ptr)
+        counts |= set(n.tolist())
+        assert np.array_equal((idx[:, ELLW - 1] & 0x80) != 0, n > ELLW)
+        assert np.array_equal(np.count_nonzero(coef, axis=1), np.minimum(n, ELLW))
+        for r in np.nonzero(n)[0]:
+            k = min(n[r], ELLW)
+            assert np.array_equal(bstart[blk[r]] + (idx[r, :k] & 0x7f), c.idx[c.ptr[r]:c.ptr[r] + k])
+            assert np.array_equal(coef[r, :k], c.coef[c.ptr[r]:c.ptr[r] + k])
+    assert {7, 8, 9, 10} <= counts
+    assert not np.isin(bstart[blk_a][:, None] + (a_idx & 0x7f), zero)[a_coef != 0].any()
+    host = np.zeros(1 << 20, np.uint8)
+    _, (_, _, _, n_blocks, nnz_msg, nnz_agg), _, _ = _packer().compact_stage(*g._compact, 133, 147, 64,
+                                                                             host.ctypes.data, host.nbytes)
+    assert (n_blocks, nnz_msg, nnz_agg) == (len(blocks), len(msg.idx), len(agg.idx))
 
 
 @pytest.mark.parametrize('name', golden_io.golden_names())

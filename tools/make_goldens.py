@@ -65,6 +65,9 @@ CASES = {
     'enc_polymer_b64_h300_t3': (('polymer', 64, 31), {}, 'encoder', True),
     # QM9 B = 64 at the benchmark width: its no-grad call runs the one-launch small-block forward
     'enc_qm9_b64_h300_t3': (('qm9', 64, 32), {}, 'encoder', False),
+    # zero and unit rule weights, hubs around the ELL width, a zero atom weight, Xn != 1 (synthetic.weight_case_batch):
+    # the oracle's treatment of those values is the reference's own; the no-grad call is the one-launch forward
+    'enc_weights_h300_t3': (('weights', 14, 33), dict(bias=True), 'encoder', True),
     'model_polymer_regression': (('polymer', 5, 23), dict(hidden_size=64, ffn_hidden_size=64), 'model', True),
     'model_two_mols_features_cls': (('polymer2', 4, 24), dict(hidden_size=32, ffn_hidden_size=16, ffn_num_layers=3,
                                                               number_of_molecules=2, use_input_features=True,
@@ -76,6 +79,8 @@ CASES = {
 def make_graphs(kind, b, seed):
     if kind == 'edge':
         return [synthetic.edge_case_batch(seed)]
+    if kind == 'weights':
+        return [synthetic.weight_case_batch(seed)]
     if kind == 'polymer2':
         return [synthetic.make_batch('polymer', b, seed), synthetic.make_batch('qm9', b, seed + 1000)]
     return [synthetic.make_batch(kind, b, seed)]
