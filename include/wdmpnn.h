@@ -400,6 +400,95 @@ typedef struct WdJoin {
 } WdJoin;
 int wdmpnn_join_rows(const WdJoin *j, void *stream);
 
+/* Atom descriptors from a device-resident table (--atom_descriptors descriptor; mpn.py:77-79, 136-143).
+ * `table` [table_rows][ld_table] holds the (already scaled) descriptor rows of a data split, d columns, the atoms
+ * of a molecule on consecutive rows; row0[b] (int64, like wdmpnn_join_rows' indices) is the first table row of
+ * batch molecule b.  atom_descriptors_layer is a Linear without an activation and the readout (mpn.py:145-171) is
+ * linear in the atom rows, so with encoder dropout inactive the layer may run after the readout, on B rows instead
+ * of n_atoms (c_a = Xn_b w_a / den_b; den_b = sum_a w_a for mean, 1 for sum, aggregation_norm for norm):
+ *     readout([h | desc] W_d^T + b_d) = [readout(h) | readout(desc)] W_d^T + s_b b_d,     s_b = sum_a c_a
+ * All four kernels: fp32 FMA, fixed thread-to-element maps, fixed summation orders (increasing index), no atomics,
+ * plain vector stores: bitwise repeatable.  None of them clamps an index: row0[b] + mol_size[b] <= table_rows is
+ * the caller's check (chemprop_amd.atom_descriptors validates every row on the host before it uploads row0).
+ *
+ * Join: one launch builds the layer's input x [B][ld_x], ld_x >= H + d + 1, from the descriptor-free encoder's
+ * output emb [B][ld_emb] (H columns) and the graph g's mol_start, mol_size, w_atoms and degree_of_polym (B =
+ * g->n_mols).  Per molecule b, atoms a = 0 .. mol_size[b] - 1 with weight w_a = w_atoms[mol_start[b] + a]:
+ *     x[b][0 .. H)  = emb[b][0 .. H)                                            a pure copy (every bit)
+ *     x[b][H + j]   = Xn_b * ((sum_a w_a table[row0[b] + a][j]) / den_b)        j < d, atoms in index order
+ *     x[b][H + d]   = Xn_b * ((sum_a w_a) / den_b)                              s_b
+ * The sum is formed first and divided afterwards, so a zero weight sum under mean gives the reference's NaN (a
+ * molecule without atoms too: the Python side refuses those).  Columns of x at and beyond H + d + 1 are not written.
+ * Refused before any launch: a NULL struct or graph, or emb, table, row0, x or one of the graph's four arrays NULL
+ * with B > 0 (WD_ERR_ARG); B < 0, H <= 0, d <= 0, table_rows < 0, ld_emb < H, ld_table < d, ld_x < H + d + 1, an
+ * unknown aggregation (WD_ERR_SHAPE); H + d > 4096 (WD_ERR_UNSUPPORTED).  B == 0 is a no-op. */
+#define WD_DESC_MAX_WIDTH 4096
+typedef struct WdDescJoin {
+    const struct WdGraph *g;              /* n_mols, mol_start, mol_size, w_atoms, degree_of_polym */
+    int32_t H, d;
+    const float *emb; int32_t ld_emb;     /* [B][ld_emb]                                  */
+    const float *table; int32_t ld_table; /* [table_rows][ld_table]                       */
+    int64_t table_rows;
+    const int64_t *row0;                  /* [B]                                          */
+    int32_t aggregation;                  /* WdAggregation                                */
+    float aggregation_norm;
+    float *x; int32_t ld_x;               /* [B][ld_x]                                    */
+} WdDescJoin;
+int wdmpnn_desc_join(const WdDescJoin *j, void *stream);
+
+/* Layer: y[b][i] = sum_{j < Hd} x[b][j] W_d[i][j] + x[b][Hd] b_d[i], i < Hd = H + d, in one launch of 16 x 16
+ * tiles over (B, Hd).  W_d is nn.Linear.weight [Hd][Hd] row-major, b_d [Hd] or NULL (no bias term).  Columns of y at
+ * and beyond Hd are not written.
+ * Refused before any launch: a NULL struct, or x, W_d or y NULL with B > 0 (WD_ERR_ARG); B < 0, Hd <= 0,
+ * ld_x < Hd + 1, ld_y < Hd (WD_ERR_SHAPE); Hd > WD_DESC_MAX_WIDTH, the heads' width limit (WD_ERR_UNSUPPORTED: the
+ * caller keeps the per-atom layer).  B == 0 is a no-op. */
+typedef struct WdDescLayer {
+    int32_t B, Hd;
+    const float *x; int32_t ld_x;         /* [B][ld_x]: Hd columns, then s                */
+    const float *W_d, *b_d;
+    float *y; int32_t ld_y;               /* [B][ld_y]                                    */
+} WdDescLayer;
+int wdmpnn_desc_layer(const WdDescLayer *l, void *stream);
+
+/* Its backward from dy [B][ld_dy] and the same x, every output in ONE launch (the head stack's "dz | dW | db"):
+ *     dW_d[i][j] = sum_b dy[b][i] x[b][j]              [Hd][Hd]
+ *     db_d[i]    = sum_b dy[b][i] x[b][Hd]             [Hd]
+ *     demb[b][h] = sum_i dy[b][i] W_d[i][h],  h < H    [B][ld_demb]: the encoder backward's input
+ * Each of the three may be NULL ("not wanted": its tiles take no workgroups; all NULL launches nothing); every
+ * wanted output is fully overwritten (no zeroing needed; with B == 0 nothing is written) and bitwise the same
+ * whatever else is wanted.  Columns of demb at and beyond H are not written.
+ * Refused before any launch: a NULL struct, or dy or x NULL with B > 0, or W_d NULL with B > 0 and demb wanted
+ * (WD_ERR_ARG); B < 0, H <= 0, Hd < H, ld_dy < Hd, ld_x < Hd + 1, ld_demb < H with demb (WD_ERR_SHAPE);
+ * Hd > WD_DESC_MAX_WIDTH (WD_ERR_UNSUPPORTED).  B == 0 is a no-op. */
+typedef struct WdDescLayerBackward {
+    int32_t B, H, Hd;
+    const float *dy; int32_t ld_dy;
+    const float *x; int32_t ld_x;
+    const float *W_d;
+    float *dW_d, *db_d;
+    float *demb; int32_t ld_demb;
+} WdDescLayerBackward;
+int wdmpnn_desc_layer_backward(const WdDescLayerBackward *l, void *stream);
+
+/* Rows: the padded per-atom array the per-atom descriptor path reads (WdGraph.atom_desc), for a training forward
+ * with active encoder dropout, where nothing commutes: atom_desc [rows][ld], rows >= n_atoms rounded up to 128 and
+ * ld >= d rounded up to 32 (the layout rule at the top of this header), from the same table in one launch:
+ *     atom_desc[mol_start[b] + a][j] = table[row0[b] + a][j]        a < mol_size[b], j < d: a pure copy
+ * and 0 everywhere else: row 0, rows outside every molecule, the rows at and beyond g->n_atoms, the columns at and
+ * beyond d.  EVERY element of the buffer is written.  mol_start must be non-decreasing, as a_scope is.
+ * Refused before any launch: a NULL struct or graph, or table, row0, atom_desc, mol_start or mol_size NULL with
+ * B > 0 (WD_ERR_ARG); B < 0, d <= 0, table_rows < 0, ld_table < d, rows < n_atoms rounded up to 128, ld < d
+ * rounded up to 32 (WD_ERR_SHAPE).  B == 0 is a no-op. */
+typedef struct WdDescRows {
+    const struct WdGraph *g;              /* n_mols, n_atoms, mol_start, mol_size          */
+    int32_t d;
+    const float *table; int32_t ld_table;
+    int64_t table_rows;
+    const int64_t *row0;                  /* [B]                                          */
+    float *atom_desc; int32_t rows, ld;
+} WdDescRows;
+int wdmpnn_desc_rows(const WdDescRows *r, void *stream);
+
 /* Ensembles (make_predictions.py:129-201): the per-cell mean and variance of the predictions of M models, and the
  * pairwise SID of an ensemble of spectra, accumulated on the device in double precision, which is what the
  * reference's numpy float64 sums of fp32 predictions are.  Both kernels are bandwidth-bound; no atomics, fixed

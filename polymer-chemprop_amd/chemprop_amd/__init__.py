@@ -6,6 +6,7 @@ Drop-in replacements for ``chemprop.models.mpn.MPNEncoder`` / ``MPN``,
 ``libwdmpnn.so`` (C-ABI: include/wdmpnn.h).
 """
 from .args import TrainArgs
+from .atom_descriptors import AtomDescriptorIndex, AtomDescriptorRows, AtomDescriptorTable
 from .evaluate import Evaluator, TargetTable, evaluate
 from .featurization import BatchMolGraph, get_atom_fdim, get_bond_fdim, mol2graph
 from .features import FeatureIndex, FeatureRows, FeatureTable
@@ -15,4 +16,5 @@ from .nn_utils import get_activation_function, index_select_ND, initialize_weigh
 
 __all__ = ['TrainArgs', 'BatchMolGraph', 'get_atom_fdim', 'get_bond_fdim', 'mol2graph', 'MoleculeModel', 'MPN',
            'MPNEncoder', 'get_activation_function', 'index_select_ND', 'initialize_weights', 'FeatureTable',
-           'FeatureIndex', 'FeatureRows', 'TargetTable', 'Evaluator', 'evaluate']
+           'FeatureIndex', 'FeatureRows', 'TargetTable', 'Evaluator', 'evaluate', 'AtomDescriptorTable',
+           'AtomDescriptorIndex', 'AtomDescriptorRows']

@@ -48,7 +48,8 @@ EXPORTED_SYMBOLS = ('wdmpnn_abi_version', 'wdmpnn_last_error', 'wdmpnn_workspace
                     'wdmpnn_head_stack_partial', 'wdmpnn_head_spectra_scratch_bytes', 'wdmpnn_head_spectra',
                     'wdmpnn_head_spectra_predict', 'wdmpnn_join_rows', 'wdmpnn_ensemble_add',
                     'wdmpnn_ensemble_sid', 'wdmpnn_eval_add', 'wdmpnn_eval_spectra', 'wdmpnn_eval_auc',
-                    'wdmpnn_head_stack_latent', 'wdmpnn_latent_add')
+                    'wdmpnn_head_stack_latent', 'wdmpnn_latent_add', 'wdmpnn_desc_join', 'wdmpnn_desc_layer',
+                    'wdmpnn_desc_layer_backward', 'wdmpnn_desc_rows')
 HEAD_MAX_LAYERS = 6  # WD_HEAD_MAX_LAYERS
 HEAD_MAX_SPECTRUM = 8192  # WD_HEAD_MAX_SPECTRUM
 SPECTRA_ACTIVATIONS = {'exp': 0, 'softplus': 1}  # WdHeadSpectra.spectra_act
@@ -58,6 +59,7 @@ ENSEMBLE_MAX_MODELS = 32  # WD_ENSEMBLE_MAX_MODELS
 EVAL_SLOTS = 4  # WD_EVAL_SLOTS
 EVAL_KINDS = {'regression': 0, 'classification': 1, 'multiclass': 2}  # WD_EVAL_*
 EVAL_AUC_MAX_ROWS = 1 << 24  # WD_EVAL_AUC_MAX_ROWS
+DESC_MAX_WIDTH = 4096  # WD_DESC_MAX_WIDTH
 
 
 class WdCsr(Structure):
@@ -230,6 +232,29 @@ class WdEvalAuc(Structure):
                 ('ld_targets', c_int32), ('preds_f32', c_int32), ('counts', c_void_p)]
 
 
+class WdDescJoin(Structure):
+    _fields_ = [('g', POINTER(WdGraph)), ('H', c_int32), ('d', c_int32), ('emb', c_void_p), ('ld_emb', c_int32),
+                ('table', c_void_p), ('ld_table', c_int32), ('table_rows', c_int64), ('row0', c_void_p),
+                ('aggregation', c_int32), ('aggregation_norm', c_float), ('x', c_void_p), ('ld_x', c_int32)]
+
+
+class WdDescLayer(Structure):
+    _fields_ = [('B', c_int32), ('Hd', c_int32), ('x', c_void_p), ('ld_x', c_int32), ('W_d', c_void_p),
+                ('b_d', c_void_p), ('y', c_void_p), ('ld_y', c_int32)]
+
+
+class WdDescLayerBackward(Structure):
+    _fields_ = [('B', c_int32), ('H', c_int32), ('Hd', c_int32), ('dy', c_void_p), ('ld_dy', c_int32),
+                ('x', c_void_p), ('ld_x', c_int32), ('W_d', c_void_p), ('dW_d', c_void_p), ('db_d', c_void_p),
+                ('demb', c_void_p), ('ld_demb', c_int32)]
+
+
+class WdDescRows(Structure):
+    _fields_ = [('g', POINTER(WdGraph)), ('d', c_int32), ('table', c_void_p), ('ld_table', c_int32),
+                ('table_rows', c_int64), ('row0', c_void_p), ('atom_desc', c_void_p), ('rows', c_int32),
+                ('ld', c_int32)]
+
+
 def join_rows(out, segments, stream: int) -> None:
     """wdmpnn_join_rows into ``out`` (float32 device tensor ``[B][ld_out]``, row-major): ``segments`` are
     ``(src data pointer, ld, c0, w, index data pointer or 0)``.  Every index must have been range-checked by the
@@ -317,6 +342,10 @@ def lib() -> ctypes.CDLL:
     L.wdmpnn_ensemble_sid.argtypes = [POINTER(WdEnsembleSid), c_void_p]
     L.wdmpnn_head_stack_latent.argtypes = [POINTER(WdHeadLatent), c_void_p]
     L.wdmpnn_latent_add.argtypes = [POINTER(WdLatentAdd), c_void_p]
+    L.wdmpnn_desc_join.argtypes = [POINTER(WdDescJoin), c_void_p]
+    L.wdmpnn_desc_layer.argtypes = [POINTER(WdDescLayer), c_void_p]
+    L.wdmpnn_desc_layer_backward.argtypes = [POINTER(WdDescLayerBackward), c_void_p]
+    L.wdmpnn_desc_rows.argtypes = [POINTER(WdDescRows), c_void_p]
     L.wdmpnn_eval_add.argtypes = [POINTER(WdEvalAdd), c_void_p]
     L.wdmpnn_eval_spectra.argtypes = [POINTER(WdEvalSpectra), c_void_p]
     L.wdmpnn_eval_auc.argtypes = [POINTER(WdEvalAuc), c_void_p]
@@ -350,7 +379,8 @@ def lib() -> ctypes.CDLL:
              'wdmpnn_head_stack_partial', 'wdmpnn_head_spectra_scratch_bytes', 'wdmpnn_head_spectra',
              'wdmpnn_head_spectra_predict', 'wdmpnn_join_rows', 'wdmpnn_ensemble_add', 'wdmpnn_ensemble_sid',
              'wdmpnn_eval_add', 'wdmpnn_eval_spectra', 'wdmpnn_eval_auc', 'wdmpnn_head_stack_latent',
-             'wdmpnn_latent_add'):
+             'wdmpnn_latent_add', 'wdmpnn_desc_join', 'wdmpnn_desc_layer', 'wdmpnn_desc_layer_backward',
+             'wdmpnn_desc_rows'):
         getattr(L, fn).restype = c_int
     v = L.wdmpnn_abi_version()
     if v != ABI_VERSION:

@@ -23,6 +23,8 @@ class TrainArgs:
     aggregation_norm: int = 100          # args.py:358
     atom_descriptors: Optional[str] = None
     atom_descriptors_size: int = 0
+    atom_descriptors_path: Optional[str] = None      # args.py:99 (the .npz of per-molecule descriptor arrays)
+    no_atom_descriptor_scaling: bool = False         # args.py:236
     device: torch.device = field(default_factory=lambda: torch.device('cuda' if torch.cuda.is_available() else 'cpu'))
     # MPN (mpn.py:189-208)
     features_only: bool = False

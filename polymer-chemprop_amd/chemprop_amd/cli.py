@@ -92,6 +92,7 @@ from .model import MoleculeModel
 from .nn_utils import initialize_weights
 from .polymer import split_polymer_string, parse_polymer_rules
 from .spectra_utils import load_phase_mask, normalize_spectra, phase_row_mask, sid_metric, wasserstein_metric
+from .atom_descriptors import AtomDescriptorTable
 from .predict import LATENT_TYPES, device_predictions
 from .train import NoamLR, _predict_head, build_optimizer, frozen_encodings, get_loss_func, train_step
 
@@ -139,12 +140,14 @@ def _plain(v):
 
 
 def save_checkpoint(path: str, model, scaler: Optional[StandardScaler] = None,
-                    features_scaler: Optional[StandardScaler] = None, args=None) -> None:
+                    features_scaler: Optional[StandardScaler] = None, args=None,
+                    atom_descriptor_scaler: Optional[StandardScaler] = None) -> None:
     """utils.py:47-73: {'args', 'state_dict', 'data_scaler', 'features_scaler', 'atom_descriptor_scaler',
     'bond_feature_scaler'}; every value a plain type (weights_only-loadable)."""
     a = {} if args is None else {k: _plain(v) for k, v in (vars(args) if not isinstance(args, dict) else args).items()}
     torch.save({'args': a, 'state_dict': model.state_dict(), 'data_scaler': _scaler_to_dict(scaler),
-                'features_scaler': _scaler_to_dict(features_scaler), 'atom_descriptor_scaler': None,
+                'features_scaler': _scaler_to_dict(features_scaler),
+                'atom_descriptor_scaler': _scaler_to_dict(atom_descriptor_scaler),
                 'bond_feature_scaler': None}, path)
 
 
@@ -315,7 +318,8 @@ def evaluate_predictions(preds, targets, num_tasks: int, metrics: List[str], dat
 
 
 def predict(model, graphs, idx, batch_size: int, scaler: Optional[StandardScaler],
-            encodings: Optional[torch.Tensor] = None, features=None, spectra_mask=None) -> List[List[float]]:
+            encodings: Optional[torch.Tensor] = None, features=None, spectra_mask=None,
+            atom_descriptors=None) -> List[List[float]]:
     """predict.py:10-68: eval, no_grad, batches in order, inverse scaling: the batches of
     ``predict.device_predictions`` copied to the host.  ``encodings``: the rows of ``idx`` from ``frozen_encodings``
     (a frozen encoder's outputs, computed once per run): the native prediction head on them in place of the
@@ -324,6 +328,8 @@ def predict(model, graphs, idx, batch_size: int, scaler: Optional[StandardScaler
     own ``features.FeatureTable`` (row k = ``idx[k]``'s features).  A spectra model's predictions are normalised
     per row on the device (make_predictions.py:175-181): ``spectra_mask`` is the bool ``[len(idx)][T]`` array of
     the positions each row's phase includes (None: all), uploaded once; excluded positions come back as None.
+    ``atom_descriptors``: the split's ``AtomDescriptorTable`` (molecule k = ``idx[k]``'s rows, already scaled), or
+    the scaled arrays of the whole data set (a list indexed by ``idx``), for a descriptor model.
     The ``BatchMolGraph`` s of the whole split are held at once."""
     model.eval()
     if not len(idx):
@@ -334,12 +340,14 @@ def predict(model, graphs, idx, batch_size: int, scaler: Optional[StandardScaler
         features = FeatureTable(np.stack([features[i] for i in idx]), device)
     if features is not None and len(features) != len(idx):
         raise ValueError(f'a feature table of {len(features)} rows for {len(idx)} molecules')
-    native = spectra or encodings is not None
-    if native and _predict_head(model) is None:
+    if atom_descriptors is not None and not isinstance(atom_descriptors, AtomDescriptorTable):
+        atom_descriptors = AtomDescriptorTable([atom_descriptors[i] for i in idx], device)
+    native = spectra or encodings is not None or atom_descriptors is not None
+    if native and _predict_head(model) is None and atom_descriptors is None:
         raise NotImplementedError('predict: the model\'s FFN is not one the native prediction heads run')
     batches = batch_size if encodings is not None else make_batches([graphs[i] for i in idx], batch_size)
     outs = device_predictions(model, batches, features, device_mask(spectra_mask, device) if spectra else None,
-                              encodings, own_forward=not native, n_rows=len(idx))
+                              encodings, own_forward=not native, n_rows=len(idx), atom_descriptors=atom_descriptors)
     preds = torch.cat([out for _, out in outs]).cpu().numpy().tolist()
     if spectra:
         preds = [[None if math.isnan(v) else v for v in row] for row in preds]
@@ -436,6 +444,75 @@ def scale_features(features: np.ndarray, train_idx: List[int], no_features_scali
     return sc.transform(features), sc
 
 
+def check_atom_descriptor_args(mode: Optional[str], path: Optional[str]) -> None:
+    """args.py:97-103, 596-607 for what this package reads: ``--atom_descriptors descriptor`` with an ``.npz``
+    file.  ``ValueError`` with the reason for everything else."""
+    if mode is None and path is None:
+        return
+    if mode is None:
+        raise ValueError('--atom_descriptors_path is given without --atom_descriptors: say how the descriptors are '
+                         'used (--atom_descriptors descriptor)')
+    if mode == 'feature':
+        raise ValueError('--atom_descriptors feature is not supported: such descriptors become columns of the atom '
+                         'features when a molecule is featurised, and this tool reads graphs that are featurised '
+                         'already (--graphs_path); featurise with them, or use --atom_descriptors descriptor')
+    if mode != 'descriptor':
+        raise ValueError(f'--atom_descriptors {mode}: "descriptor" is the supported mode')
+    if path is None:
+        raise ValueError('--atom_descriptors descriptor needs --atom_descriptors_path')
+    check_atom_descriptors_path(path)
+
+
+def check_atom_descriptors_path(path: str) -> None:
+    ext = os.path.splitext(path)[1].lower()
+    if ext in ('.pkl', '.pckl', '.pickle'):
+        raise ValueError(f'{path}: pickled descriptor tables are read with pandas, which this package does not '
+                         'depend on; save the arrays with numpy.savez, one array per molecule in data order')
+    if ext == '.sdf':
+        raise ValueError(f'{path}: descriptors in an .sdf file are read with RDKit, which this package does not '
+                         'depend on; save the arrays with numpy.savez, one array per molecule in data order')
+    if ext != '.npz':
+        raise ValueError(f'{path}: atom descriptors are read from an .npz file (numpy.savez: one [n_atoms][d] array '
+                         'per molecule, in data order)')
+
+
+def load_atom_descriptors(path: str, graphs) -> List[np.ndarray]:
+    """``--atom_descriptors_path`` (features/utils.py:76-78, data/utils.py:310-339): the arrays of an ``.npz`` file
+    in file order, one float64 ``[n_atoms][d]`` array per graph, NaN replaced by 0 (data.py:133-135).
+    ``ValueError`` naming the first offender: another number of arrays than graphs, an array that is not 2-D, of
+    another width than the first, or with another number of rows than its graph has atoms."""
+    check_atom_descriptors_path(path)
+    with np.load(path, allow_pickle=False) as container:
+        arrays = [np.asarray(container[key]) for key in container]
+    if len(arrays) != len(graphs):
+        raise ValueError(f'{path} holds {len(arrays)} descriptor arrays for {len(graphs)} molecules')
+    out = []
+    for k, (a, g) in enumerate(zip(arrays, graphs)):
+        if a.ndim != 2 or a.shape[1] < 1 or a.dtype.kind not in 'fiu':
+            raise ValueError(f'{path}: array {k} has shape {a.shape} ({a.dtype}); a numeric [n_atoms][d] array is '
+                             'expected')
+        if a.shape[1] != arrays[0].shape[1]:
+            raise ValueError(f'{path}: array {k} has {a.shape[1]} descriptors per atom, array 0 has '
+                             f'{arrays[0].shape[1]}')
+        if a.shape[0] != g.n_atoms:
+            raise ValueError(f'{path}: array {k} has {a.shape[0]} rows, molecule {k} has {g.n_atoms} atoms (the '
+                             'number of atoms is different from the length of the extra atom features)')
+        a = a.astype(np.float64)
+        out.append(np.where(np.isnan(a), 0.0, a))
+    return out
+
+
+def scale_atom_descriptors(descriptors: List[np.ndarray], train_idx: List[int],
+                           no_atom_descriptor_scaling: bool = False):
+    """data.py:432-478 with run_training.py:118-123: ``(every molecule's descriptors as the model sees them, the
+    scaler or None)``.  Unless ``no_atom_descriptor_scaling``, a ``StandardScaler(replace_nan_token=0)`` is fitted on
+    the stacked rows of the training molecules and applied to every molecule."""
+    if no_atom_descriptor_scaling:
+        return list(descriptors), None
+    sc = StandardScaler(replace_nan_token=0).fit(np.vstack([descriptors[i] for i in train_idx]))
+    return [sc.transform(a) for a in descriptors], sc
+
+
 METRICS_OF = {'spectra': ('sid', 'wasserstein')}  # (args.py:568-573, for the metrics only spectra has)
 
 
@@ -474,6 +551,13 @@ def parse_args(argv=None, spectra: bool = False) -> argparse.Namespace:
     ap.add_argument('--no_features_scaling', action='store_true',
                     help='feed the features of --features_path as they are (default: standardised on the training '
                          'split, NaN -> 0)')
+    ap.add_argument('--atom_descriptors', default=None, choices=['feature', 'descriptor'],
+                    help='descriptor: per-atom descriptors joined to the atom hidden states before the readout '
+                         '(feature is refused: it belongs to featurisation)')
+    ap.add_argument('--atom_descriptors_path', default=None,
+                    help='.npz file: one [n_atoms][d] array per data row, in data order')
+    ap.add_argument('--no_atom_descriptor_scaling', action='store_true',
+                    help='feed the atom descriptors as they are (default: standardised on the training split)')
     ap.add_argument('--save_dir', required=True)
     ap.add_argument('--polymer', action='store_true')
     ap.add_argument('--split_type', default='random', choices=['random'])
@@ -525,6 +609,7 @@ def parse_args(argv=None, spectra: bool = False) -> argparse.Namespace:
     if a.dataset_type == 'spectra' and not a.spectra_target_floor > 0:
         raise ValueError('--spectra_target_floor must be greater than 0')
     check_metrics(a.dataset_type, ([a.metric] if a.metric else []) + list(a.extra_metrics))
+    check_atom_descriptor_args(a.atom_descriptors, a.atom_descriptors_path)
     return a
 
 
@@ -573,6 +658,13 @@ def run_training(a: argparse.Namespace) -> Dict[str, list]:
                                                    a.no_features_scaling)
     if phase_features is not None:
         features = phase_features if features is None else np.concatenate([features, phase_features], axis=1)
+    # --atom_descriptors descriptor: every molecule's [n_atoms][d] rows, standardised on the training split's
+    # stacked rows (run_training.py:118-123)
+    descriptors = atom_descriptor_scaler = None
+    if getattr(a, 'atom_descriptors', None) is not None:
+        check_atom_descriptor_args(a.atom_descriptors, a.atom_descriptors_path)
+        descriptors, atom_descriptor_scaler = scale_atom_descriptors(
+            load_atom_descriptors(a.atom_descriptors_path, graphs), train_idx, a.no_atom_descriptor_scaling)
     args = TrainArgs(hidden_size=a.hidden_size, depth=a.depth, dropout=a.dropout, activation=a.activation,
                      aggregation=a.aggregation, aggregation_norm=a.aggregation_norm, bias=a.bias,
                      undirected=a.undirected, ffn_num_layers=a.ffn_num_layers,
@@ -587,6 +679,10 @@ def run_training(a: argparse.Namespace) -> Dict[str, list]:
                      no_features_scaling=bool(a.no_features_scaling),
                      use_input_features=features is not None,
                      features_size=0 if features is None else int(features.shape[1]),
+                     atom_descriptors=None if descriptors is None else 'descriptor',
+                     atom_descriptors_size=0 if descriptors is None else int(descriptors[0].shape[1]),
+                     atom_descriptors_path=None if descriptors is None else a.atom_descriptors_path,
+                     no_atom_descriptor_scaling=bool(getattr(a, 'no_atom_descriptor_scaling', False)),
                      polymer=bool(a.polymer), ensemble_size=a.ensemble_size, task_names=list(header[1:]),
                      device_metrics=bool(getattr(a, 'device_metrics', False)))
     torch.manual_seed(a.pytorch_seed)
@@ -604,14 +700,21 @@ def run_training(a: argparse.Namespace) -> Dict[str, list]:
     splits = (('train', train_idx), ('val', val_idx), ('test', test_idx))
     tables = None if features is None else {name: FeatureTable(features[idx], device) if len(idx) else None
                                             for name, idx in splits}
+    # and one resident atom descriptor table per split: a batch is a slice of an index of its molecules
+    desc_tables = None if descriptors is None else {
+        name: AtomDescriptorTable([descriptors[i] for i in idx], device) if len(idx) else None for name, idx in splits}
     loss_func = get_loss_func(a.dataset_type, a.alternative_loss_function)
+
+    def save(path, model):
+        save_checkpoint(path, model, scaler, features_scaler, args, atom_descriptor_scaler)
 
     def batch_targets(pos):
         return train_targets[pos] if spectra else [train_targets[p] for p in pos]
 
     def run_predict(model, enc_cache, name, idx):
         return predict(model, graphs, idx, a.batch_size, scaler, enc_cache and enc_cache[name],
-                       tables and tables[name], None if row_mask is None else row_mask[idx])
+                       tables and tables[name], None if row_mask is None else row_mask[idx],
+                       atom_descriptors=desc_tables and desc_tables[name])
     # --device_metrics: every split's target table and phase mask go to the device once per run, its
     # BatchMolGraphs are built once (on first use: a run on cached encodings never needs them), and a split is
     # scored by evaluate.evaluate without a host copy per batch
@@ -634,7 +737,8 @@ def run_training(a: argparse.Namespace) -> Dict[str, list]:
                 split_batches[name] = make_batches([graphs[i] for i in split_idx[name]], a.batch_size)
             batches = split_batches[name]
         return evaluate(model, batches, table, metrics, scaler, tables and tables[name], split_masks[name],
-                        enc_cache and enc_cache[name], evaluator=ev), ev
+                        enc_cache and enc_cache[name], evaluator=ev,
+                        atom_descriptors=desc_tables and desc_tables[name]), ev
     sampler = Random(a.seed)  # (one stream of shuffles for the run: an ensemble's later models continue it)
 
     def train_model(save_dir):
@@ -650,7 +754,7 @@ def run_training(a: argparse.Namespace) -> Dict[str, list]:
         # a frozen encoder without dropout gives every molecule the same encoding at every step: computed once
         # per split, the steps and the per-epoch scores then run the head alone (train.frozen_encodings)
         enc_cache = None
-        if args.frzn_encoder and a.dropout == 0 and not a.no_encoding_cache and \
+        if args.frzn_encoder and a.dropout == 0 and not a.no_encoding_cache and descriptors is None and \
                 _predict_head(model.eval()) is not None:
             enc_cache = {name: frozen_encodings(model, [graphs[i] for i in idx], a.batch_size)
                          for name, idx in splits}
@@ -670,6 +774,7 @@ def run_training(a: argparse.Namespace) -> Dict[str, list]:
                 losses = []
                 # the epoch's order as one validated index upload; every step takes a slice of it
                 findex = tables['train'].index(order) if tables is not None and order else None
+                dindex = desc_tables['train'].index(order) if desc_tables is not None and order else None
                 for s in range(0, len(order), a.batch_size):
                     pos = order[s:s + a.batch_size]
                     feats = None if findex is None else findex[s:s + a.batch_size]
@@ -681,7 +786,9 @@ def run_training(a: argparse.Namespace) -> Dict[str, list]:
                     else:
                         g = BatchMolGraph([graphs[train_idx[p]] for p in pos])
                         loss = train_step(model, [g], batch_targets(pos), loss_func, optimizer, scheduler,
-                                          a.dataset_type, features_batch=feats, grad_clip=a.grad_clip)
+                                          a.dataset_type, features_batch=feats, grad_clip=a.grad_clip,
+                                          atom_descriptors_batch=None if dindex is None else
+                                          dindex[s:s + a.batch_size])
                     losses.append(float(loss))
                 if device_metrics:
                     val_scores = score_on_device(model, enc_cache, 'val')[0]
@@ -696,11 +803,11 @@ def run_training(a: argparse.Namespace) -> Dict[str, list]:
                 w.writerow([epoch, float(np.mean(losses)) if losses else float('nan')] +
                            [float(np.nanmean(tr_scores[m])) if tr_scores[m] else float('nan') for m in metrics] +
                            [float(np.nanmean(val_scores[m])) if val_scores[m] else float('nan') for m in metrics])
-                save_checkpoint(os.path.join(save_dir, 'model.pt'), model, scaler, features_scaler, args)
+                save(os.path.join(save_dir, 'model.pt'), model)
                 v = float(np.nanmean(val_scores[metric])) if val_scores[metric] else float('nan')
                 if (minimize and v < best) or (not minimize and v > best) or (epoch == 0 and math.isnan(v)):
                     best, best_epoch = v, epoch
-                    save_checkpoint(os.path.join(save_dir, 'best_model.pt'), model, scaler, features_scaler, args)
+                    save(os.path.join(save_dir, 'best_model.pt'), model)
         ckpt = torch.load(os.path.join(save_dir, 'best_model.pt'), map_location=device, weights_only=True)
         model.load_state_dict(ckpt['state_dict'])
         return model, enc_cache, best_epoch
@@ -729,7 +836,8 @@ def run_training(a: argparse.Namespace) -> Dict[str, list]:
             model, _, epoch = train_model(model_dir)
             best_epoch.append(epoch)
             if len(test_idx):
-                accumulate_model(acc, k, model, test_batches, scaler, tables and tables['test'], test_mask)
+                accumulate_model(acc, k, model, test_batches, scaler, tables and tables['test'], test_mask,
+                                 atom_descriptors=desc_tables and desc_tables['test'])
             del model
         each = acc.individual().cpu().numpy() if len(test_idx) else np.zeros((a.ensemble_size, 0, width))
         mean = acc.mean().cpu().numpy() if len(test_idx) else np.zeros((0, width))
@@ -794,6 +902,9 @@ def _prediction_parser(prog: str, description: str) -> argparse.ArgumentParser:
     ap.add_argument('--phase_features_path', default=None)
     ap.add_argument('--no_features_scaling', action='store_true',
                     help='feed the features as they are instead of through each checkpoint\'s features scaler')
+    ap.add_argument('--atom_descriptors_path', default=None,
+                    help='.npz file of the atom descriptors the models were trained with (one [n_atoms][d] array '
+                         'per CSV row); the mode, the width and the scaler come from each checkpoint')
     ap.add_argument('--batch_size', type=int, default=50)
     ap.add_argument('--gpu', type=int, default=0)
     return ap
@@ -805,6 +916,8 @@ def _check_prediction_args(a: argparse.Namespace) -> argparse.Namespace:
         raise ValueError('give exactly one of --checkpoint_dir, --checkpoint_path and --checkpoint_paths')
     if a.batch_size < 1:
         raise ValueError('--batch_size must be at least 1')
+    if a.atom_descriptors_path is not None:
+        check_atom_descriptors_path(a.atom_descriptors_path)
     return a
 
 
@@ -953,6 +1066,28 @@ def check_polymer_rows(smiles: List[str], graphs) -> None:
                 raise ValueError(f'graph degree_of_polym {g.degree_of_polym} != 1 + log10(Xn) = {deg} for {s}')
 
 
+def _prediction_descriptors(a: argparse.Namespace, paths: List[str], graphs):
+    """The raw atom descriptors of a prediction run, or None: ``--atom_descriptors_path`` must be given exactly
+    when the checkpoints were trained with ``--atom_descriptors descriptor`` (their stored args say)."""
+    state = torch.load(paths[0], map_location='cpu', weights_only=True)
+    mode = state['args'].get('atom_descriptors')
+    path = getattr(a, 'atom_descriptors_path', None)
+    if mode is None:
+        if path is not None:
+            raise ValueError(f'{paths[0]} was trained without atom descriptors, but --atom_descriptors_path is given')
+        return None
+    if path is None:
+        raise ValueError(f'{paths[0]} was trained with --atom_descriptors {mode}: give --atom_descriptors_path')
+    return load_atom_descriptors(path, graphs)
+
+
+def _descriptor_scaling_of(paths: List[str]) -> bool:
+    """Whether the run's checkpoints scale their atom descriptors (the first one's stored flag, as
+    make_predictions.py:143-153 reads ``train_args.atom_descriptor_scaling``)."""
+    state = torch.load(paths[0], map_location='cpu', weights_only=True)
+    return not bool(state['args'].get('no_atom_descriptor_scaling', False))
+
+
 def make_predictions(a: argparse.Namespace):
     """make_predictions.py:272-372 for this package's checkpoints: the ensemble's predictions of ``--test_path``
     written to ``--preds_path``; returns the mean predictions ``[N][W]`` (float64)."""
@@ -980,7 +1115,9 @@ def make_predictions(a: argparse.Namespace):
     mean, spread, individual, *embeddings = predict_ensemble(
         paths, graphs, a.batch_size, features=features, phase_features=phase_features, phase_mask=phase_mask,
         variance=a.ensemble_variance, individual=a.individual_ensemble_predictions,
-        device=torch.device('cuda', a.gpu), features_scaling=not a.no_features_scaling, embeddings=save_embeddings)
+        device=torch.device('cuda', a.gpu), features_scaling=not a.no_features_scaling, embeddings=save_embeddings,
+        atom_descriptors=_prediction_descriptors(a, paths, graphs),
+        atom_descriptor_scaling=_descriptor_scaling_of(paths))
     if save_embeddings:  # (make_predictions.py:191-195: averaged across the ensemble, next to the predictions)
         parent = os.path.dirname(a.graph_embeddings_path)
         if parent:
@@ -1038,7 +1175,9 @@ def make_fingerprints(a: argparse.Namespace) -> np.ndarray:
         phase_features = load_phase_features(a.phase_features_path, len(rows))
     fp = molecule_fingerprint(paths, graphs, a.batch_size, a.fingerprint_type, features=features,
                               phase_features=phase_features, features_scaling=not a.no_features_scaling,
-                              device=torch.device('cuda', a.gpu))
+                              device=torch.device('cuda', a.gpu),
+                              atom_descriptors=_prediction_descriptors(a, paths, graphs),
+                              atom_descriptor_scaling=_descriptor_scaling_of(paths))
     write_fingerprints(a.preds_path, header[0], [r[0] for r in rows], fp)
     return fp
 

@@ -125,17 +125,19 @@ def make_batches(graphs: Sequence, batch_size: int) -> list:
 
 def accumulate_model(acc: PredictionSink, k: int, model, batches, scaler=None, table: Optional[FeatureTable] = None,
                      row_mask: Optional[torch.Tensor] = None, encodings: Optional[torch.Tensor] = None,
-                     embeddings: Optional[PredictionSink] = None) -> None:
+                     embeddings: Optional[PredictionSink] = None, atom_descriptors=None) -> None:
     """Model ``k``'s predictions of ``batches`` into ``acc``, an ``EnsembleAccumulator`` or an ``Evaluator``: every
     batch of ``predict.device_predictions`` (which explains the other arguments) through ``acc.add``.
     ``embeddings``: a ``fingerprint.LatentAccumulator`` that takes, in the same pass, the FFN input of every batch
-    (``with_encodings``).  No host sync."""
+    (``with_encodings``).  ``atom_descriptors``: the rows' ``AtomDescriptorTable`` for a descriptor model.  No host
+    sync."""
     if embeddings is None:
-        for r0, out in device_predictions(model, batches, table, row_mask, encodings, n_rows=acc.n_rows):
+        for r0, out in device_predictions(model, batches, table, row_mask, encodings, n_rows=acc.n_rows,
+                                          atom_descriptors=atom_descriptors):
             acc.add(out, r0, k, scaler)
         return
     for r0, out, x in device_predictions(model, batches, table, row_mask, encodings, n_rows=acc.n_rows,
-                                         with_encodings=True):
+                                         with_encodings=True, atom_descriptors=atom_descriptors):
         acc.add(out, r0, k, scaler)
         embeddings.add(x, r0, k)
 
@@ -149,9 +151,38 @@ def _open_model(item, device):
         scalers = cli.load_scalers(path)
         return cli.load_checkpoint(path, device), scalers[0], scalers[1]
     if isinstance(item, (tuple, list)):
-        model, data_scaler, features_scaler = item
+        model, data_scaler, features_scaler = item[:3]  # (a fourth entry: the atom descriptor scaler)
         return model, data_scaler, features_scaler
     return item, None, None
+
+
+def model_atom_descriptors(item, model, atom_descriptors, device, scaling: bool = True, k: int = 0):
+    """The ``AtomDescriptorTable`` of the rows as model ``k`` sees them (make_predictions.py:143-153): the raw
+    per-molecule arrays ``atom_descriptors`` through that model's own ``atom_descriptor_scaler`` -- the one stored in
+    its checkpoint when ``item`` is a path, ``item[3]`` of a ``(model, data scaler, features scaler, atom descriptor
+    scaler)`` tuple, none for a model alone or with ``scaling=False``.  NaN becomes 0 (data.py:133-135).
+    ``ValueError`` when the model needs descriptors and gets none, gets descriptors it does not take, or another
+    width than it was trained on."""
+    from .atom_descriptors import AtomDescriptorTable
+    needs = getattr(model.encoder, 'atom_descriptors', None) == 'descriptor'
+    if atom_descriptors is None:
+        if needs:
+            raise ValueError(f'model {k} was trained with atom descriptors: give --atom_descriptors_path to predict')
+        return None
+    if not needs:
+        raise ValueError(f'model {k} was trained without atom descriptors, but atom descriptors were given')
+    scaler = None
+    if scaling:
+        if isinstance(item, (str, bytes)) or hasattr(item, '__fspath__'):
+            from . import cli
+            scaler = cli.load_scalers(str(item))[2]
+        elif isinstance(item, (tuple, list)) and len(item) > 3:
+            scaler = item[3]
+    arrays = [np.where(np.isnan(a), 0.0, a) for a in (np.asarray(a, dtype=np.float64) for a in atom_descriptors)]
+    width = model.encoder.encoder[0].atom_descriptors_size
+    if arrays and arrays[0].ndim == 2 and arrays[0].shape[1] != width:
+        raise ValueError(f'model {k} was trained with {width} descriptors per atom and {arrays[0].shape[1]} were given')
+    return AtomDescriptorTable(arrays, device, scaler)
 
 
 def model_features(model, features, features_scaler, phase_features, k: int = 0) -> Optional[np.ndarray]:
@@ -174,7 +205,8 @@ def model_features(model, features, features_scaler, phase_features, k: int = 0)
         raise ValueError(f'model {k} was trained without input features, but features were given')
     rows = np.concatenate(parts, axis=1)
     lin = next(m for m in model.ffn if isinstance(m, torch.nn.Linear))
-    width = lin.in_features - sum(e.hidden_size for e in getattr(model.encoder, 'encoder', ()))
+    width = lin.in_features - sum(e.hidden_size + getattr(e, 'atom_descriptors_size', 0)
+                                  for e in getattr(model.encoder, 'encoder', ()))
     if rows.shape[1] != width:
         raise ValueError(f'model {k} was trained with {width} input features and {rows.shape[1]} were given')
     return rows
@@ -182,7 +214,8 @@ def model_features(model, features, features_scaler, phase_features, k: int = 0)
 
 def predict_ensemble(checkpoints_or_models, graphs: Sequence, batch_size: int, features=None, phase_features=None,
                      phase_mask=None, variance: bool = False, individual: bool = False, device=None,
-                     n_models: Optional[int] = None, features_scaling: bool = True, embeddings: bool = False):
+                     n_models: Optional[int] = None, features_scaling: bool = True, embeddings: bool = False,
+                     atom_descriptors=None, atom_descriptor_scaling: bool = True):
     """The ensemble's predictions of ``graphs`` (``MolGraph`` records, one per row): ``(mean, variance,
     individual)`` as float64 numpy arrays, ``[N][W]``, ``[N][W]`` (for spectra models the per-row pairwise SID
     ``[N]``; None without ``variance``) and ``[M][N][W]`` (None without ``individual``).  W is the flat output width:
@@ -198,7 +231,11 @@ def predict_ensemble(checkpoints_or_models, graphs: Sequence, batch_size: int, f
     ``embeddings``: return a fourth value as well, the ensemble-mean graph embeddings (make_predictions.py:156-195
     with ``--save_graph_embeddings``): float32 ``[N][F]``, the fp32 sum over the models, in order, of the FFN input
     of every row (the encoding, features joined), divided by the model count; gathered in the same pass as the
-    predictions (``n_models`` is then needed with a generator of models)."""
+    predictions (``n_models`` is then needed with a generator of models).
+
+    ``atom_descriptors``: one raw ``[n_atoms][d]`` array per row for models trained with ``--atom_descriptors
+    descriptor``; every model builds its own device table with its own ``atom_descriptor_scaler``
+    (``model_atom_descriptors``; ``atom_descriptor_scaling=False``: as they are)."""
     device = torch.device('cuda', 0) if device is None else torch.device(device)
     if n_models is None and hasattr(checkpoints_or_models, '__len__'):
         n_models = len(checkpoints_or_models)
@@ -238,8 +275,10 @@ def predict_ensemble(checkpoints_or_models, graphs: Sequence, batch_size: int, f
                              f'ensemble\'s first model {"spectra" if spectra else "values"} of width {acc.width}')
         rows = model_features(model, features, features_scaler if features_scaling else None, phase_features, k)
         table = None if rows is None else FeatureTable(rows, device)
-        accumulate_model(acc, k, model, batches, data_scaler, table, row_mask, embeddings=emb_acc)
-        del model, table
+        desc = model_atom_descriptors(item, model, atom_descriptors, device, atom_descriptor_scaling, k)
+        accumulate_model(acc, k, model, batches, data_scaler, table, row_mask, embeddings=emb_acc,
+                         atom_descriptors=desc)
+        del model, table, desc
     if acc is None:
         raise ValueError('predict_ensemble: no model given')
     if n == 0:

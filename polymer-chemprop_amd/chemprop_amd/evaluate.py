@@ -272,16 +272,19 @@ class Evaluator(PredictionSink):
 
 def evaluate(model, batches, table: TargetTable, metrics: Sequence[str], scaler=None,
              features: Optional[FeatureTable] = None, row_mask: Optional[torch.Tensor] = None,
-             encodings: Optional[torch.Tensor] = None, evaluator: Optional[Evaluator] = None) -> Dict[str, list]:
+             encodings: Optional[torch.Tensor] = None, evaluator: Optional[Evaluator] = None,
+             atom_descriptors=None) -> Dict[str, list]:
     """The scores of ``model`` on one split: its ``BatchMolGraph`` s ``batches`` (row order = batch order), the split's
     ``features`` table, a spectra model's ``row_mask`` and the split's cached ``encodings`` (``batches`` may then be
     a plain batch size) go through ``ensemble.accumulate_model`` into an ``Evaluator``, as
     ``predict.device_predictions`` describes them; no host sync before ``scores()``.  ``evaluator``: fill this one
-    (made by the caller, say with ``keep=True`` to read ``predictions()`` afterwards) instead of a fresh one."""
+    (made by the caller, say with ``keep=True`` to read ``predictions()`` afterwards) instead of a fresh one.
+    ``atom_descriptors``: the split's ``AtomDescriptorTable`` for a descriptor model."""
     from .ensemble import accumulate_model
     ev = Evaluator(table, metrics, table.dataset_type, scaler) if evaluator is None else evaluator
     if ev.table is not table:
         raise ValueError('evaluate: the evaluator given scores another target table')
     if table.n_rows:
-        accumulate_model(ev, 0, model, batches, scaler, features, row_mask, encodings)
+        accumulate_model(ev, 0, model, batches, scaler, features, row_mask, encodings,
+                         atom_descriptors=atom_descriptors)
     return ev.scores()

@@ -16,7 +16,7 @@ import numpy as np
 import torch
 
 from . import _native
-from .ensemble import _open_model, make_batches, model_features
+from .ensemble import _open_model, make_batches, model_atom_descriptors, model_features
 from .features import FeatureTable
 from .predict import LATENT_TYPES, PredictionSink, device_predictions
 
@@ -97,13 +97,15 @@ class LatentAccumulator(PredictionSink):
         return (self._sum.double() / m).float()
 
 
-def model_fingerprint(model, batches, fingerprint_type: str = 'MPN', features: Optional[FeatureTable] = None
-                      ) -> torch.Tensor:
+def model_fingerprint(model, batches, fingerprint_type: str = 'MPN', features: Optional[FeatureTable] = None,
+                      atom_descriptors=None) -> torch.Tensor:
     """``model_fingerprint`` of the reference (molecule_fingerprint.py:151-183) as one float32 device tensor: the
     model's ``fingerprint(..., fingerprint_type)`` of every batch of ``batches`` (``BatchMolGraph`` s; a model of
     several molecules takes lists of them), rows in batch order.  ``MPN``: the FFN's input, ``features`` joined when
-    given (they may be left out: the encoders alone run); ``last_FFN``: ``[N][ffn_hidden_size]``."""
-    parts = [v for _, v in device_predictions(model, batches, features, latent=fingerprint_type)]
+    given (they may be left out: the encoders alone run); ``last_FFN``: ``[N][ffn_hidden_size]``.
+    ``atom_descriptors``: the rows' ``AtomDescriptorTable`` for a descriptor model."""
+    parts = [v for _, v in device_predictions(model, batches, features, latent=fingerprint_type,
+                                              atom_descriptors=atom_descriptors)]
     if not parts:
         dev = next(model.parameters()).device
         return torch.empty((0, 0), dtype=torch.float32, device=dev)
@@ -128,7 +130,8 @@ def fingerprint_width(model, fingerprint_type: str) -> int:
 
 
 def molecule_fingerprint(checkpoints_or_models, graphs: Sequence, batch_size: int, fingerprint_type: str = 'MPN',
-                         features=None, phase_features=None, features_scaling: bool = True, device=None) -> np.ndarray:
+                         features=None, phase_features=None, features_scaling: bool = True, device=None,
+                         atom_descriptors=None, atom_descriptor_scaling: bool = True) -> np.ndarray:
     """The fingerprints of ``graphs`` (``MolGraph`` records, one per row) under every model, float64 numpy
     ``[N][fp][M]`` as the reference's ``molecule_fingerprint`` returns them.  ``checkpoints_or_models``: checkpoint
     paths, ``(model, data_scaler, features_scaler)`` tuples or models (a sequence: the array's last axis is its
@@ -136,7 +139,9 @@ def molecule_fingerprint(checkpoints_or_models, graphs: Sequence, batch_size: in
     ``features`` through its own features scaler (``features_scaling=False``: as they are) and ``phase_features``
     unscaled.  ``MPN``: fp = ``hidden_size * number_of_molecules``, the feature columns dropped; features are not
     needed, even for a model trained with them (the encoders alone run).  ``last_FFN``: fp = ``ffn_hidden_size``.
-    One host copy, after the last model."""
+    ``atom_descriptors``: one raw ``[n_atoms][d]`` array per row for descriptor models, each model scaling them
+    with its own ``atom_descriptor_scaler`` (``ensemble.model_atom_descriptors``).  One host copy, after the last
+    model."""
     device = torch.device('cuda', 0) if device is None else torch.device(device)
     items = list(checkpoints_or_models)
     if not items:
@@ -158,9 +163,11 @@ def molecule_fingerprint(checkpoints_or_models, graphs: Sequence, batch_size: in
         if fingerprint_type != 'MPN' or (needs and (features is not None or phase_features is not None)):
             rows = model_features(model, features, features_scaler if features_scaling else None, phase_features, k)
             table = None if rows is None else FeatureTable(rows, device)
-        for r0, v in device_predictions(model, batches, table, n_rows=n, latent=fingerprint_type):
+        desc = model_atom_descriptors(item, model, atom_descriptors, device, atom_descriptor_scaling, k)
+        for r0, v in device_predictions(model, batches, table, n_rows=n, latent=fingerprint_type,
+                                        atom_descriptors=desc):
             acc.add(v, r0, k)
-        del model, table
+        del model, table, desc
     if n == 0:
         return np.zeros((0, acc.width, len(items)))
     return acc.columns().cpu().numpy()

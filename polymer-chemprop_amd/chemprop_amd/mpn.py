@@ -19,6 +19,7 @@ import torch.nn as nn
 from torch.optim.optimizer import register_optimizer_step_post_hook
 
 from . import _native
+from . import atom_descriptors as _ad
 from .featurization import BatchMolGraph, get_atom_fdim, get_bond_fdim, mol2graph
 from .nn_utils import get_activation_function
 
@@ -127,6 +128,8 @@ def saved_preactivations(out: torch.Tensor):
     W_o pre-activation [n_atoms, H] (mpn.py:133)}``.  ``out`` must come from ``MPNEncoder.forward``
     with gradients enabled."""
     ctx = out.grad_fn
+    if ctx is not None and not hasattr(ctx, 'ws') and type(ctx).__name__.startswith('_LayerAfterReadout'):
+        ctx = ctx.next_functions[0][0]  # (descriptors from a device table: the layer sits behind the encoder)
     if ctx is None or not hasattr(ctx, 'ws'):
         raise ValueError('not the output of a training-mode MPNEncoder forward')
     lay = _native.WdSaved()
@@ -467,9 +470,76 @@ class MPNEncoder(nn.Module):
         gs.atom_fdim, gs.bond_fdim = self.atom_fdim, self.bond_fdim
         return gs
 
-    def forward(self, mol_graph: BatchMolGraph, atom_descriptors_batch: List[np.ndarray] = None) -> torch.FloatTensor:
-        """mpn.py:66-173 -> [num_molecules, hidden_size (+ atom_descriptors_size)]."""
-        if atom_descriptors_batch is None and not torch.is_grad_enabled():
+    def _table_rows_checked(self, mol_graph, rows):
+        """The host checks of a device-table descriptor batch (``atom_descriptors.AtomDescriptorRows``)."""
+        if not isinstance(rows, _ad.AtomDescriptorRows):
+            raise TypeError('atom descriptors are a list of numpy arrays or atom_descriptors.AtomDescriptorRows '
+                            f'(got {type(rows).__name__})')
+        if not hasattr(self, 'atom_descriptors_layer'):
+            raise ValueError('atom descriptors given but the encoder has no atom_descriptors_layer')
+        if rows.width != self.atom_descriptors_size:
+            raise ValueError(f'{rows.width} descriptors per atom for an encoder with atom_descriptors_size '
+                             f'{self.atom_descriptors_size}')
+        device = self.W_i.weight.device
+        if device.type != 'cuda' or rows.device != device:
+            raise RuntimeError(f'atom descriptor table on {rows.device}, encoder on {device}: both belong on one GPU')
+        rows.bind(mol_graph)
+        return device
+
+    def _after_readout(self) -> bool:
+        """Whether ``atom_descriptors_layer`` may run after the readout: encoder dropout inactive (the masks sit
+        on the atom rows, before and after the layer: nothing commutes then) and a width the row kernels take."""
+        return not (self.training and self.dropout > 0) and \
+            self.hidden_size + self.atom_descriptors_size <= _native.DESC_MAX_WIDTH
+
+    def _join_struct(self, mol_graph, device, grad: bool):
+        """The graph struct whose molecule scopes, atom weights and Xn the descriptor join reads: the one the
+        descriptor-free forward just used."""
+        dg = mol_graph.device_graph(device, self.atom_messages, self.bond_fdim, not self.bias and not grad)
+        dg.use_on(torch.cuda.current_stream(device))
+        return self._graph_struct(dg), dg
+
+    def _forward_table_rows(self, mol_graph, rows) -> torch.FloatTensor:
+        """``forward`` for descriptors in a device table.  Dropout inactive: the descriptor-free forward (every
+        fast path it has), then ``wdmpnn_desc_join`` and ``wdmpnn_desc_layer`` on the B readout rows.  Active
+        dropout: ``wdmpnn_desc_rows`` fills the per-atom array and the per-atom path runs as for a list."""
+        device = self._table_rows_checked(mol_graph, rows)
+        if not self._after_readout():
+            return self.forward(mol_graph, None, _desc_rows=rows)
+        emb = self.forward(mol_graph)
+        lin = self.atom_descriptors_layer
+        W, b = _f32(lin.weight), _f32(lin.bias)
+        if not (torch.is_grad_enabled() and (emb.requires_grad or W.requires_grad or
+                                             (b is not None and b.requires_grad))):
+            return self.apply_descriptor_layer(mol_graph, emb, rows)
+        # (the context keeps the device graph and the rows alive: the join reads both through raw pointers)
+        gs, dg = self._join_struct(mol_graph, device, emb.requires_grad)
+        return _ad._LayerAfterReadout.apply(emb, W, b, rows, gs, _native.AGGREGATIONS[self.aggregation],
+                                            float(self.aggregation_norm), (dg, rows))
+
+    def apply_descriptor_layer(self, mol_graph, emb: torch.Tensor, rows) -> torch.FloatTensor:
+        """``atom_descriptors_layer`` after the readout, without autograd: ``emb`` is this encoder's
+        descriptor-free output for ``mol_graph`` (from ``forward`` or ``forward_many``), ``rows`` the batch's
+        ``AtomDescriptorRows``; one join and one layer launch.  For callers that encode several batches at once
+        (``predict.device_predictions``)."""
+        device = self._table_rows_checked(mol_graph, rows)
+        if not self._after_readout():
+            raise RuntimeError('the descriptor layer runs after the readout only without active encoder dropout '
+                               f'and up to a width of {_native.DESC_MAX_WIDTH}')
+        lin = self.atom_descriptors_layer
+        gs, _ = self._join_struct(mol_graph, device, False)
+        sid = _native.current_stream(device)
+        x = _ad.desc_join(rows, gs, emb.detach().contiguous(), _native.AGGREGATIONS[self.aggregation],
+                          float(self.aggregation_norm), sid)
+        return _ad.desc_layer(x, _f32(lin.weight).detach(), None if lin.bias is None else _f32(lin.bias).detach(), sid)
+
+    def forward(self, mol_graph: BatchMolGraph, atom_descriptors_batch: List[np.ndarray] = None,
+                _desc_rows=None) -> torch.FloatTensor:
+        """mpn.py:66-173 -> [num_molecules, hidden_size (+ atom_descriptors_size)].  ``atom_descriptors_batch``:
+        the reference's list of numpy arrays, or ``atom_descriptors.AtomDescriptorRows`` of a device table."""
+        if atom_descriptors_batch is not None and not isinstance(atom_descriptors_batch, (list, tuple)):
+            return self._forward_table_rows(mol_graph, atom_descriptors_batch)
+        if atom_descriptors_batch is None and _desc_rows is None and not torch.is_grad_enabled():
             out = self._infer(mol_graph)
             if out is not None:
                 return out
@@ -483,10 +553,15 @@ class MPNEncoder(nn.Module):
         dg = mol_graph.device_graph(device, self.atom_messages, self.bond_fdim, not self.bias and not grad)
         dg.use_on(torch.cuda.current_stream(device))
         # descriptors are per call: their struct is never cached
-        gs = self._graph_struct(dg) if atom_descriptors_batch is None else self._new_graph_struct(dg)
+        gs = self._graph_struct(dg) if atom_descriptors_batch is None and _desc_rows is None else \
+            self._new_graph_struct(dg)
         desc = None
         hidden_out = self.hidden_size
-        if atom_descriptors_batch is not None:  # mpn.py:77-79, 136-143
+        if _desc_rows is not None:  # rows of a device table (active dropout): one gather launch, no host copy
+            desc = _ad.desc_rows(_desc_rows, gs, _native.current_stream(device))
+            gs.atom_desc, gs.desc_dim = desc.data_ptr(), _desc_rows.width
+            hidden_out += _desc_rows.width
+        elif atom_descriptors_batch is not None:  # mpn.py:77-79, 136-143
             if not hasattr(self, 'atom_descriptors_layer'):
                 raise ValueError('atom descriptors given but the encoder has no atom_descriptors_layer')
             d = atom_descriptors_batch[0].shape[1]

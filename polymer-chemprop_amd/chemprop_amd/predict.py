@@ -15,6 +15,7 @@ from typing import Iterator, Optional, Tuple
 import numpy as np
 import torch
 
+from .atom_descriptors import AtomDescriptorTable
 from .features import FeatureTable, join_features
 
 
@@ -56,14 +57,14 @@ class PredictionSink:
         return hit[1], hit[2]
 
 
-def _fallback_predict(model, batch, feats, mask, return_embeddings: bool = False):
+def _fallback_predict(model, batch, feats, mask, return_embeddings: bool = False, desc=None):
     """A model whose FFN the native prediction heads refuse: its own forward (a spectra model's output
     normalised per row with torch ops, as ``head_predict(normalize=True)`` does it natively).
     ``return_embeddings``: (predictions, the FFN input), as the model's forward returns them."""
     if return_embeddings:
-        out, emb = model(_molecules(batch), feats, return_embeddings=True)
+        out, emb = model(_molecules(batch), feats, desc, return_embeddings=True)
     else:
-        out, emb = model(_molecules(batch), feats), None
+        out, emb = model(_molecules(batch), feats, desc), None
     if getattr(model, 'spectra', False):
         m = torch.ones_like(out, dtype=torch.bool) if mask is None else mask.bool()
         s = torch.where(m, out, torch.zeros_like(out))
@@ -93,7 +94,8 @@ LATENT_TYPES = ('MPN', 'last_FFN')
 def device_predictions(model, batches, features: Optional[FeatureTable] = None,
                        row_mask: Optional[torch.Tensor] = None, encodings: Optional[torch.Tensor] = None,
                        own_forward: bool = False, n_rows: Optional[int] = None, latent: Optional[str] = None,
-                       with_encodings: bool = False) -> Iterator[Tuple]:
+                       with_encodings: bool = False,
+                       atom_descriptors: Optional[AtomDescriptorTable] = None) -> Iterator[Tuple]:
     """``(row0, predictions)`` of ``model`` for every ``BatchMolGraph`` of ``batches`` (row order = batch order):
     eval mode, ``no_grad``, float32 on the device, no host sync.  ``features``: the model's input features of
     every row, as the model sees them; ``row_mask``: a spectra model's included positions, bool or uint8
@@ -113,7 +115,14 @@ def device_predictions(model, batches, features: Optional[FeatureTable] = None,
     the features may then be left out for a model trained with them, and the encoders alone run.  ``'last_FFN'``:
     ``train.head_latent`` of that input, ``[B][ffn_hidden_size]`` (``MoleculeModel.fingerprint``'s torch slice for an
     FFN the native stack does not run).  ``with_encodings``: yield ``(row0, predictions, x)``, ``x`` being the FFN
-    input the same pass holds, as ``model.encoder(...)`` returns it."""
+    input the same pass holds, as ``model.encoder(...)`` returns it.
+
+    ``atom_descriptors``: the table of every row's (scaled) atom descriptors, for a model with
+    ``atom_descriptors='descriptor'``, molecule k of the table being row k.  The encodings still come from
+    ``forward_many`` (the encoder runs as for a model without descriptors); per batch one join and one layer launch
+    apply ``atom_descriptors_layer`` after the readout (``MPNEncoder.apply_descriptor_layer``).  A descriptor
+    model given no table, or a table given to a model without the layer, is a ``ValueError``; so are cached
+    ``encodings`` with descriptors."""
     # (here: importing the package does not import the training code)
     from .train import NO_LATENT_LAYER, _head_linears, _predict_head, head_latent, head_predict
     model.eval()
@@ -143,6 +152,17 @@ def device_predictions(model, batches, features: Optional[FeatureTable] = None,
                          'the model takes no input features, but features were given')
     if own_forward and encodings is not None:
         raise ValueError('own_forward runs the encoder: it takes no encodings')
+    wants_desc = getattr(mpn, 'atom_descriptors', None) == 'descriptor' and not mpn.features_only
+    if wants_desc != (atom_descriptors is not None) and not (alone and wants_desc):
+        raise ValueError('the model takes atom descriptors and none were given' if wants_desc else
+                         'the model takes no atom descriptors, but atom descriptors were given')
+    if atom_descriptors is not None:
+        if not isinstance(atom_descriptors, AtomDescriptorTable):
+            raise ValueError('atom_descriptors: an atom_descriptors.AtomDescriptorTable of the rows is expected')
+        if len(atom_descriptors) != n:
+            raise ValueError(f'{len(atom_descriptors)} molecules in the atom descriptor table for {n} rows')
+        if encodings is not None:
+            raise ValueError('cached encodings hold no atom descriptors: a descriptor model runs its encoder')
     head = None if own_forward else _predict_head(model)
     spectra = bool(getattr(model, 'spectra', False))
     if latent == 'last_FFN':
@@ -157,8 +177,10 @@ def device_predictions(model, batches, features: Optional[FeatureTable] = None,
     if encodings is not None and head is None:
         raise NotImplementedError('predictions from encodings: the model\'s FFN is not one the native heads run')
     findex = features.index(range(n)) if features is not None and n else None
+    dindex = atom_descriptors.index(range(n)) if atom_descriptors is not None and n else None
     many = encodings is None and (head is not None or latent == 'MPN') and not mpn.features_only and \
-        len(mpn.encoder) == 1 and mpn.atom_descriptors is None
+        len(mpn.encoder) == 1 and (mpn.atom_descriptors is None or
+                                   (dindex is not None and mpn.encoder[0]._after_readout()))
     for g0 in range(0, len(sizes), 8):
         embs = mpn.encoder[0].forward_many([_molecules(b)[0] for b in batches[g0:g0 + 8]]) if many else \
             [None] * len(sizes[g0:g0 + 8])
@@ -166,18 +188,21 @@ def device_predictions(model, batches, features: Optional[FeatureTable] = None,
             r0, r1 = starts[j], starts[j + 1]
             feats = None if findex is None else findex[r0:r1]
             mask = None if row_mask is None or not spectra else row_mask[r0:r1]
+            desc = None if dindex is None else dindex[r0:r1]
             if own_forward:
-                yield r0, model(_molecules(batches[j]), feats)
+                yield r0, model(_molecules(batches[j]), feats, desc)
                 continue
             if head is None and latent is None:
-                out = _fallback_predict(model, batches[j], feats, mask, with_encodings)
+                out = _fallback_predict(model, batches[j], feats, mask, with_encodings, desc)
                 yield (r0,) + tuple(out) if with_encodings else (r0, out)
                 continue
             if encodings is not None:
                 emb = encodings[r0:r1]
             if emb is None:
-                x = _encode_alone(mpn, batches[j]) if alone else mpn(_molecules(batches[j]), feats)
+                x = _encode_alone(mpn, batches[j]) if alone else mpn(_molecules(batches[j]), feats, desc)
             else:
+                if desc is not None:  # (atom_descriptors_layer after the readout: one join, one layer launch)
+                    emb = mpn.encoder[0].apply_descriptor_layer(_molecules(batches[j])[0], emb, desc)
                 x = emb if feats is None else join_features(emb, feats)
             if latent == 'MPN':
                 yield r0, x

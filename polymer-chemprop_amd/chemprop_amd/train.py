@@ -873,20 +873,35 @@ def _features_ok(mpn, features_batch) -> bool:
     return features_batch is None
 
 
-def _direct_encoder(model: nn.Module, mol_batch, features_batch, head):
-    """The MPNEncoder when the step can skip autograd: one molecule per input, no descriptors, extra features
+def _descriptors_ok(mpn, enc, atom_descriptors_batch) -> bool:
+    """The descriptor side of a direct step: a model without ``atom_descriptors_layer`` gets none; a model with
+    it gets rows of a device table (``atom_descriptors.AtomDescriptorRows``) and has no encoder dropout, so that the
+    layer runs after the readout (``MPNEncoder._after_readout``).  A list of numpy arrays and active dropout keep
+    the autograd path."""
+    has = hasattr(enc, 'atom_descriptors_layer')
+    if not mpn.atom_descriptors and not has:
+        return atom_descriptors_batch is None
+    from .atom_descriptors import is_device_descriptors
+    return mpn.atom_descriptors == 'descriptor' and has and is_device_descriptors(atom_descriptors_batch) and \
+        atom_descriptors_batch.device.type == 'cuda' and enc.dropout == 0 and enc._after_readout()
+
+
+def _direct_encoder(model: nn.Module, mol_batch, features_batch, head, atom_descriptors_batch=None):
+    """The MPNEncoder when the step can skip autograd: one molecule per input, atom descriptors only as rows of
+    a device table with the layer after the readout (``_descriptors_ok``), extra features
     only as device rows (``_features_ok``), depth >= 2, every parameter trainable and written by the direct
-    step (the encoder's native gradients and the fused head's); else None."""
+    step (the encoder's native gradients, the descriptor layer's and the fused head's); else None."""
     from .model import MoleculeModel
     from .mpn import MPNEncoder
     if not isinstance(model, MoleculeModel) or type(model).forward is not MoleculeModel.forward:
         return None
     mpn = model.encoder
-    if mpn.features_only or not _features_ok(mpn, features_batch) or mpn.atom_descriptors or \
+    if mpn.features_only or not _features_ok(mpn, features_batch) or \
             len(mpn.encoder) != 1 or not isinstance(mol_batch, (list, tuple)) or len(mol_batch) != 1:
         return None
     enc = mpn.encoder[0]
-    if type(enc) is not MPNEncoder or enc.depth < 2 or enc.atom_messages or hasattr(enc, 'atom_descriptors_layer'):
+    if type(enc) is not MPNEncoder or enc.depth < 2 or enc.atom_messages or \
+            not _descriptors_ok(mpn, enc, atom_descriptors_batch):
         return None
     if type(mol_batch[0]).__name__ != 'BatchMolGraph':
         return None
@@ -898,6 +913,8 @@ def _direct_encoder(model: nn.Module, mol_batch, features_batch, head):
     linears, _, slope, _, _, _ = _head_parts(head)
     head_params = [t for l in linears for t in (l.weight, l.bias)] + [slope]
     written = {id(t) for _, t in enc._direct_names()} | {id(t) for t in head_params if t is not None}
+    if atom_descriptors_batch is not None:  # (the layer after the readout writes its own two gradients)
+        written |= {id(t) for t in enc.atom_descriptors_layer._parameters.values() if t is not None}
     # (a shared activation module sits at several places of the FFN's Sequential: its slope is met once per site)
     if set(ids) != written:
         return None
@@ -1015,7 +1032,8 @@ def frozen_encodings(model: nn.Module, graphs: Sequence, batch_size: int) -> tor
 
 
 def _direct_step(model, enc, graph, head, target_batch, target_weights, data_weights, bucket=None,
-                 plan: _FrozenPlan = None, encodings: torch.Tensor = None, features=None) -> torch.Tensor:
+                 plan: _FrozenPlan = None, encodings: torch.Tensor = None, features=None,
+                 descriptors=None) -> torch.Tensor:
     """Forward, loss and every gradient of a fused-head step without the autograd engine: the encoder's
     training forward, wdmpnn_head_mse (loss, d loss / d encoding, the head's gradients) and the encoder's
     backward on that gradient (the incoming gradient of the loss is 1), each written straight into the
@@ -1030,7 +1048,11 @@ def _direct_step(model, enc, graph, head, target_batch, target_weights, data_wei
     one ``wdmpnn_join_rows`` launch builds the head's input x = [encoding | features] after the encoder
     forward, the head runs on x (F = ld_x = H + Ff), and one more launch makes the encoder's slice of dx,
     dx[:, 0:H], contiguous for the encoder backward (a frozen encoder has no dx and no such launch): what
-    ``torch.cat`` and its backward do on the autograd path, bitwise."""
+    ``torch.cat`` and its backward do on the autograd path, bitwise.
+    ``descriptors`` (``atom_descriptors.AtomDescriptorRows``, encoder dropout 0): the encoder runs as for a model
+    without descriptors, then ``wdmpnn_desc_join`` and ``wdmpnn_desc_layer`` give the encoding ``[B][H + d]`` the
+    rest of the step sees; after the head, one ``wdmpnn_desc_layer_backward`` launch writes the layer's two
+    gradients and the encoder backward's input."""
     linears, _, _, kind, n_classes, spectra = _head_parts(head)
     spectra = spectra is not None
     nc = n_classes if kind == 2 and not spectra else 0  # (multiclass: _loss_table checks the class indices on the host)
@@ -1041,6 +1063,14 @@ def _direct_step(model, enc, graph, head, target_batch, target_weights, data_wei
         out = enc._frozen_forward(graph)
     else:
         out, state = enc._train_forward(graph)
+    desc_x = None
+    if descriptors is not None:
+        from . import atom_descriptors as ad
+        descriptors.bind(graph)
+        lin, sid = enc.atom_descriptors_layer, _native.current_stream(out.device)
+        desc_x = ad.desc_join(descriptors, state[0], out, _native.AGGREGATIONS[enc.aggregation],
+                              float(enc.aggregation_norm), sid)
+        out = ad.desc_layer(desc_x, lin.weight, lin.bias, sid)
     n_emb = out.shape[1] if out.dim() == 2 else 0
     if features is not None:
         out = join_features(out, features)  # (x: the head's input from here on)
@@ -1074,6 +1104,12 @@ def _direct_step(model, enc, graph, head, target_batch, target_weights, data_wei
     if not enc_frozen:
         if features is not None:
             dx = split_columns(dx, 0, n_emb)  # (the encoder's slice of dx, contiguous: torch.cat's backward)
+        if desc_x is not None:
+            lin, dy = enc.atom_descriptors_layer, dx
+            dx = torch.empty((dy.shape[0], enc.hidden_size), dtype=torch.float32, device=dev)
+            ad.desc_layer_backward(dy, desc_x, lin.weight, enc.hidden_size, _grad_buffer(lin.weight),
+                                   None if lin.bias is None else _grad_buffer(lin.bias), dx,
+                                   _native.current_stream(dev))
         enc._train_backward(state, dx, {n: _grad_buffer(p) for n, p in enc._direct_names()})
     return loss
 
@@ -1082,7 +1118,7 @@ def train_step(model: nn.Module, mol_batch, target_batch, loss_func: Callable, o
                scheduler: _LRScheduler = None, dataset_type: str = 'regression', features_batch=None,
                target_weights=None, data_weights=None, grad_clip: float = None,
                bucket: GradBucket = None, fused_head: bool = True, direct: bool = True,
-               encodings: torch.Tensor = None) -> torch.Tensor:
+               encodings: torch.Tensor = None, atom_descriptors_batch=None) -> torch.Tensor:
     """One optimisation step (train.py:55-86).  With ``bucket`` the gradients are averaged over the
     data-parallel ranks (one all-reduce) before clipping and the optimizer step.  ``fused_head``: the
     default regression / classification / multiclass head + loss run as ``wdmpnn_head_mse`` (same loss and gradients within fp32
@@ -1109,12 +1145,21 @@ def train_step(model: nn.Module, mol_batch, target_batch, loss_func: Callable, o
     autograd path (``MPN.forward`` stacks, copies and concatenates them); ``features.FeatureRows`` (rows of a
     device-resident ``FeatureTable``) or a float32 device tensor ``[B][Ff]`` take the direct step, frozen plans and
     ``encodings=`` included: two more launches than the same step without features (the join and the split of
-    dx), one with a frozen encoder or cached encodings, and the same losses and gradients, bitwise."""
+    dx), one with a frozen encoder or cached encodings, and the same losses and gradients, bitwise.
+
+    ``atom_descriptors_batch`` (a model with ``atom_descriptors='descriptor'``): ``AtomDescriptorRows`` of a
+    device-resident ``atom_descriptors.AtomDescriptorTable`` take the direct step when the encoder has no dropout
+    (the descriptor layer runs after the readout: encoder forward, join, layer, features join if any, head,
+    layer backward, encoder backward).  A list of numpy arrays as in the reference, active dropout, atom
+    messages, depth 1 and partly frozen models take the autograd path."""
+    if encodings is not None and atom_descriptors_batch is not None:
+        raise ValueError('train_step(encodings=...) takes no atom descriptors (frozen plans with descriptors keep the '
+                         'autograd path)')
     if not model.training:  # (module.train() walks every submodule: the reference sets it once per epoch)
         model.train()
     head = _fusable_head(model, loss_func, dataset_type) if fused_head else None
-    enc = _direct_encoder(model, mol_batch, features_batch, head) if head is not None and direct and \
-        encodings is None else None
+    enc = _direct_encoder(model, mol_batch, features_batch, head, atom_descriptors_batch) \
+        if head is not None and direct and encodings is None else None
     plan = None
     if enc is None and head is not None and bucket is None:
         plan = _frozen_plan(model, mol_batch, features_batch, head, cached=encodings is not None)
@@ -1142,17 +1187,19 @@ def train_step(model: nn.Module, mol_batch, target_batch, loss_func: Callable, o
         if bucket is not None:
             bucket.attach()
         loss = _direct_step(model, enc, mol_batch[0], head, target_batch, target_weights, data_weights, bucket,
-                            features=features_batch)
+                            features=features_batch, descriptors=atom_descriptors_batch)
     else:
         if bucket is not None:
             bucket.zero()
         else:
             optimizer.zero_grad(set_to_none=True)  # (the optimizer holds every model parameter: build_optimizer)
+        # (any model with a (batch, features) forward trains here: descriptors are passed on only when given)
+        desc = () if atom_descriptors_batch is None else (atom_descriptors_batch,)
         if head is not None:  # the default regression head: ffn + loss + their gradients as two HIP launches
-            loss = head_loss(model.encoder(mol_batch, features_batch), head, target_batch, target_weights,
-                             data_weights)
+            loss = head_loss(model.encoder(mol_batch, features_batch, *desc), head, target_batch,
+                             target_weights, data_weights)
         else:
-            preds = model(mol_batch, features_batch)
+            preds = model(mol_batch, features_batch, *desc)
             loss = batch_loss(preds, target_batch, loss_func, dataset_type, target_weights, data_weights)
         loss.backward()
     if bucket is not None:

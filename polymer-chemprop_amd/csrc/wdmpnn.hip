@@ -39,6 +39,7 @@
 #include "wdmpnn.h"
 #include "ensemble.hpp"
 #include "evaluate.hpp"
+#include "atom_desc.hpp"
 
 using namespace wd;
 
@@ -1771,6 +1772,136 @@ int wdmpnn_join_rows(const WdJoin *j, void *stream) {
     A.units = units;
     hipLaunchKernelGGL(join_rows_kernel, dim3(ew_blocks((size_t)j->B * units)), dim3(256), 0, (hipStream_t)stream, A);
     WD_CHECK_LAUNCH("join_rows");
+    return 0;
+}
+
+int wdmpnn_desc_join(const WdDescJoin *j, void *stream) {
+    WD_KERNELS_OK();
+    if (!j || !j->g) return fail(WD_ERR_ARG, "desc_join: null %s", !j ? "struct" : "graph");
+    const WdGraph *g = j->g;
+    const int B = g->n_mols;
+    if (B < 0 || j->H <= 0 || j->d <= 0 || j->table_rows < 0 || j->ld_emb < j->H || j->ld_table < j->d ||
+        (int64_t)j->ld_x < (int64_t)j->H + j->d + 1 || j->aggregation < WD_AGG_MEAN || j->aggregation > WD_AGG_NORM)
+        return fail(WD_ERR_SHAPE, "desc_join: needs B >= 0, H > 0, d > 0, table_rows >= 0, ld_emb >= H, ld_table >= d, "
+                    "ld_x >= H + d + 1, a known aggregation (got B %d H %d d %d table_rows %lld ld_emb %d ld_table %d "
+                    "ld_x %d aggregation %d)", B, j->H, j->d, (long long)j->table_rows, j->ld_emb, j->ld_table, j->ld_x,
+                    j->aggregation);
+    if ((int64_t)j->H + j->d > WD_DESC_MAX_WIDTH)
+        return fail(WD_ERR_UNSUPPORTED, "desc_join: H + d = %lld (at most %d)", (long long)j->H + j->d, WD_DESC_MAX_WIDTH);
+    if (B == 0) return 0;
+    if (!j->emb || !j->table || !j->row0 || !j->x || !g->mol_start || !g->mol_size || !g->w_atoms || !g->degree_of_polym)
+        return fail(WD_ERR_ARG, "desc_join: null emb, table, row0, x, mol_start, mol_size, w_atoms or degree_of_polym");
+    DescJoinArgs A{};
+    A.emb = reinterpret_cast<const uint32_t *>(j->emb);
+    A.table = j->table;
+    A.row0 = j->row0;
+    A.mol_start = g->mol_start;
+    A.mol_size = g->mol_size;
+    A.w_atoms = g->w_atoms;
+    A.xn = g->degree_of_polym;
+    A.x = reinterpret_cast<uint32_t *>(j->x);
+    A.norm = j->aggregation_norm;
+    A.H = j->H;
+    A.d = j->d;
+    A.ld_emb = j->ld_emb;
+    A.ld_table = j->ld_table;
+    A.ld_x = j->ld_x;
+    A.agg = j->aggregation;
+    hipLaunchKernelGGL(desc_join_kernel, dim3(B), dim3(256), 0, (hipStream_t)stream, A);
+    WD_CHECK_LAUNCH("desc_join");
+    return 0;
+}
+
+int wdmpnn_desc_layer(const WdDescLayer *l, void *stream) {
+    WD_KERNELS_OK();
+    if (!l) return fail(WD_ERR_ARG, "desc_layer: null struct");
+    if (l->B < 0 || l->Hd <= 0 || (int64_t)l->ld_x < (int64_t)l->Hd + 1 || l->ld_y < l->Hd)
+        return fail(WD_ERR_SHAPE, "desc_layer: needs B >= 0, Hd > 0, ld_x >= Hd + 1, ld_y >= Hd (got B %d Hd %d ld_x %d "
+                    "ld_y %d)", l->B, l->Hd, l->ld_x, l->ld_y);
+    if (l->Hd > WD_DESC_MAX_WIDTH)
+        return fail(WD_ERR_UNSUPPORTED, "desc_layer: width %d (at most %d)", l->Hd, WD_DESC_MAX_WIDTH);
+    if (l->B == 0) return 0;
+    if (!l->x || !l->W_d || !l->y) return fail(WD_ERR_ARG, "desc_layer: null x, W_d or y");
+    DescLayerArgs A{};
+    A.x = l->x;
+    A.W = l->W_d;
+    A.bias = l->b_d;
+    A.y = l->y;
+    A.B = l->B;
+    A.Hd = l->Hd;
+    A.ld_x = l->ld_x;
+    A.ld_y = l->ld_y;
+    hipLaunchKernelGGL(desc_layer_kernel, dim3((l->Hd + 15) / 16, (l->B + 15) / 16), dim3(256), 0, (hipStream_t)stream, A);
+    WD_CHECK_LAUNCH("desc_layer");
+    return 0;
+}
+
+int wdmpnn_desc_layer_backward(const WdDescLayerBackward *l, void *stream) {
+    WD_KERNELS_OK();
+    if (!l) return fail(WD_ERR_ARG, "desc_layer_backward: null struct");
+    if (l->B < 0 || l->H <= 0 || l->Hd < l->H || l->ld_dy < l->Hd || (int64_t)l->ld_x < (int64_t)l->Hd + 1 ||
+        (l->demb && l->ld_demb < l->H))
+        return fail(WD_ERR_SHAPE, "desc_layer_backward: needs B >= 0, H > 0, Hd >= H, ld_dy >= Hd, ld_x >= Hd + 1, "
+                    "ld_demb >= H (got B %d H %d Hd %d ld_dy %d ld_x %d ld_demb %d)", l->B, l->H, l->Hd, l->ld_dy,
+                    l->ld_x, l->ld_demb);
+    if (l->Hd > WD_DESC_MAX_WIDTH)
+        return fail(WD_ERR_UNSUPPORTED, "desc_layer_backward: width %d (at most %d)", l->Hd, WD_DESC_MAX_WIDTH);
+    if (l->B == 0) return 0;
+    if (!l->dy || !l->x || (l->demb && !l->W_d)) return fail(WD_ERR_ARG, "desc_layer_backward: null dy, x or W_d");
+    DescLayerBwdArgs A{};
+    A.dy = l->dy;
+    A.x = l->x;
+    A.W = l->W_d;
+    A.dW = l->dW_d;
+    A.db = l->db_d;
+    A.demb = l->demb;
+    A.B = l->B;
+    A.H = l->H;
+    A.Hd = l->Hd;
+    A.ld_dy = l->ld_dy;
+    A.ld_x = l->ld_x;
+    A.ld_demb = l->ld_demb;
+    // the dW part's column tiles: x's columns 0 .. Hd - 1 for dW, column Hd (s) for db
+    const int jt_end = l->db_d ? l->Hd / 16 + 1 : (l->Hd + 15) / 16;
+    A.jt0 = l->dW_d ? 0 : l->Hd / 16;
+    A.jt_n = (l->dW_d || l->db_d) ? jt_end - A.jt0 : 0;
+    A.n_w = A.jt_n * ((l->Hd + 15) / 16);
+    A.e_cols = (l->H + 15) / 16;
+    const int n_e = l->demb ? A.e_cols * ((l->B + 15) / 16) : 0;
+    if (A.n_w + n_e == 0) return 0;
+    hipLaunchKernelGGL(desc_layer_bwd_kernel, dim3(A.n_w + n_e), dim3(256), 0, (hipStream_t)stream, A);
+    WD_CHECK_LAUNCH("desc_layer_backward");
+    return 0;
+}
+
+int wdmpnn_desc_rows(const WdDescRows *r, void *stream) {
+    WD_KERNELS_OK();
+    if (!r || !r->g) return fail(WD_ERR_ARG, "desc_rows: null %s", !r ? "struct" : "graph");
+    const WdGraph *g = r->g;
+    const int B = g->n_mols;
+    if (B < 0 || g->n_atoms < 1 || r->d <= 0 || r->table_rows < 0 || r->ld_table < r->d ||
+        r->rows < rup(g->n_atoms, 128) || r->ld < rup(r->d, 32))
+        return fail(WD_ERR_SHAPE, "desc_rows: needs B >= 0, n_atoms >= 1, d > 0, table_rows >= 0, ld_table >= d, rows >= "
+                    "n_atoms rounded up to 128, ld >= d rounded up to 32 (got B %d n_atoms %d d %d table_rows %lld "
+                    "ld_table %d rows %d ld %d)", B, g->n_atoms, r->d, (long long)r->table_rows, r->ld_table, r->rows,
+                    r->ld);
+    if (B == 0) return 0;
+    if (!r->table || !r->row0 || !r->atom_desc || !g->mol_start || !g->mol_size)
+        return fail(WD_ERR_ARG, "desc_rows: null table, row0, atom_desc, mol_start or mol_size");
+    DescRowsArgs A{};
+    A.table = reinterpret_cast<const uint32_t *>(r->table);
+    A.row0 = r->row0;
+    A.mol_start = g->mol_start;
+    A.mol_size = g->mol_size;
+    A.out = reinterpret_cast<uint32_t *>(r->atom_desc);
+    A.B = B;
+    A.d = r->d;
+    A.ld_table = r->ld_table;
+    A.rows = r->rows;
+    A.ld = r->ld;
+    A.n_atoms = g->n_atoms;
+    hipLaunchKernelGGL(desc_rows_kernel, dim3(ew_blocks((size_t)r->rows * r->ld)), dim3(256), 0, (hipStream_t)stream, A);
+    WD_CHECK_LAUNCH("desc_rows");
     return 0;
 }
 
