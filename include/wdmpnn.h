@@ -400,6 +400,37 @@ typedef struct WdJoin {
 } WdJoin;
 int wdmpnn_join_rows(const WdJoin *j, void *stream);
 
+/* The FFN input of a model of several molecules per input (number_of_molecules > 1; mpn.py:270-285, the
+ * torch.cat of the encoders' outputs and of the features) and its inverse, each one launch for any number
+ * of slots up to WD_MAX_SLOTS.  wdmpnn_slots_join:
+ *     x[b][k * H + j]       = slot[k][b * ld_slot + j]                              k < n_slots, j < H
+ *     x[b][n_slots * H + j] = feat[(feat_idx ? feat_idx[b] : b) * ld_feat + j]      j < Ff
+ * wdmpnn_slots_split: slot[k][b * ld_slot + j] = x[b][k * H + j] (the gradient of the join with respect to
+ * the slots: what torch.cat's backward hands to each encoder); it ignores the feature fields.
+ * Pure copies: every payload bit is preserved (NaN payloads, -0.0).  The join never writes columns of x at
+ * and beyond n_slots * H + Ff.  No atomics, a fixed thread-to-element map.  Both move 16-byte vectors when x,
+ * every slot pointer, feat (join with Ff > 0), ld_x, ld_slot, ld_feat (likewise) and H are all multiples of
+ * 16 bytes (the last Ff % 4 feature columns as single words), else word by word.  The slot pointers may
+ * point into one buffer: slot[k] = base + k * B * H with ld_slot = H is the slot-major [n_slots * B][H]
+ * matrix a shared encoder writes for the merged batch of all slots.  Indices are int64 like
+ * wdmpnn_join_rows'; the kernel clamps nothing and reads feat[feat_idx[b]]: range checking is the caller's.
+ * Refused before any launch: n_slots > WD_MAX_SLOTS (WD_ERR_UNSUPPORTED), n_slots < 1 or a NULL struct
+ * (WD_ERR_ARG); B < 0, H <= 0, ld_slot < H, Ff < 0, ld_feat < Ff, ld_x < n_slots * H + Ff (WD_ERR_SHAPE);
+ * x, a slot pointer or feat (with Ff > 0) NULL with B > 0 (WD_ERR_ARG).  B == 0 is a no-op. */
+#define WD_MAX_SLOTS 8
+typedef struct WdSlots {
+    int32_t B, n_slots, H;       /* rows, molecules per input, columns per slot          */
+    float *slot[WD_MAX_SLOTS];   /* slot k: [B][ld_slot], H columns used                 */
+    int32_t ld_slot;
+    const float *feat;           /* join only: [rows][ld_feat], or NULL with Ff == 0     */
+    int32_t ld_feat, Ff;
+    const int64_t *feat_idx;     /* [B] feature rows, or NULL: row b                     */
+    float *x;                    /* [B][ld_x], ld_x >= n_slots * H + Ff                  */
+    int32_t ld_x;
+} WdSlots;
+int wdmpnn_slots_join(const WdSlots *s, void *stream);
+int wdmpnn_slots_split(const WdSlots *s, void *stream);
+
 /* Atom descriptors from a device-resident table (--atom_descriptors descriptor; mpn.py:77-79, 136-143).
  * `table` [table_rows][ld_table] holds the (already scaled) descriptor rows of a data split, d columns, the atoms
  * of a molecule on consecutive rows; row0[b] (int64, like wdmpnn_join_rows' indices) is the first table row of

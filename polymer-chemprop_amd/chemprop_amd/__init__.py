@@ -13,8 +13,9 @@ from .features import FeatureIndex, FeatureRows, FeatureTable
 from .model import MoleculeModel
 from .mpn import MPN, MPNEncoder
 from .nn_utils import get_activation_function, index_select_ND, initialize_weights
+from .slots import SlotBatch
 
 __all__ = ['TrainArgs', 'BatchMolGraph', 'get_atom_fdim', 'get_bond_fdim', 'mol2graph', 'MoleculeModel', 'MPN',
            'MPNEncoder', 'get_activation_function', 'index_select_ND', 'initialize_weights', 'FeatureTable',
            'FeatureIndex', 'FeatureRows', 'TargetTable', 'Evaluator', 'evaluate', 'AtomDescriptorTable',
-           'AtomDescriptorIndex', 'AtomDescriptorRows']
+           'AtomDescriptorIndex', 'AtomDescriptorRows', 'SlotBatch']

@@ -49,12 +49,13 @@ EXPORTED_SYMBOLS = ('wdmpnn_abi_version', 'wdmpnn_last_error', 'wdmpnn_workspace
                     'wdmpnn_head_spectra_predict', 'wdmpnn_join_rows', 'wdmpnn_ensemble_add',
                     'wdmpnn_ensemble_sid', 'wdmpnn_eval_add', 'wdmpnn_eval_spectra', 'wdmpnn_eval_auc',
                     'wdmpnn_head_stack_latent', 'wdmpnn_latent_add', 'wdmpnn_desc_join', 'wdmpnn_desc_layer',
-                    'wdmpnn_desc_layer_backward', 'wdmpnn_desc_rows')
+                    'wdmpnn_desc_layer_backward', 'wdmpnn_desc_rows', 'wdmpnn_slots_join', 'wdmpnn_slots_split')
 HEAD_MAX_LAYERS = 6  # WD_HEAD_MAX_LAYERS
 HEAD_MAX_SPECTRUM = 8192  # WD_HEAD_MAX_SPECTRUM
 SPECTRA_ACTIVATIONS = {'exp': 0, 'softplus': 1}  # WdHeadSpectra.spectra_act
 SPECTRA_LOSSES = {'sid': 0, 'wasserstein': 1}  # WdHeadSpectra.loss_kind
 JOIN_MAX_SEGMENTS = 4  # WD_JOIN_MAX_SEGMENTS
+MAX_SLOTS = 8  # WD_MAX_SLOTS
 ENSEMBLE_MAX_MODELS = 32  # WD_ENSEMBLE_MAX_MODELS
 EVAL_SLOTS = 4  # WD_EVAL_SLOTS
 EVAL_KINDS = {'regression': 0, 'classification': 1, 'multiclass': 2}  # WD_EVAL_*
@@ -197,6 +198,12 @@ class WdJoin(Structure):
                 ('ld_out', c_int32)]
 
 
+class WdSlots(Structure):
+    _fields_ = [('B', c_int32), ('n_slots', c_int32), ('H', c_int32), ('slot', c_void_p * MAX_SLOTS),
+                ('ld_slot', c_int32), ('feat', c_void_p), ('ld_feat', c_int32), ('Ff', c_int32),
+                ('feat_idx', c_void_p), ('x', c_void_p), ('ld_x', c_int32)]
+
+
 class WdEnsembleAdd(Structure):
     _fields_ = [('pred', c_void_p), ('ld_pred', c_int32), ('B', c_int32), ('W', c_int32), ('k', c_int32),
                 ('row0', c_int64), ('scale_mean', c_void_p), ('scale_std', c_void_p), ('mean', c_void_p),
@@ -272,6 +279,36 @@ def join_rows(out, segments, stream: int) -> None:
     check(lib().wdmpnn_join_rows(ctypes.byref(j), stream), 'join rows')
 
 
+def _slots(x, slots, ld_slot: int, H: int, feat=None) -> WdSlots:
+    if len(slots) > MAX_SLOTS:
+        raise NotImplementedError(f'{len(slots)} molecules per input (at most {MAX_SLOTS})')
+    if x.dim() != 2 or not x.is_contiguous() or x.dtype != torch.float32:
+        raise TypeError('the joined matrix is a contiguous float32 matrix')
+    s = WdSlots()
+    s.B, s.n_slots, s.H, s.ld_slot = x.shape[0], len(slots), H, ld_slot
+    for k, p in enumerate(slots):
+        s.slot[k] = p
+    if feat is not None:
+        s.feat, s.ld_feat, s.Ff, s.feat_idx = feat[0], feat[1], feat[3], feat[4] or None
+    s.x, s.ld_x = x.data_ptr(), x.shape[1]
+    return s
+
+
+def slots_join(x, slots, ld_slot: int, H: int, feat, stream: int) -> None:
+    """wdmpnn_slots_join into ``x`` (float32 device tensor ``[B][ld_x]``, row-major): ``slots`` are the data
+    pointers of the per-molecule encodings ``[B][ld_slot]`` (``H`` columns used), ``feat`` a ``join_rows`` segment
+    ``(table pointer, ld, 0, Ff, index pointer or 0)`` or None.  Every index must have been range-checked by the
+    caller (``features.FeatureTable.index``)."""
+    if feat is not None and feat[2] != 0:
+        raise ValueError('slots_join: the feature rows start at column 0 of their table')
+    check(lib().wdmpnn_slots_join(ctypes.byref(_slots(x, slots, ld_slot, H, feat)), stream), 'slots join')
+
+
+def slots_split(x, slots, ld_slot: int, H: int, stream: int) -> None:
+    """wdmpnn_slots_split: ``x[:, k H : (k + 1) H]`` into slot ``k`` (data pointers as for :func:`slots_join`)."""
+    check(lib().wdmpnn_slots_split(ctypes.byref(_slots(x, slots, ld_slot, H)), stream), 'slots split')
+
+
 def head_spectra_scratch_bytes(B: int, F: int, Hf: int, T: int, L: int) -> int:
     """wdmpnn_head_spectra_scratch_bytes."""
     n = c_size_t()
@@ -338,6 +375,8 @@ def lib() -> ctypes.CDLL:
     L.wdmpnn_head_spectra.argtypes = [POINTER(WdHeadSpectra), c_void_p]
     L.wdmpnn_head_spectra_predict.argtypes = [POINTER(WdHeadSpectraPredict), c_void_p]
     L.wdmpnn_join_rows.argtypes = [POINTER(WdJoin), c_void_p]
+    L.wdmpnn_slots_join.argtypes = [POINTER(WdSlots), c_void_p]
+    L.wdmpnn_slots_split.argtypes = [POINTER(WdSlots), c_void_p]
     L.wdmpnn_ensemble_add.argtypes = [POINTER(WdEnsembleAdd), c_void_p]
     L.wdmpnn_ensemble_sid.argtypes = [POINTER(WdEnsembleSid), c_void_p]
     L.wdmpnn_head_stack_latent.argtypes = [POINTER(WdHeadLatent), c_void_p]
@@ -380,7 +419,7 @@ def lib() -> ctypes.CDLL:
              'wdmpnn_head_spectra_predict', 'wdmpnn_join_rows', 'wdmpnn_ensemble_add', 'wdmpnn_ensemble_sid',
              'wdmpnn_eval_add', 'wdmpnn_eval_spectra', 'wdmpnn_eval_auc', 'wdmpnn_head_stack_latent',
              'wdmpnn_latent_add', 'wdmpnn_desc_join', 'wdmpnn_desc_layer', 'wdmpnn_desc_layer_backward',
-             'wdmpnn_desc_rows'):
+             'wdmpnn_desc_rows', 'wdmpnn_slots_join', 'wdmpnn_slots_split'):
         getattr(L, fn).restype = c_int
     v = L.wdmpnn_abi_version()
     if v != ABI_VERSION:

@@ -32,6 +32,10 @@ restated here:
   features appended after them unscaled; each split's rows live in one ``features.FeatureTable`` on the
   device, an epoch's shuffled order is one index upload and a step takes a slice of it, so these models
   train on the direct step and from cached encodings;
+* ``--number_of_molecules N [--mpn_shared] --extra_graphs_path G2 [.. GN]``: N molecules per row, the first N CSV
+  columns being their SMILES (the reference's default ``smiles_columns``) and ``--graphs_path`` / the extra files
+  their graphs in column order; a step's batch is a ``slots.SlotBatch``, so these models train on the direct step
+  too; the checkpoint's args hold both settings, and the prediction tools read them there;
 * MoleculeModel + initialize_weights after ``torch.manual_seed(pytorch_seed)`` (run_training.py:36,
   model.py:39), Adam (utils.py:295-310), NoamLR stepped per batch (utils.py:490-541, nn_utils.py:115-194),
   training batches reshuffled every epoch by one ``Random(seed)`` (data.py:537-587);
@@ -81,7 +85,7 @@ from typing import Dict, List, Optional
 import numpy as np
 import torch
 
-from ._native import ENSEMBLE_MAX_MODELS
+from ._native import ENSEMBLE_MAX_MODELS, MAX_SLOTS
 from .args import TrainArgs
 from .featurization import BatchMolGraph
 from .ensemble import EnsembleAccumulator, accumulate_model, make_batches, predict_ensemble
@@ -94,6 +98,7 @@ from .polymer import split_polymer_string, parse_polymer_rules
 from .spectra_utils import load_phase_mask, normalize_spectra, phase_row_mask, sid_metric, wasserstein_metric
 from .atom_descriptors import AtomDescriptorTable
 from .predict import LATENT_TYPES, device_predictions
+from .slots import SlotBatch, shares_encoder
 from .train import NoamLR, _predict_head, build_optimizer, frozen_encodings, get_loss_func, train_step
 
 
@@ -345,7 +350,8 @@ def predict(model, graphs, idx, batch_size: int, scaler: Optional[StandardScaler
     native = spectra or encodings is not None or atom_descriptors is not None
     if native and _predict_head(model) is None and atom_descriptors is None:
         raise NotImplementedError('predict: the model\'s FFN is not one the native prediction heads run')
-    batches = batch_size if encodings is not None else make_batches([graphs[i] for i in idx], batch_size)
+    batches = batch_size if encodings is not None else \
+        make_batches([graphs[i] for i in idx], batch_size, shared=shares_encoder(model))
     outs = device_predictions(model, batches, features, device_mask(spectra_mask, device) if spectra else None,
                               encodings, own_forward=not native, n_rows=len(idx), atom_descriptors=atom_descriptors)
     preds = torch.cat([out for _, out in outs]).cpu().numpy().tolist()
@@ -372,9 +378,58 @@ def read_csv(path: str):
     return header, smiles, targets
 
 
-def read_class_targets(path: str, num_classes: int) -> List[List[Optional[int]]]:
+def read_csv_molecules(path: str, number_of_molecules: int):
+    """``read_csv`` for ``number_of_molecules`` molecules per row: the first N columns are the SMILES columns (the
+    reference's default ``smiles_columns``), the rest the targets.  Returns (header, one list of N SMILES per row,
+    targets).  ``ValueError`` for a CSV of fewer than N + 1 columns."""
+    n = int(number_of_molecules)
+    with open(path) as f:
+        rows = list(csv.reader(f))
+    header, body = rows[0], [r for r in rows[1:] if r]
+    if len(header) < n + 1:
+        raise ValueError(f'{path} has {len(header)} columns: {n} SMILES columns and at least one target column are '
+                         f'needed for --number_of_molecules {n}')
+    smiles = [list(r[:n]) for r in body]
+    targets = [[float(x) if x.strip() != '' else None for x in r[n:]] for r in body]
+    return header, smiles, targets
+
+
+def check_number_of_molecules(n: int, extra_graphs_path, atom_descriptors=None) -> None:
+    """``--number_of_molecules`` in 1 .. 8 with one graph file per molecule (``--graphs_path`` for the first,
+    ``--extra_graphs_path`` for the others), and no atom descriptors with several molecules (the reference's own
+    refusal, mpn.py:249-251)."""
+    if not 1 <= n <= MAX_SLOTS:
+        raise ValueError(f'--number_of_molecules must be in 1 .. {MAX_SLOTS} (got {n})')
+    extra = list(extra_graphs_path or [])
+    if len(extra) != n - 1:
+        raise ValueError(f'--number_of_molecules {n} needs {n - 1} --extra_graphs_path file(s), the graphs of molecules '
+                         f'2 .. {n} ({len(extra)} given)')
+    if n > 1 and atom_descriptors is not None:
+        raise ValueError('Atom descriptors are currently only supported with one molecule per input (i.e., '
+                         'number_of_molecules = 1).')
+
+
+def load_molecule_graphs(graphs_path: str, extra_graphs_path, n_rows: int, smiles_rows=None, polymer: bool = False):
+    """The graphs of every row: a list of ``MolGraph`` for one molecule per row, a list of per-row tuples of N for
+    several (slot k from ``graphs_path`` for k = 0, ``extra_graphs_path[k - 1]`` otherwise).  ``ValueError`` when a
+    table does not hold one graph per CSV row.  ``polymer``: ``check_polymer_rows`` on every SMILES column against
+    its own slot's graphs (``smiles_rows``: one list of N strings per row)."""
+    paths = [graphs_path] + list(extra_graphs_path or [])
+    tables = []
+    for k, path in enumerate(paths):
+        graphs = load_graphs(path)
+        if len(graphs) != n_rows:
+            raise ValueError(f'{path} holds {len(graphs)} graphs for {n_rows} CSV rows')
+        if polymer and smiles_rows is not None:
+            check_polymer_rows([r[k] for r in smiles_rows], graphs)
+        tables.append(graphs)
+    return tables[0] if len(tables) == 1 else list(zip(*tables))
+
+
+def read_class_targets(path: str, num_classes: int, number_of_molecules: int = 1) -> List[List[Optional[int]]]:
     """The target cells of a multiclass CSV as class indices (empty = missing): every other cell must be an
-    integer in [0, num_classes), else ValueError naming the CSV row (1-based, the header being row 1)."""
+    integer in [0, num_classes), else ValueError naming the CSV row (1-based, the header being row 1).  The first
+    ``number_of_molecules`` columns hold the SMILES."""
     with open(path) as f:
         rows = list(csv.reader(f))
     out = []
@@ -382,7 +437,7 @@ def read_class_targets(path: str, num_classes: int) -> List[List[Optional[int]]]
         if not r:
             continue
         row = []
-        for col, x in enumerate(r[1:], start=2):
+        for col, x in enumerate(r[number_of_molecules:], start=number_of_molecules + 1):
             if x.strip() == '':
                 row.append(None)
                 continue
@@ -532,6 +587,11 @@ def parse_args(argv=None, spectra: bool = False) -> argparse.Namespace:
     ap = argparse.ArgumentParser(prog='chemprop_train', description=__doc__.split('\n')[0])
     ap.add_argument('--data_path', required=True)
     ap.add_argument('--graphs_path', required=True, help='pre-featurised MolGraph records, one per CSV row')
+    ap.add_argument('--number_of_molecules', type=int, default=1,
+                    help='molecules per data row (1 .. 8): the first N CSV columns hold their SMILES')
+    ap.add_argument('--mpn_shared', action='store_true', help='one encoder for every molecule of a row')
+    ap.add_argument('--extra_graphs_path', nargs='+', default=None,
+                    help='the graph files of molecules 2 .. N (--graphs_path holds molecule 1)')
     ap.add_argument('--dataset_type', default='regression',
                     choices=['regression', 'classification', 'multiclass'] + (['spectra'] if spectra else []))
     ap.add_argument('--multiclass_num_classes', type=int, default=3)
@@ -610,23 +670,30 @@ def parse_args(argv=None, spectra: bool = False) -> argparse.Namespace:
         raise ValueError('--spectra_target_floor must be greater than 0')
     check_metrics(a.dataset_type, ([a.metric] if a.metric else []) + list(a.extra_metrics))
     check_atom_descriptor_args(a.atom_descriptors, a.atom_descriptors_path)
+    check_number_of_molecules(a.number_of_molecules, a.extra_graphs_path, a.atom_descriptors)
     return a
 
 
 def run_training(a: argparse.Namespace) -> Dict[str, list]:
     os.makedirs(a.save_dir, exist_ok=True)
-    header, smiles, targets = read_csv(a.data_path)
-    graphs = load_graphs(a.graphs_path)
-    if len(graphs) != len(smiles):
-        raise ValueError(f'{a.graphs_path} holds {len(graphs)} graphs for {len(smiles)} CSV rows')
-    if a.polymer:  # every row must be a well-formed polymer string (data.py:695-703, featurization.py:335-364)
-        check_polymer_rows(smiles, graphs)
-    num_tasks = len(header) - 1
+    n_mols = int(getattr(a, 'number_of_molecules', 1))
+    mpn_shared = bool(getattr(a, 'mpn_shared', False))
+    extra_graphs = getattr(a, 'extra_graphs_path', None)
+    check_number_of_molecules(n_mols, extra_graphs, getattr(a, 'atom_descriptors', None))
+    if n_mols == 1:
+        header, smiles, targets = read_csv(a.data_path)
+        smiles_rows = [[s] for s in smiles]
+    else:
+        header, smiles_rows, targets = read_csv_molecules(a.data_path, n_mols)
+        smiles = [r[0] for r in smiles_rows]
+    # every row must be a well-formed polymer string (data.py:695-703, featurization.py:335-364)
+    graphs = load_molecule_graphs(a.graphs_path, extra_graphs, len(smiles), smiles_rows, bool(a.polymer))
+    num_tasks = len(header) - n_mols
     multiclass = a.dataset_type == 'multiclass'
     if multiclass:  # class indices, checked here: a bad one must not reach the loss on the device
         if a.multiclass_num_classes < 2:
             raise ValueError('--multiclass_num_classes must be at least 2')
-        targets = read_class_targets(a.data_path, a.multiclass_num_classes)
+        targets = read_class_targets(a.data_path, a.multiclass_num_classes, n_mols)
     spectra = a.dataset_type == 'spectra'
     phase_features = phase_mask = row_mask = None
     if spectra:  # run_training.py:146-157: every split's targets normalised once, per row, under its phase mask
@@ -683,7 +750,8 @@ def run_training(a: argparse.Namespace) -> Dict[str, list]:
                      atom_descriptors_size=0 if descriptors is None else int(descriptors[0].shape[1]),
                      atom_descriptors_path=None if descriptors is None else a.atom_descriptors_path,
                      no_atom_descriptor_scaling=bool(getattr(a, 'no_atom_descriptor_scaling', False)),
-                     polymer=bool(a.polymer), ensemble_size=a.ensemble_size, task_names=list(header[1:]),
+                     polymer=bool(a.polymer), ensemble_size=a.ensemble_size, task_names=list(header[n_mols:]),
+                     number_of_molecules=n_mols, mpn_shared=mpn_shared,
                      device_metrics=bool(getattr(a, 'device_metrics', False)))
     torch.manual_seed(a.pytorch_seed)
     scaler = None
@@ -734,7 +802,8 @@ def run_training(a: argparse.Namespace) -> Dict[str, list]:
             batches = a.batch_size
         else:
             if name not in split_batches:
-                split_batches[name] = make_batches([graphs[i] for i in split_idx[name]], a.batch_size)
+                split_batches[name] = make_batches([graphs[i] for i in split_idx[name]], a.batch_size,
+                                                   shared=mpn_shared)
             batches = split_batches[name]
         return evaluate(model, batches, table, metrics, scaler, tables and tables[name], split_masks[name],
                         enc_cache and enc_cache[name], evaluator=ev,
@@ -755,6 +824,7 @@ def run_training(a: argparse.Namespace) -> Dict[str, list]:
         # per split, the steps and the per-epoch scores then run the head alone (train.frozen_encodings)
         enc_cache = None
         if args.frzn_encoder and a.dropout == 0 and not a.no_encoding_cache and descriptors is None and \
+                n_mols == 1 and \
                 _predict_head(model.eval()) is not None:
             enc_cache = {name: frozen_encodings(model, [graphs[i] for i in idx], a.batch_size)
                          for name, idx in splits}
@@ -784,8 +854,12 @@ def run_training(a: argparse.Namespace) -> Dict[str, list]:
                                           a.dataset_type, features_batch=feats, grad_clip=a.grad_clip,
                                           encodings=rows)
                     else:
-                        g = BatchMolGraph([graphs[train_idx[p]] for p in pos])
-                        loss = train_step(model, [g], batch_targets(pos), loss_func, optimizer, scheduler,
+                        if n_mols == 1:
+                            g = [BatchMolGraph([graphs[train_idx[p]] for p in pos])]
+                        else:  # (one BatchMolGraph per slot, and the merged one for a shared encoder)
+                            g = SlotBatch([[graphs[train_idx[p]][k] for p in pos] for k in range(n_mols)],
+                                          shared=mpn_shared)
+                        loss = train_step(model, g, batch_targets(pos), loss_func, optimizer, scheduler,
                                           a.dataset_type, features_batch=feats, grad_clip=a.grad_clip,
                                           atom_descriptors_batch=None if dindex is None else
                                           dindex[s:s + a.batch_size])
@@ -827,7 +901,7 @@ def run_training(a: argparse.Namespace) -> Dict[str, list]:
         # into one accumulator on the device, and the top-level scores and predictions are the ensemble's
         width = num_tasks * (a.multiclass_num_classes if multiclass else 1)
         acc = EnsembleAccumulator(len(test_idx), width, device, keep=True, n_models=a.ensemble_size)
-        test_batches = make_batches([graphs[i] for i in test_idx], a.batch_size)
+        test_batches = make_batches([graphs[i] for i in test_idx], a.batch_size, shared=mpn_shared)
         test_mask = device_mask(row_mask, device, test_idx)
         best_epoch = []
         for k in range(a.ensemble_size):
@@ -854,18 +928,18 @@ def run_training(a: argparse.Namespace) -> Dict[str, list]:
     with open(os.path.join(a.save_dir, 'test_scores.csv'), 'w', newline='') as f:
         w = csv.writer(f)
         w.writerow(['Task'] + [f'Mean {m}' for m in metrics])
-        for t, name in enumerate(['spectra'] if spectra else header[1:]):  # (cross_validate.py:158-159)
+        for t, name in enumerate(['spectra'] if spectra else header[n_mols:]):  # (cross_validate.py:158-159)
             w.writerow([name] + [scores[m][t] if t < len(scores[m]) else '' for m in metrics])
     with open(os.path.join(a.save_dir, 'test_preds.csv'), 'w', newline='') as f:
         w = csv.writer(f)
         if multiclass:  # one column per class (make_predictions.py:213)
-            w.writerow(header[:1] + [f'{name}_class_{k}' for name in header[1:]
-                                     for k in range(a.multiclass_num_classes)])
+            w.writerow(header[:n_mols] + [f'{name}_class_{k}' for name in header[n_mols:]
+                                          for k in range(a.multiclass_num_classes)])
         else:
             w.writerow(header)
         for i, p in zip(test_idx, test_preds):
-            w.writerow([smiles[i]] + ([x for task in p for x in task] if multiclass else
-                                      ['' if x is None else x for x in p]))
+            w.writerow(smiles_rows[i] + ([x for task in p for x in task] if multiclass else
+                                         ['' if x is None else x for x in p]))
     with open(os.path.join(a.save_dir, 'split_indices.json'), 'w') as f:
         json.dump({'train': train_idx, 'val': val_idx, 'test': test_idx, 'best_epoch': best_epoch}, f)
     return scores
@@ -892,6 +966,8 @@ def _prediction_parser(prog: str, description: str) -> argparse.ArgumentParser:
     ap = argparse.ArgumentParser(prog=prog, description=description)
     ap.add_argument('--test_path', required=True, help='CSV with a header; the first column holds the SMILES')
     ap.add_argument('--graphs_path', required=True, help='pre-featurised MolGraph records, one per CSV row')
+    ap.add_argument('--extra_graphs_path', nargs='+', default=None,
+                    help='the graph files of molecules 2 .. N for checkpoints trained with --number_of_molecules N')
     ap.add_argument('--preds_path', required=True, help='the CSV to write')
     ap.add_argument('--checkpoint_dir', default=None,
                     help='every best_model.pt below this directory if there is one, else every .pt file')
@@ -990,7 +1066,9 @@ def update_prediction_args(paths: List[str]) -> Dict[str, object]:
                 names = [f'task_{i}' for i in range(num_tasks)]
             out = {'dataset_type': dataset_type, 'num_tasks': num_tasks, 'multiclass_num_classes': classes,
                    'task_names': list(names), 'spectra_phase_mask_path': t.get('spectra_phase_mask_path'),
-                   'polymer': bool(t.get('polymer', False)), 'width': num_tasks * classes}
+                   'polymer': bool(t.get('polymer', False)), 'width': num_tasks * classes,
+                   'number_of_molecules': int(t.get('number_of_molecules', 1)),
+                   'mpn_shared': bool(t.get('mpn_shared', False))}
         elif dataset_type != out['dataset_type'] or num_tasks * classes != out['width']:
             raise ValueError(f'{path} ({dataset_type}, {num_tasks * classes} outputs) does not fit the ensemble\'s '
                              f'first checkpoint {paths[0]} ({out["dataset_type"]}, {out["width"]} outputs)')
@@ -1001,10 +1079,10 @@ def update_prediction_args(paths: List[str]) -> Dict[str, object]:
 
 def write_predictions(path: str, header: List[str], rows: List[List[str]], task_names: List[str], mean,
                       dataset_type: str = 'regression', num_classes: int = 1, spread=None, individual=None,
-                      drop_extra_columns: bool = False) -> List[str]:
+                      drop_extra_columns: bool = False, smiles_columns: int = 1) -> List[str]:
     """The predictions CSV (make_predictions.py:211-263); returns its header.  ``header`` / ``rows``: the input
     CSV; ``mean`` ``[N][W]``, ``spread`` ``[N][W]`` (spectra: the pairwise SID ``[N]``) or None, ``individual``
-    ``[M][N][W]`` or None.  Columns: the input row's (``drop_extra_columns``: its first, the SMILES), one per task
+    ``[M][N][W]`` or None.  Columns: the input row's (``drop_extra_columns``: its first ``smiles_columns``, the SMILES), one per task
     (multiclass: ``<task>_class_<i>``), then ``<task>_model_<k>`` task by task, then ``<task>_epi_unc`` per task
     (spectra: one ``epi_unc``); a prediction column named like a kept input column (the target column of a
     training CSV) replaces it where it stands, as the reference's per-row dict does.  NaN cells (a spectrum's excluded positions) are written empty, as
@@ -1020,7 +1098,7 @@ def write_predictions(path: str, header: List[str], rows: List[List[str]], task_
         individual = np.asarray(individual, dtype=np.float64).reshape(-1, len(mean), len(names))
     if spread is not None:
         spread = np.asarray(spread, dtype=np.float64).reshape((len(mean),) if spectra else mean.shape)
-    keep = 1 if drop_extra_columns else len(header)
+    keep = smiles_columns if drop_extra_columns else len(header)
     added = list(names)
     if individual is not None:
         added += [f'{n}_model_{k}' for n in names for k in range(len(individual))]
@@ -1066,6 +1144,17 @@ def check_polymer_rows(smiles: List[str], graphs) -> None:
                 raise ValueError(f'graph degree_of_polym {g.degree_of_polym} != 1 + log10(Xn) = {deg} for {s}')
 
 
+def _prediction_graphs(a: argparse.Namespace, info: Dict[str, object], header: List[str], rows: List[List[str]]):
+    """The graphs of a prediction run's rows (``load_molecule_graphs``): the checkpoints' ``number_of_molecules``
+    decides how many SMILES columns the CSV needs and how many ``--extra_graphs_path`` files."""
+    n_mols = int(info['number_of_molecules'])
+    check_number_of_molecules(n_mols, getattr(a, 'extra_graphs_path', None))
+    if len(header) < n_mols:
+        raise ValueError(f'{a.test_path} has {len(header)} columns for checkpoints of {n_mols} molecules per row')
+    return load_molecule_graphs(a.graphs_path, getattr(a, 'extra_graphs_path', None), len(rows),
+                                [r[:n_mols] for r in rows], bool(info['polymer']))
+
+
 def _prediction_descriptors(a: argparse.Namespace, paths: List[str], graphs):
     """The raw atom descriptors of a prediction run, or None: ``--atom_descriptors_path`` must be given exactly
     when the checkpoints were trained with ``--atom_descriptors descriptor`` (their stored args say)."""
@@ -1101,11 +1190,7 @@ def make_predictions(a: argparse.Namespace):
     with open(a.test_path) as f:
         table = list(csv.reader(f))
     header, rows = table[0], [r for r in table[1:] if r]
-    graphs = load_graphs(a.graphs_path)
-    if len(graphs) != len(rows):
-        raise ValueError(f'{a.graphs_path} holds {len(graphs)} graphs for {len(rows)} CSV rows')
-    if info['polymer']:
-        check_polymer_rows([r[0] for r in rows], graphs)
+    graphs = _prediction_graphs(a, info, header, rows)
     features = load_input_features(a.features_path, len(rows)) if a.features_path else None
     phase_features = phase_mask = None
     if a.phase_features_path is not None:
@@ -1124,7 +1209,8 @@ def make_predictions(a: argparse.Namespace):
             os.makedirs(parent, exist_ok=True)
         np.save(a.graph_embeddings_path, embeddings[0])
     write_predictions(a.preds_path, header, rows, info['task_names'], mean, info['dataset_type'],
-                      info['multiclass_num_classes'], spread, individual, a.drop_extra_columns)
+                      info['multiclass_num_classes'], spread, individual, a.drop_extra_columns,
+                      smiles_columns=info['number_of_molecules'])
     return mean
 
 
@@ -1141,7 +1227,8 @@ def write_fingerprints(path: str, smiles_header: str, smiles: List[str], fingerp
     fp = np.asarray(fingerprints, dtype=np.float64)
     if fp.ndim != 3 or len(fp) != len(smiles):
         raise ValueError(f'fingerprints of shape {fp.shape} for {len(smiles)} rows ([N][fp][M] expected)')
-    header = [smiles_header] + fingerprint_columns(fp.shape[1], fp.shape[2])
+    several = isinstance(smiles_header, (list, tuple))  # (rows of several molecules: every SMILES column in front)
+    header = (list(smiles_header) if several else [smiles_header]) + fingerprint_columns(fp.shape[1], fp.shape[2])
     parent = os.path.dirname(path)
     if parent:
         os.makedirs(parent, exist_ok=True)
@@ -1149,7 +1236,7 @@ def write_fingerprints(path: str, smiles_header: str, smiles: List[str], fingerp
         w = csv.writer(f)
         w.writerow(header)
         for s, row in zip(smiles, fp.reshape(len(fp), -1)):
-            w.writerow([s] + [str(v) for v in row])
+            w.writerow((list(s) if several else [s]) + [str(v) for v in row])
     return header
 
 
@@ -1164,11 +1251,7 @@ def make_fingerprints(a: argparse.Namespace) -> np.ndarray:
     with open(a.test_path) as f:
         table = list(csv.reader(f))
     header, rows = table[0], [r for r in table[1:] if r]
-    graphs = load_graphs(a.graphs_path)
-    if len(graphs) != len(rows):
-        raise ValueError(f'{a.graphs_path} holds {len(graphs)} graphs for {len(rows)} CSV rows')
-    if info['polymer']:
-        check_polymer_rows([r[0] for r in rows], graphs)
+    graphs = _prediction_graphs(a, info, header, rows)
     features = load_input_features(a.features_path, len(rows)) if a.features_path else None
     phase_features = None
     if a.phase_features_path is not None:
@@ -1178,7 +1261,9 @@ def make_fingerprints(a: argparse.Namespace) -> np.ndarray:
                               device=torch.device('cuda', a.gpu),
                               atom_descriptors=_prediction_descriptors(a, paths, graphs),
                               atom_descriptor_scaling=_descriptor_scaling_of(paths))
-    write_fingerprints(a.preds_path, header[0], [r[0] for r in rows], fp)
+    n_mols = info['number_of_molecules']
+    write_fingerprints(a.preds_path, header[0] if n_mols == 1 else header[:n_mols],
+                       [r[0] if n_mols == 1 else list(r[:n_mols]) for r in rows], fp)
     return fp
 
 

@@ -116,10 +116,19 @@ class EnsembleAccumulator(PredictionSink):
         return out
 
 
-def make_batches(graphs: Sequence, batch_size: int) -> list:
-    """The data set as ``BatchMolGraph`` s of ``batch_size`` molecules, in order."""
+def make_batches(graphs: Sequence, batch_size: int, shared: bool = False) -> list:
+    """The data set as ``BatchMolGraph`` s of ``batch_size`` molecules, in order.  Rows given as tuples or lists of
+    N ``MolGraph`` s (a model of N molecules per input) become ``slots.SlotBatch`` es, with their merged graph
+    when ``shared`` (a model with ``mpn_shared``)."""
     if batch_size < 1:
         raise ValueError('batch_size must be at least 1')
+    if len(graphs) and isinstance(graphs[0], (tuple, list)):
+        from .slots import SlotBatch
+        n = len(graphs[0])
+        if any(not isinstance(r, (tuple, list)) or len(r) != n for r in graphs):
+            raise ValueError(f'make_batches: every row needs {n} molecules, as the first has')
+        return [SlotBatch([[r[k] for r in graphs[s:s + batch_size]] for k in range(n)], shared=shared)
+                for s in range(0, len(graphs), batch_size)]
     return [BatchMolGraph(list(graphs[s:s + batch_size])) for s in range(0, len(graphs), batch_size)]
 
 
@@ -239,7 +248,7 @@ def predict_ensemble(checkpoints_or_models, graphs: Sequence, batch_size: int, f
     device = torch.device('cuda', 0) if device is None else torch.device(device)
     if n_models is None and hasattr(checkpoints_or_models, '__len__'):
         n_models = len(checkpoints_or_models)
-    batches = make_batches(graphs, batch_size)
+    batches = None
     n = len(graphs)
     acc = spectra = emb_acc = None
     row_mask = None
@@ -247,6 +256,9 @@ def predict_ensemble(checkpoints_or_models, graphs: Sequence, batch_size: int, f
     for k, item in enumerate(checkpoints_or_models):
         model, data_scaler, features_scaler = _open_model(item, device)
         model.eval()
+        if batches is None:  # (rows of several molecules: with the merged graphs a shared encoder runs once over)
+            from .slots import shares_encoder
+            batches = make_batches(graphs, batch_size, shared=shares_encoder(model))
         is_spectra = bool(getattr(model, 'spectra', False))
         width = int([m for m in model.ffn if isinstance(m, torch.nn.Linear)][-1].out_features)
         if acc is None:

@@ -17,6 +17,7 @@ import torch
 
 from . import _native
 from .ensemble import _open_model, make_batches, model_atom_descriptors, model_features
+from .slots import shares_encoder
 from .features import FeatureTable
 from .predict import LATENT_TYPES, PredictionSink, device_predictions
 
@@ -146,12 +147,14 @@ def molecule_fingerprint(checkpoints_or_models, graphs: Sequence, batch_size: in
     items = list(checkpoints_or_models)
     if not items:
         raise ValueError('molecule_fingerprint: no model given')
-    batches = make_batches(graphs, batch_size)
+    batches = None
     n = len(graphs)
     acc = None
     for k, item in enumerate(items):
         model, _, features_scaler = _open_model(item, device)
         model.eval()
+        if batches is None:  # (rows of several molecules: with the merged graphs a shared encoder runs once over)
+            batches = make_batches(graphs, batch_size, shared=shares_encoder(model))
         width = fingerprint_width(model, fingerprint_type)
         if acc is None:
             acc = LatentAccumulator(n, width, device, n_models=len(items))

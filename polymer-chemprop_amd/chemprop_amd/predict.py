@@ -16,7 +16,9 @@ import numpy as np
 import torch
 
 from .atom_descriptors import AtomDescriptorTable
+from ._native import MAX_SLOTS
 from .features import FeatureTable, join_features
+from .slots import join_slots, merged_graph
 
 
 class PredictionSink:
@@ -87,6 +89,26 @@ def _encode_alone(mpn, batch) -> torch.Tensor:
     return torch.cat([enc(ba) for enc, ba in zip(mpn.encoder, _molecules(batch))], dim=1)
 
 
+def _encode_slots(mpn, group) -> list:
+    """The encodings of a group of batches of a model of N molecules per input, per batch the list ``join_slots``
+    takes.  Distinct encoders: one ``forward_many`` per slot encoder over that slot's graphs of the group.  A
+    shared encoder: one ``forward_many`` over the batches' merged graphs (``slots.SlotBatch(shared=True)``: per
+    batch one slot-major ``[N B][H]`` tensor), or over the flattened slot graphs of plain lists."""
+    n = len(mpn.encoder)
+    mols = [_molecules(b) for b in group]
+    if any(len(m) != n for m in mols):
+        raise ValueError(f'a batch of {[len(m) for m in mols]} molecule graphs for a model of {n} molecules per input')
+    enc = mpn.encoder[0]
+    if all(e is enc for e in mpn.encoder):
+        merged = [merged_graph(b) for b in group]
+        if all(g is not None for g in merged):
+            return [[o] for o in enc.forward_many(merged)]
+        outs = enc.forward_many([g for m in mols for g in m])
+        return [[o.contiguous() for o in outs[k * n:(k + 1) * n]] for k in range(len(mols))]
+    per_slot = [mpn.encoder[k].forward_many([m[k] for m in mols]) for k in range(n)]
+    return [[per_slot[k][j].contiguous() for k in range(n)] for j in range(len(mols))]
+
+
 LATENT_TYPES = ('MPN', 'last_FFN')
 
 
@@ -102,7 +124,10 @@ def device_predictions(model, batches, features: Optional[FeatureTable] = None,
     ``[rows][T]`` on the device (ignored for other models): its predictions are normalised per row, the excluded
     positions NaN.  The batches run in groups of up to eight through ``forward_many``, then per batch
     ``join_features`` and the native prediction head; a model whose FFN the native heads refuse runs its own
-    forward (``_fallback_predict``).  A batch of a model of several molecules is the list of its ``BatchMolGraph`` s.
+    forward (``_fallback_predict``).  A batch of a model of several molecules is the list of its ``BatchMolGraph`` s
+    (or a ``slots.SlotBatch``): per group one ``forward_many`` per slot encoder (a shared encoder: one, over the
+    batches' merged graphs or the flattened slot graphs), then per batch one ``wdmpnn_slots_join`` launch builds the
+    FFN input from every slot's encoding and the feature rows.
 
     ``encodings``: the rows' cached ``train.frozen_encodings``; the head runs straight from them, in the batch
     sizes of ``batches`` (which may then be a plain batch size as well; ``NotImplementedError`` without a native
@@ -178,12 +203,16 @@ def device_predictions(model, batches, features: Optional[FeatureTable] = None,
         raise NotImplementedError('predictions from encodings: the model\'s FFN is not one the native heads run')
     findex = features.index(range(n)) if features is not None and n else None
     dindex = atom_descriptors.index(range(n)) if atom_descriptors is not None and n else None
-    many = encodings is None and (head is not None or latent == 'MPN') and not mpn.features_only and \
-        len(mpn.encoder) == 1 and (mpn.atom_descriptors is None or
-                                   (dindex is not None and mpn.encoder[0]._after_readout()))
+    n_enc = 0 if mpn.features_only else len(mpn.encoder)
+    one_ok = n_enc == 1 and (mpn.atom_descriptors is None or (dindex is not None and mpn.encoder[0]._after_readout()))
+    slots_ok = 1 < n_enc <= MAX_SLOTS and mpn.atom_descriptors is None
+    many = encodings is None and (head is not None or latent == 'MPN') and (one_ok or slots_ok)
     for g0 in range(0, len(sizes), 8):
-        embs = mpn.encoder[0].forward_many([_molecules(b)[0] for b in batches[g0:g0 + 8]]) if many else \
-            [None] * len(sizes[g0:g0 + 8])
+        if many and n_enc > 1:
+            embs = _encode_slots(mpn, batches[g0:g0 + 8])
+        else:
+            embs = mpn.encoder[0].forward_many([_molecules(b)[0] for b in batches[g0:g0 + 8]]) if many else \
+                [None] * len(sizes[g0:g0 + 8])
         for j, emb in enumerate(embs, g0):
             r0, r1 = starts[j], starts[j + 1]
             feats = None if findex is None else findex[r0:r1]
@@ -200,6 +229,8 @@ def device_predictions(model, batches, features: Optional[FeatureTable] = None,
                 emb = encodings[r0:r1]
             if emb is None:
                 x = _encode_alone(mpn, batches[j]) if alone else mpn(_molecules(batches[j]), feats, desc)
+            elif n_enc > 1 and encodings is None:  # (one launch: every slot's encoding and the feature rows into the FFN input)
+                x = join_slots(emb, r1 - r0, feats)
             else:
                 if desc is not None:  # (atom_descriptors_layer after the readout: one join, one layer launch)
                     emb = mpn.encoder[0].apply_descriptor_layer(_molecules(batches[j])[0], emb, desc)

@@ -106,15 +106,23 @@ class HipAdam(Optimizer):
         super().__init__(params, dict(lr=lr, betas=tuple(betas), eps=eps, weight_decay=weight_decay))
         self.decoupled = bool(decoupled)
         self._tables = {}  # parameter pointers of one launch -> its ctypes tensor table
-        self._repack = None  # (encoder, its training pack) for the next step (train_step's direct path)
+        self._repack = None  # [(encoder, its training pack)] for the next step (train_step's direct path)
 
-    def repack_next(self, encoder) -> None:
-        """Have the next :meth:`step` also rewrite ``encoder``'s training pack (the packed weight copies its
-        direct training forward reads) from the updated weights, instead of a pack launch before the next
-        forward (``wdmpnn_adam_step_repack``).  No effect unless the encoder's six weights are updated in
-        one call of that step."""
-        tp = encoder.__dict__.get('_train_pack')
-        self._repack = (encoder, tp) if tp is not None and ADAM_REPACK else None
+    def repack_next(self, *encoders) -> None:
+        """Have the next :meth:`step` also rewrite every given encoder's training pack (the packed weight copies
+        its direct training forward reads) from the updated weights, instead of a pack launch before the next
+        forward (``wdmpnn_adam_step_repack``).  No effect for an encoder whose six weights are not updated in
+        one call of that step.  With several encoders (a model of several molecules per input) the step's tensor
+        table is split: one ``wdmpnn_adam_step_repack`` call per encoder over that encoder's weights and one
+        ``wdmpnn_adam_step`` call for the rest (Adam is element-wise: the values do not depend on the split).  A
+        shared encoder is one encoder."""
+        pend = []
+        if ADAM_REPACK:
+            for enc in encoders:
+                tp = enc.__dict__.get('_train_pack')
+                if tp is not None and all(tp is not q for _, q in pend):
+                    pend.append((enc, tp))
+        self._repack = pend or None
 
     @torch.no_grad()
     def step(self, closure=None):
@@ -159,18 +167,56 @@ class HipAdam(Optimizer):
                 h = _native.WdAdamHyper(float(group['lr']), float(group['betas'][0]), float(group['betas'][1]),
                                         float(group['eps']), float(group['weight_decay']), step, int(self.decoupled))
                 sid = _native.current_stream(sub[0][0].device)
-                if rp is not None and rp[1]['ptrs'] <= frozenset(key) and rp[1]['key'][-1] == sid:
-                    enc, tp = rp
-                    rp = None
-                    rc = L.wdmpnn_adam_step_repack(tab, len(sub), ctypes.byref(h), ctypes.byref(tp['gs']),
-                                                   ctypes.byref(tp['p']), ctypes.byref(tp['cfg']), tp['buf'].data_ptr(),
-                                                   tp['buf'].numel(), sid)
-                    if rc != _native.ERR_UNSUPPORTED:
-                        _native.check(rc, 'adam step + repack')
-                        enc._repacked_by_optimizer(tp)
+                if rp:
+                    ptrs = frozenset(key)
+                    now = [(e, tp) for e, tp in rp if tp['ptrs'] <= ptrs and tp['key'][-1] == sid]
+                    if len(now) > 1:
+                        rp = [q for q in rp if all(q is not r for r in now)]
+                        self._step_split(L, tab, sub, key, h, now, sid)
                         continue
+                    if now:
+                        enc, tp = now[0]
+                        rp = [q for q in rp if q is not now[0]]
+                        rc = L.wdmpnn_adam_step_repack(tab, len(sub), ctypes.byref(h), ctypes.byref(tp['gs']),
+                                                       ctypes.byref(tp['p']), ctypes.byref(tp['cfg']),
+                                                       tp['buf'].data_ptr(), tp['buf'].numel(), sid)
+                        if rc != _native.ERR_UNSUPPORTED:
+                            _native.check(rc, 'adam step + repack')
+                            enc._repacked_by_optimizer(tp)
+                            continue
                 _native.check(L.wdmpnn_adam_step(tab, len(sub), ctypes.byref(h), sid), 'adam step')
         return loss
+
+    def _step_split(self, L, tab, sub, key, h, now, sid) -> None:
+        """One step-count group with several encoders to repack: a sub-table and a ``wdmpnn_adam_step_repack`` call
+        per encoder, one ``wdmpnn_adam_step`` call for the remaining tensors.  The sub-tables are cached next to
+        the group's table (their gradient pointers are copied from it every step)."""
+        skey = (key, tuple(tuple(sorted(tp['ptrs'])) for _, tp in now))
+        parts = self._tables.get(skey)
+        if parts is None:
+            taken, parts = set(), []
+            for _, tp in now:
+                rows = [k for k, (p, _) in enumerate(sub) if p.data_ptr() in tp['ptrs'] and k not in taken]
+                taken.update(rows)
+                parts.append(rows)
+            parts.append([k for k in range(len(sub)) if k not in taken])
+            parts = [(rows, (_native.WdAdamTensor * max(len(rows), 1))()) for rows in parts]
+            self._tables[skey] = parts
+        for rows, t in parts:
+            for j, k in enumerate(rows):
+                t[j] = tab[k]
+        for (enc, tp), (rows, t) in zip(now, parts):
+            rc = L.wdmpnn_adam_step_repack(t, len(rows), ctypes.byref(h), ctypes.byref(tp['gs']), ctypes.byref(tp['p']),
+                                           ctypes.byref(tp['cfg']), tp['buf'].data_ptr(), tp['buf'].numel(), sid)
+            if rc == _native.ERR_UNSUPPORTED:  # (this encoder packs before its next forward)
+                rc = L.wdmpnn_adam_step(t, len(rows), ctypes.byref(h), sid)
+                _native.check(rc, 'adam step')
+                continue
+            _native.check(rc, 'adam step + repack')
+            enc._repacked_by_optimizer(tp)
+        rows, t = parts[-1]
+        if rows:
+            _native.check(L.wdmpnn_adam_step(t, len(rows), ctypes.byref(h), sid), 'adam step')
 
     def load_state_dict(self, state_dict) -> None:
         super().load_state_dict(state_dict)
@@ -1031,6 +1077,36 @@ def frozen_encodings(model: nn.Module, graphs: Sequence, batch_size: int) -> tor
     return torch.cat(outs, dim=0)
 
 
+def _direct_head(out, head, target_batch, target_weights, data_weights, grad_of: Callable, want_dx: bool = True):
+    """The head's part of a direct step on its input ``out`` ``[B][F]``: the loss table, the fused head (loss, dx
+    and the head's gradients into ``grad_of``'s buffers).  Returns (loss, dx)."""
+    linears, _, _, kind, n_classes, spectra = _head_parts(head)
+    spectra = spectra is not None
+    nc = n_classes if kind == 2 and not spectra else 0  # (multiclass: _loss_table checks the class indices on the host)
+    # the loss table read by the head kernel straight from its pinned host buffer (no copy launch in the
+    # step: the copy kernel and its gap were ~10 us, profiles/round4_train_kernel_trace_v1.txt)
+    # (the spectra row kernel reads its table rows in several passes: a device copy, not the pinned buffer)
+    zc = None
+    if not spectra:
+        zc, n_t, n_mask, tshape = _loss_table(target_batch, target_weights, data_weights, out.device, zero_copy=True,
+                                              num_classes=nc)
+    if zc is None:
+        table, n_t, n_mask = _loss_table(target_batch, target_weights, data_weights, out.device, num_classes=nc,
+                                         spectra=spectra)
+        tab_ptr, tshape = table.data_ptr(), tuple(table.shape)
+    else:
+        tab_ptr = zc[0]
+    inv_n = _check_head_batch(linears, n_classes, n_t, n_mask, tshape[0], out)
+    dev = out.device
+    if isinstance(head, _StackHead):
+        loss, dx, _ = _run_head_stack(out, head, tab_ptr, tshape[1], inv_n, _head_seed(head), grad_of, want_dx)
+    else:
+        loss, dx, _ = _run_head_two(out, head, tab_ptr, tshape[1], inv_n, _grad_buffer)
+    if zc is not None:
+        zc[1].record(torch.cuda.current_stream(dev))  # (the pinned buffer's last reader)
+    return loss, dx
+
+
 def _direct_step(model, enc, graph, head, target_batch, target_weights, data_weights, bucket=None,
                  plan: _FrozenPlan = None, encodings: torch.Tensor = None, features=None,
                  descriptors=None) -> torch.Tensor:
@@ -1053,9 +1129,6 @@ def _direct_step(model, enc, graph, head, target_batch, target_weights, data_wei
     without descriptors, then ``wdmpnn_desc_join`` and ``wdmpnn_desc_layer`` give the encoding ``[B][H + d]`` the
     rest of the step sees; after the head, one ``wdmpnn_desc_layer_backward`` launch writes the layer's two
     gradients and the encoder backward's input."""
-    linears, _, _, kind, n_classes, spectra = _head_parts(head)
-    spectra = spectra is not None
-    nc = n_classes if kind == 2 and not spectra else 0  # (multiclass: _loss_table checks the class indices on the host)
     enc_frozen = plan is not None and plan.enc_frozen
     if encodings is not None:
         out = encodings
@@ -1074,28 +1147,9 @@ def _direct_step(model, enc, graph, head, target_batch, target_weights, data_wei
     n_emb = out.shape[1] if out.dim() == 2 else 0
     if features is not None:
         out = join_features(out, features)  # (x: the head's input from here on)
-    # the loss table read by the head kernel straight from its pinned host buffer (no copy launch in the
-    # step: the copy kernel and its gap were ~10 us, profiles/round4_train_kernel_trace_v1.txt)
-    # (the spectra row kernel reads its table rows in several passes: a device copy, not the pinned buffer)
-    zc = None
-    if not spectra:
-        zc, n_t, n_mask, tshape = _loss_table(target_batch, target_weights, data_weights, out.device, zero_copy=True,
-                                              num_classes=nc)
-    if zc is None:
-        table, n_t, n_mask = _loss_table(target_batch, target_weights, data_weights, out.device, num_classes=nc,
-                                         spectra=spectra)
-        tab_ptr, tshape = table.data_ptr(), tuple(table.shape)
-    else:
-        tab_ptr = zc[0]
-    inv_n = _check_head_batch(linears, n_classes, n_t, n_mask, tshape[0], out)
+    loss, dx = _direct_head(out, head, target_batch, target_weights, data_weights,
+                            _grad_buffer if plan is None else plan.grad_of, not enc_frozen)
     dev = out.device
-    if isinstance(head, _StackHead):
-        loss, dx, _ = _run_head_stack(out, head, tab_ptr, tshape[1], inv_n, _head_seed(head),
-                                      _grad_buffer if plan is None else plan.grad_of, not enc_frozen)
-    else:
-        loss, dx, _ = _run_head_two(out, head, tab_ptr, tshape[1], inv_n, _grad_buffer)
-    if zc is not None:
-        zc[1].record(torch.cuda.current_stream(dev))  # (the pinned buffer's last reader)
     if bucket is not None:  # the head's gradients are enqueued: their all-reduce overlaps the encoder backward
         bucket.start_early()
     if plan is not None:
@@ -1111,6 +1165,108 @@ def _direct_step(model, enc, graph, head, target_batch, target_weights, data_wei
                                    None if lin.bias is None else _grad_buffer(lin.bias), dx,
                                    _native.current_stream(dev))
         enc._train_backward(state, dx, {n: _grad_buffer(p) for n, p in enc._direct_names()})
+    return loss
+
+
+class _SlotPlan:
+    """A model of several molecules per input the direct step runs (``_direct_slots``): its distinct encoders (one
+    for ``mpn_shared``), the number of slots and whether one encoder serves all of them."""
+    __slots__ = ('encoders', 'n', 'shared')
+
+    def __init__(self, encoders, n, shared):
+        self.encoders, self.n, self.shared = encoders, n, shared
+
+
+def _all_trainable_but(mod: nn.Module, skip: set, ids: list) -> bool:
+    """``_all_trainable`` with several parameters left out (``skip``: their ids)."""
+    for p in mod._parameters.values():
+        if p is not None and id(p) not in skip:
+            if not p.requires_grad:
+                return False
+            ids.append(id(p))
+    for m in mod._modules.values():
+        if m is not None and not _all_trainable_but(m, skip, ids):
+            return False
+    return True
+
+
+def _direct_slots(model: nn.Module, mol_batch, features_batch, head, atom_descriptors_batch=None):
+    """``_direct_encoder`` for ``number_of_molecules > 1``: the :class:`_SlotPlan` when the step can skip autograd,
+    else None.  The same conditions on every encoder (plain ``MPNEncoder``, depth >= 2, no atom messages, features
+    only as device rows, every parameter trainable and written by the step), no atom descriptors, one
+    ``BatchMolGraph`` per slot.  A shared encoder (``mpn_shared``) also needs the batch's merged graph
+    (``slots.SlotBatch(shared=True)``) and no encoder dropout: the one forward over the merged batch would draw
+    one seed where the per-slot path draws N."""
+    from .model import MoleculeModel
+    from .mpn import MPNEncoder
+    from .slots import merged_graph
+    if not isinstance(model, MoleculeModel) or type(model).forward is not MoleculeModel.forward:
+        return None
+    mpn = model.encoder
+    if mpn.features_only or len(mpn.encoder) < 2 or len(mpn.encoder) > _native.MAX_SLOTS or \
+            not _features_ok(mpn, features_batch) or mpn.atom_descriptors or atom_descriptors_batch is not None or \
+            not isinstance(mol_batch, (list, tuple)) or len(mol_batch) != len(mpn.encoder):
+        return None
+    encoders = []
+    for enc, g in zip(mpn.encoder, mol_batch):
+        if type(enc) is not MPNEncoder or enc.depth < 2 or enc.atom_messages or \
+                hasattr(enc, 'atom_descriptors_layer') or type(g).__name__ != 'BatchMolGraph' or \
+                enc.hidden_size != mpn.encoder[0].hidden_size:
+            return None
+        if all(enc is not e for e in encoders):
+            encoders.append(enc)
+    n = len(mpn.encoder)
+    shared = len(encoders) == 1
+    if not shared and len(encoders) != n:
+        return None
+    if shared and (encoders[0].dropout > 0 or merged_graph(mol_batch) is None):
+        return None
+    ids = []
+    if not _all_trainable_but(model, {id(e.cached_zero_vector) for e in encoders}, ids):
+        return None
+    linears, _, slope, _, _, _ = _head_parts(head)
+    head_params = [t for l in linears for t in (l.weight, l.bias)] + [slope]
+    written = {id(t) for e in encoders for _, t in e._direct_names()} | {id(t) for t in head_params if t is not None}
+    if set(ids) != written:
+        return None
+    return _SlotPlan(encoders, n, shared)
+
+
+def _direct_step_slots(plan: _SlotPlan, mol_batch, head, target_batch, target_weights, data_weights,
+                       features=None) -> torch.Tensor:
+    """``_direct_step`` for a model of N molecules per input.  Not shared: every encoder's training forward in slot
+    order (their dropout seeds are drawn in that order, as on the autograd path), one ``wdmpnn_slots_join`` launch
+    that builds x = [enc_0 | .. | enc_{N-1} | features], the fused head on x, one ``wdmpnn_slots_split`` launch
+    that makes every slot's slice of dx contiguous, every encoder's backward into its own ``.grad`` buffers: two
+    launches more than the one-molecule pieces, and the losses and gradients of the autograd path, bitwise (the join
+    and the split move what ``torch.cat`` and its backward move).  Shared: one training forward over the merged
+    batch, whose output ``[N B][H]`` is the join's slot-major input; the split writes one ``[N B][H]`` buffer, the
+    merged backward's ``dout``, and the one backward's split-K GEMMs sum the shared weights' gradients over the
+    slots themselves."""
+    from .slots import join_slots, split_slots
+    n_rows = len(mol_batch[0].a_scope)
+    if plan.shared:
+        enc = plan.encoders[0]
+        out, state = enc._train_forward(mol_batch.merged)
+        if out.shape[0] != plan.n * n_rows:
+            raise ValueError(f'the merged batch holds {out.shape[0]} molecules for {plan.n} slots of {n_rows} rows')
+        embs, states = [out], [state]
+    else:
+        embs, states = [], []
+        for enc, g in zip(plan.encoders, mol_batch):
+            out, state = enc._train_forward(g)
+            embs.append(out)
+            states.append(state)
+    H = embs[0].shape[1]
+    x = join_slots(embs, n_rows, features)
+    loss, dx = _direct_head(x, head, target_batch, target_weights, data_weights, _grad_buffer)
+    d = split_slots(dx, plan.n, H)
+    if plan.shared:
+        enc = plan.encoders[0]
+        enc._train_backward(states[0], d.view(plan.n * n_rows, H), {n: _grad_buffer(p) for n, p in enc._direct_names()})
+    else:
+        for k, enc in enumerate(plan.encoders):
+            enc._train_backward(states[k], d[k], {n: _grad_buffer(p) for n, p in enc._direct_names()})
     return loss
 
 
@@ -1151,7 +1307,16 @@ def train_step(model: nn.Module, mol_batch, target_batch, loss_func: Callable, o
     device-resident ``atom_descriptors.AtomDescriptorTable`` take the direct step when the encoder has no dropout
     (the descriptor layer runs after the readout: encoder forward, join, layer, features join if any, head,
     layer backward, encoder backward).  A list of numpy arrays as in the reference, active dropout, atom
-    messages, depth 1 and partly frozen models take the autograd path."""
+    messages, depth 1 and partly frozen models take the autograd path.
+
+    A model of several molecules per input (``number_of_molecules > 1``; ``mol_batch`` is the list of one
+    ``BatchMolGraph`` per molecule, or a ``slots.SlotBatch``) takes the direct step as well (``_direct_slots``,
+    ``_direct_step_slots``): every encoder's forward, one ``wdmpnn_slots_join`` launch, the fused head, one
+    ``wdmpnn_slots_split`` launch, every encoder's backward; bitwise the autograd path's losses and gradients, and
+    :class:`HipAdam` rewrites every encoder's pack.  A shared encoder (``mpn_shared``) runs once, forward and
+    backward, over ``SlotBatch(shared=True).merged`` when it has no dropout (the project's parity bound instead of
+    bitwise: the merged batch is cut into other molecule blocks); given a plain list, or with dropout, it keeps the
+    autograd path.  So do frozen plans, ``encodings=``, ``bucket`` steps and atom descriptors with several molecules."""
     if encodings is not None and atom_descriptors_batch is not None:
         raise ValueError('train_step(encodings=...) takes no atom descriptors (frozen plans with descriptors keep the '
                          'autograd path)')
@@ -1160,8 +1325,12 @@ def train_step(model: nn.Module, mol_batch, target_batch, loss_func: Callable, o
     head = _fusable_head(model, loss_func, dataset_type) if fused_head else None
     enc = _direct_encoder(model, mol_batch, features_batch, head, atom_descriptors_batch) \
         if head is not None and direct and encodings is None else None
+    slots = None
+    if enc is None and head is not None and direct and encodings is None and bucket is None and \
+            len(getattr(model.encoder, 'encoder', ())) > 1:
+        slots = _direct_slots(model, mol_batch, features_batch, head, atom_descriptors_batch)
     plan = None
-    if enc is None and head is not None and bucket is None:
+    if enc is None and slots is None and head is not None and bucket is None:
         plan = _frozen_plan(model, mol_batch, features_batch, head, cached=encodings is not None)
         if plan is not None:
             head = plan.head  # (the stack head on either path: the same head arithmetic with and without autograd)
@@ -1182,6 +1351,8 @@ def train_step(model: nn.Module, mol_batch, target_batch, loss_func: Callable, o
         enc = plan.enc if not plan.enc_frozen else None  # (HipAdam rewrites a trainable encoder's pack)
         loss = _direct_step(model, plan.enc, None if encodings is not None else mol_batch[0], head, target_batch,
                             target_weights, data_weights, None, plan, encodings, features_batch)
+    elif slots is not None:
+        loss = _direct_step_slots(slots, mol_batch, head, target_batch, target_weights, data_weights, features_batch)
     elif enc is not None:
         # every trainable parameter's gradient is overwritten: no zeroing, no autograd
         if bucket is not None:
@@ -1210,8 +1381,11 @@ def train_step(model: nn.Module, mol_batch, target_batch, loss_func: Callable, o
         bucket.finish_allreduce()
     if grad_clip:
         nn.utils.clip_grad_norm_(model.parameters(), grad_clip)
-    if enc is not None and isinstance(optimizer, HipAdam):
-        optimizer.repack_next(enc)
+    if isinstance(optimizer, HipAdam):
+        if enc is not None:
+            optimizer.repack_next(enc)
+        elif slots is not None:
+            optimizer.repack_next(*slots.encoders)
     optimizer.step()
     if scheduler is not None and isinstance(scheduler, (NoamLR, torch.optim.lr_scheduler.CosineAnnealingLR,
                                                         torch.optim.lr_scheduler.CyclicLR)):

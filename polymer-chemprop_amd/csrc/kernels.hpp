@@ -614,6 +614,60 @@ __global__ __launch_bounds__(256) void join_rows_kernel(const JoinArgs A) {
     }
 }
 
+// wdmpnn_slots_join / wdmpnn_slots_split: the FFN input of a model of several molecules, x[b] = [slot_0[b] | ..
+// | slot_{n-1}[b] | feat[idx[b]]], and its inverse on the slot columns (SPLIT: slot_k[b] = x[b][k H .. k H + H),
+// the feature columns ignored).  A pure copy of 32-bit words.  Each row is cut into units: `su` units per slot,
+// then `fu` for the features.  On the vector path (`vec`, chosen by the host from the alignment of every side;
+// H % 4 == 0 there) a slot is H / 4 16-byte units and the features Ff / 4 such units followed by Ff % 4 single
+// words; else a unit is one word.  One thread per unit in a fixed map (unit t of the launch = row t / units,
+// unit t % units of that row).
+struct SlotArgs {
+    uint32_t *slot[8];
+    const uint32_t *feat;
+    const int64_t *idx;
+    uint32_t *x;
+    int B, n, H, ld_slot, ld_feat, Ff, ld_x, vec, su, units;
+};
+template <bool SPLIT>
+__global__ __launch_bounds__(256) void slots_kernel(const SlotArgs A) {
+    const size_t total = (size_t)A.B * A.units;
+    const int nsu = A.n * A.su;
+    for (size_t t = (size_t)blockIdx.x * blockDim.x + threadIdx.x; t < total; t += (size_t)gridDim.x * blockDim.x) {
+        const int b = (int)(t / A.units);
+        int u = (int)(t % A.units);
+        uint32_t *xr = A.x + (size_t)b * A.ld_x;
+        if (u < nsu) {
+            const int k = u / A.su;
+            u -= k * A.su;
+            uint32_t *sp = A.slot[0];
+#pragma unroll
+            for (int q = 1; q < 8; ++q)
+                if (q == k) sp = A.slot[q];  // (a by-value array indexed by a run-time value would go to scratch)
+            sp += (size_t)b * A.ld_slot;
+            uint32_t *xs = xr + (size_t)k * A.H;
+            if (A.vec) {
+                if (SPLIT) reinterpret_cast<uint4 *>(sp)[u] = reinterpret_cast<const uint4 *>(xs)[u];
+                else reinterpret_cast<uint4 *>(xs)[u] = reinterpret_cast<const uint4 *>(sp)[u];
+            } else {
+                if (SPLIT) sp[u] = xs[u];
+                else xs[u] = sp[u];
+            }
+        } else if (!SPLIT) {
+            u -= nsu;
+            const int64_t r = A.idx ? A.idx[b] : (int64_t)b;
+            const uint32_t *from = A.feat + r * A.ld_feat;
+            uint32_t *to = xr + (size_t)A.n * A.H;
+            const int nv = A.vec ? A.Ff >> 2 : 0;
+            if (u < nv) {
+                reinterpret_cast<uint4 *>(to)[u] = reinterpret_cast<const uint4 *>(from)[u];
+            } else {
+                const int c = 4 * nv + (u - nv);
+                to[c] = from[c];
+            }
+        }
+    }
+}
+
 // Gradient of index_select_rows: dsrc[j] = sum over positions p with index[p] == j of grad[p], added in
 // increasing p (deterministic, no atomics).  perm = positions sorted stably by index, ptr[j] .. ptr[j+1]
 // the positions of row j in perm; one thread per output value.

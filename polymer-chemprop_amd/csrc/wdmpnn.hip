@@ -1775,6 +1775,67 @@ int wdmpnn_join_rows(const WdJoin *j, void *stream) {
     return 0;
 }
 
+// the checks and the launch shared by wdmpnn_slots_join and wdmpnn_slots_split (`split`: the feature fields
+// are not read)
+static int slots_launch(const WdSlots *s, bool split, void *stream) {
+    const char *what = split ? "slots_split" : "slots_join";
+    if (!s) return fail(WD_ERR_ARG, "%s: null struct", what);
+    if (s->n_slots > WD_MAX_SLOTS)
+        return fail(WD_ERR_UNSUPPORTED, "%s: %d slots (at most %d)", what, s->n_slots, WD_MAX_SLOTS);
+    if (s->n_slots < 1) return fail(WD_ERR_ARG, "%s: %d slots (at least 1)", what, s->n_slots);
+    const int Ff = split ? 0 : s->Ff;
+    if (s->B < 0 || s->H <= 0 || s->ld_slot < s->H)
+        return fail(WD_ERR_SHAPE, "%s: needs B >= 0, H > 0, ld_slot >= H (got B %d H %d ld_slot %d)", what, s->B, s->H,
+                    s->ld_slot);
+    if (s->Ff < 0 || s->ld_feat < s->Ff)
+        return fail(WD_ERR_SHAPE, "%s: needs Ff >= 0, ld_feat >= Ff (got Ff %d ld_feat %d)", what, s->Ff, s->ld_feat);
+    const int64_t width = (int64_t)s->n_slots * s->H + s->Ff;
+    if ((int64_t)s->ld_x < width)
+        return fail(WD_ERR_SHAPE, "%s: ld_x %d for %lld columns", what, s->ld_x, (long long)width);
+    if (s->B == 0) return 0;
+    if (!s->x) return fail(WD_ERR_ARG, "%s: null x", what);
+    for (int k = 0; k < s->n_slots; ++k)
+        if (!s->slot[k]) return fail(WD_ERR_ARG, "%s: null slot %d", what, k);
+    if (s->Ff > 0 && !s->feat) return fail(WD_ERR_ARG, "%s: null feat with %d feature columns", what, s->Ff);
+    SlotArgs A{};
+    // the 16-byte path: every row's first word of every slot, of x's slot columns and of the features on a
+    // 16-byte boundary
+    bool vec = aligned16(s->x) && s->ld_x % 4 == 0 && s->H % 4 == 0 && s->ld_slot % 4 == 0;
+    for (int k = 0; k < s->n_slots; ++k) {
+        A.slot[k] = reinterpret_cast<uint32_t *>(s->slot[k]);
+        vec = vec && aligned16(s->slot[k]);
+    }
+    if (Ff > 0) vec = vec && aligned16(s->feat) && s->ld_feat % 4 == 0;
+    A.feat = Ff > 0 ? reinterpret_cast<const uint32_t *>(s->feat) : nullptr;
+    A.idx = Ff > 0 ? s->feat_idx : nullptr;
+    A.x = reinterpret_cast<uint32_t *>(s->x);
+    A.B = s->B;
+    A.n = s->n_slots;
+    A.H = s->H;
+    A.ld_slot = s->ld_slot;
+    A.ld_feat = s->ld_feat;
+    A.Ff = Ff;
+    A.ld_x = s->ld_x;
+    A.vec = vec;
+    A.su = vec ? s->H / 4 : s->H;
+    A.units = s->n_slots * A.su + (vec ? Ff / 4 + Ff % 4 : Ff);
+    const int nb = ew_blocks((size_t)s->B * A.units);
+    if (split) hipLaunchKernelGGL(slots_kernel<true>, dim3(nb), dim3(256), 0, (hipStream_t)stream, A);
+    else hipLaunchKernelGGL(slots_kernel<false>, dim3(nb), dim3(256), 0, (hipStream_t)stream, A);
+    WD_CHECK_LAUNCH(what);
+    return 0;
+}
+
+int wdmpnn_slots_join(const WdSlots *s, void *stream) {
+    WD_KERNELS_OK();
+    return slots_launch(s, false, stream);
+}
+
+int wdmpnn_slots_split(const WdSlots *s, void *stream) {
+    WD_KERNELS_OK();
+    return slots_launch(s, true, stream);
+}
+
 int wdmpnn_desc_join(const WdDescJoin *j, void *stream) {
     WD_KERNELS_OK();
     if (!j || !j->g) return fail(WD_ERR_ARG, "desc_join: null %s", !j ? "struct" : "graph");
