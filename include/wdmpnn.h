@@ -361,6 +361,50 @@ int wdmpnn_build_graph(const WdCompact *c, void *buffer, size_t bytes, WdGraph *
 #define WDMPNN_GRAPH_NO_PLANES 2
 int wdmpnn_build_graph_ex(const WdCompact *c, void *buffer, size_t bytes, WdGraph *g, int32_t flags, void *stream);
 
+/* Resident graph tables: the compact image of a batch assembled on the device from the codes of a whole data
+ * split, uploaded once per run (chemprop_amd.graph_table).  A molecule's compact record is position-independent
+ * (WdAtomCode holds nothing batch-relative, WdBondPair.a1 / a2 are molecule-local), so the xn, atoms and pairs
+ * sections of the image of any batch are a segmented copy of per-molecule records; mols, blocks and block_nnz
+ * are the small host plan (csrc/compact.hpp plan_sizes, from the molecules' sizes and entry counts alone).
+ *
+ * The table: t_atoms and t_pairs hold every molecule's records back to back (no pad rows), t_xn its
+ * degree_of_polym, t_first [molecules][2] (int64, so a table of millions of molecules does not overflow) the
+ * index of its first atom record and of its first pair record.  A table of rows of n_slots molecules
+ * (number_of_molecules > 1) numbers its molecules row * n_slots + slot.
+ * The batch: ids [n_rows] (int64) are table rows, a slice of an index that was validated on the host; batch
+ * molecule m, m < n_mols, is slot slot0 + m / n_rows of row ids[m % n_rows].  A batch of one slot has
+ * n_mols = n_rows; the merged batch of a shared encoder (slot 0's molecules, then slot 1's, ...) has
+ * n_mols = n_slots * n_rows and slot0 = 0.  Repeated ids, or ids in any order, give the corresponding copies.
+ * The destination: the sections of an image laid out as the staged upload image (mols | xn | atoms | pairs |
+ * blocks | block_nnz); mols [n_mols][4] must already be there (uploaded earlier on the same stream) and must
+ * give every molecule the sizes its table record has.  One launch writes
+ *     atoms[0]                                 the pad row (no columns, last = 0, w = 0)
+ *     atoms[atom_start_m + i]                = t_atoms[first atom record + i]     i < n_atoms_m
+ *     pairs[(bond_start_m - 1) / 2 + i]      = t_pairs[first pair record + i]     i < n_bonds_m / 2
+ *     xn[m]                                  = t_xn[molecule]
+ * and with the host plan's three sections the image is bitwise the one the host stages for the same molecules
+ * in the same order, so the graph built from it and everything downstream are bitwise unchanged.
+ * One wave per molecule, a 128-bit load and a 128-bit store per record per lane; no atomics, no LDS, plain
+ * vector stores, a fixed thread-to-record map.  The kernel clamps nothing, like the row join above: range
+ * checking of ids is the caller's (chemprop_amd.graph_table.GraphTable.index).
+ * Refused before any launch: a NULL struct, or with n_mols > 0 one of the nine pointers NULL or one of t_atoms,
+ * t_pairs, mols, atoms, pairs off a 16-byte boundary (WD_ERR_ARG);
+ * n_mols < 0, n_rows < 0, or with n_mols > 0: n_rows < 1, n_slots < 1, slot0 < 0, n_mols not a multiple of
+ * n_rows, slot0 + n_mols / n_rows > n_slots (WD_ERR_SHAPE).  n_mols == 0 is a no-op. */
+typedef struct WdGatherCompact {
+    int32_t n_mols, n_rows, n_slots, slot0;
+    const WdAtomCode *t_atoms;    /* table: atom records of every molecule                  */
+    const WdBondPair *t_pairs;    /* table: pair records of every molecule                  */
+    const float *t_xn;            /* table: [molecules] degree_of_polym                     */
+    const int64_t *t_first;       /* table: [molecules][2] first atom / first pair record   */
+    const int64_t *ids;           /* [n_rows] table rows                                    */
+    const int32_t *mols;          /* image: [n_mols][4], already uploaded                   */
+    float *xn;                    /* image: [n_mols]                                        */
+    WdAtomCode *atoms;            /* image: [1 + sum n_atoms]                               */
+    WdBondPair *pairs;            /* image: [sum n_bonds / 2]                               */
+} WdGatherCompact;
+int wdmpnn_gather_compact(const WdGatherCompact *g, void *stream);
+
 /* index_select_ND (nn_utils.py:50-67): out[i, :] = src[index[i], :], row_len floats per row.
  * Indices are int64 like the reference's LongTensor; out-of-range indices are an error checked by
  * the caller (the kernel clamps nothing and reads src[index]). */

@@ -10,6 +10,7 @@ from .atom_descriptors import AtomDescriptorIndex, AtomDescriptorRows, AtomDescr
 from .evaluate import Evaluator, TargetTable, evaluate
 from .featurization import BatchMolGraph, get_atom_fdim, get_bond_fdim, mol2graph
 from .features import FeatureIndex, FeatureRows, FeatureTable
+from .graph_table import GraphIndex, GraphRows, GraphTable
 from .model import MoleculeModel
 from .mpn import MPN, MPNEncoder
 from .nn_utils import get_activation_function, index_select_ND, initialize_weights
@@ -18,4 +19,4 @@ from .slots import SlotBatch
 __all__ = ['TrainArgs', 'BatchMolGraph', 'get_atom_fdim', 'get_bond_fdim', 'mol2graph', 'MoleculeModel', 'MPN',
            'MPNEncoder', 'get_activation_function', 'index_select_ND', 'initialize_weights', 'FeatureTable',
            'FeatureIndex', 'FeatureRows', 'TargetTable', 'Evaluator', 'evaluate', 'AtomDescriptorTable',
-           'AtomDescriptorIndex', 'AtomDescriptorRows', 'SlotBatch']
+           'AtomDescriptorIndex', 'AtomDescriptorRows', 'SlotBatch', 'GraphTable', 'GraphIndex', 'GraphRows']

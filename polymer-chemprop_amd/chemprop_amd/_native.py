@@ -49,7 +49,8 @@ EXPORTED_SYMBOLS = ('wdmpnn_abi_version', 'wdmpnn_last_error', 'wdmpnn_workspace
                     'wdmpnn_head_spectra_predict', 'wdmpnn_join_rows', 'wdmpnn_ensemble_add',
                     'wdmpnn_ensemble_sid', 'wdmpnn_eval_add', 'wdmpnn_eval_spectra', 'wdmpnn_eval_auc',
                     'wdmpnn_head_stack_latent', 'wdmpnn_latent_add', 'wdmpnn_desc_join', 'wdmpnn_desc_layer',
-                    'wdmpnn_desc_layer_backward', 'wdmpnn_desc_rows', 'wdmpnn_slots_join', 'wdmpnn_slots_split')
+                    'wdmpnn_desc_layer_backward', 'wdmpnn_desc_rows', 'wdmpnn_slots_join', 'wdmpnn_slots_split',
+                    'wdmpnn_gather_compact')
 HEAD_MAX_LAYERS = 6  # WD_HEAD_MAX_LAYERS
 HEAD_MAX_SPECTRUM = 8192  # WD_HEAD_MAX_SPECTRUM
 SPECTRA_ACTIVATIONS = {'exp': 0, 'softplus': 1}  # WdHeadSpectra.spectra_act
@@ -262,6 +263,12 @@ class WdDescRows(Structure):
                 ('ld', c_int32)]
 
 
+class WdGatherCompact(Structure):
+    _fields_ = [('n_mols', c_int32), ('n_rows', c_int32), ('n_slots', c_int32), ('slot0', c_int32),
+                ('t_atoms', c_void_p), ('t_pairs', c_void_p), ('t_xn', c_void_p), ('t_first', c_void_p),
+                ('ids', c_void_p), ('mols', c_void_p), ('xn', c_void_p), ('atoms', c_void_p), ('pairs', c_void_p)]
+
+
 def join_rows(out, segments, stream: int) -> None:
     """wdmpnn_join_rows into ``out`` (float32 device tensor ``[B][ld_out]``, row-major): ``segments`` are
     ``(src data pointer, ld, c0, w, index data pointer or 0)``.  Every index must have been range-checked by the
@@ -385,6 +392,7 @@ def lib() -> ctypes.CDLL:
     L.wdmpnn_desc_layer.argtypes = [POINTER(WdDescLayer), c_void_p]
     L.wdmpnn_desc_layer_backward.argtypes = [POINTER(WdDescLayerBackward), c_void_p]
     L.wdmpnn_desc_rows.argtypes = [POINTER(WdDescRows), c_void_p]
+    L.wdmpnn_gather_compact.argtypes = [POINTER(WdGatherCompact), c_void_p]
     L.wdmpnn_eval_add.argtypes = [POINTER(WdEvalAdd), c_void_p]
     L.wdmpnn_eval_spectra.argtypes = [POINTER(WdEvalSpectra), c_void_p]
     L.wdmpnn_eval_auc.argtypes = [POINTER(WdEvalAuc), c_void_p]
@@ -419,7 +427,7 @@ def lib() -> ctypes.CDLL:
              'wdmpnn_head_spectra_predict', 'wdmpnn_join_rows', 'wdmpnn_ensemble_add', 'wdmpnn_ensemble_sid',
              'wdmpnn_eval_add', 'wdmpnn_eval_spectra', 'wdmpnn_eval_auc', 'wdmpnn_head_stack_latent',
              'wdmpnn_latent_add', 'wdmpnn_desc_join', 'wdmpnn_desc_layer', 'wdmpnn_desc_layer_backward',
-             'wdmpnn_desc_rows', 'wdmpnn_slots_join', 'wdmpnn_slots_split'):
+             'wdmpnn_desc_rows', 'wdmpnn_slots_join', 'wdmpnn_slots_split', 'wdmpnn_gather_compact'):
         getattr(L, fn).restype = c_int
     v = L.wdmpnn_abi_version()
     if v != ABI_VERSION:

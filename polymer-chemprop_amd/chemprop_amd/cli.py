@@ -50,6 +50,11 @@ restated here:
 * ``--device_metrics``: the per-epoch validation and training scores and a single model's test scores come from
   ``evaluate.evaluate`` (resident targets, partial sums on the device) instead of ``predict`` +
   ``evaluate_predictions``; the same files are written;
+* ``--resident_graphs``: the training split's graphs are encoded once into a ``graph_table.GraphTable`` on the
+  device; each epoch's order is one index upload next to the feature and descriptor indices, each step's graphs a
+  slice of it (one gather launch assembles the batch's compact image, the usual build launch expands it), and
+  every split's scoring batches are built once per run; a split the table refuses (extra features, a molecule
+  larger than a block) is reported in one line and trains on the list path; every output is bitwise unchanged;
 * every prediction above walks its split with ``predict.device_predictions``: ``predict`` copies the batches to the
   host, the ensemble's accumulator and ``evaluate``'s evaluator take them where the head wrote them.
 
@@ -91,6 +96,7 @@ from .featurization import BatchMolGraph
 from .ensemble import EnsembleAccumulator, accumulate_model, make_batches, predict_ensemble
 from .evaluate import Evaluator, TargetTable, evaluate
 from .features import FeatureTable
+from .graph_table import GraphTable
 from .graph_io import load_graphs
 from .model import MoleculeModel
 from .nn_utils import initialize_weights
@@ -324,7 +330,7 @@ def evaluate_predictions(preds, targets, num_tasks: int, metrics: List[str], dat
 
 def predict(model, graphs, idx, batch_size: int, scaler: Optional[StandardScaler],
             encodings: Optional[torch.Tensor] = None, features=None, spectra_mask=None,
-            atom_descriptors=None) -> List[List[float]]:
+            atom_descriptors=None, batches=None) -> List[List[float]]:
     """predict.py:10-68: eval, no_grad, batches in order, inverse scaling: the batches of
     ``predict.device_predictions`` copied to the host.  ``encodings``: the rows of ``idx`` from ``frozen_encodings``
     (a frozen encoder's outputs, computed once per run): the native prediction head on them in place of the
@@ -335,7 +341,8 @@ def predict(model, graphs, idx, batch_size: int, scaler: Optional[StandardScaler
     the positions each row's phase includes (None: all), uploaded once; excluded positions come back as None.
     ``atom_descriptors``: the split's ``AtomDescriptorTable`` (molecule k = ``idx[k]``'s rows, already scaled), or
     the scaled arrays of the whole data set (a list indexed by ``idx``), for a descriptor model.
-    The ``BatchMolGraph`` s of the whole split are held at once."""
+    ``batches``: the ``make_batches`` of ``idx``'s graphs built earlier (``graphs`` is then not read), for a caller
+    that scores the same split many times.  The ``BatchMolGraph`` s of the whole split are held at once."""
     model.eval()
     if not len(idx):
         return []
@@ -350,8 +357,10 @@ def predict(model, graphs, idx, batch_size: int, scaler: Optional[StandardScaler
     native = spectra or encodings is not None or atom_descriptors is not None
     if native and _predict_head(model) is None and atom_descriptors is None:
         raise NotImplementedError('predict: the model\'s FFN is not one the native prediction heads run')
-    batches = batch_size if encodings is not None else \
-        make_batches([graphs[i] for i in idx], batch_size, shared=shares_encoder(model))
+    if encodings is not None:
+        batches = batch_size
+    elif batches is None:
+        batches = make_batches([graphs[i] for i in idx], batch_size, shared=shares_encoder(model))
     outs = device_predictions(model, batches, features, device_mask(spectra_mask, device) if spectra else None,
                               encodings, own_forward=not native, n_rows=len(idx), atom_descriptors=atom_descriptors)
     preds = torch.cat([out for _, out in outs]).cpu().numpy().tolist()
@@ -660,6 +669,10 @@ def parse_args(argv=None, spectra: bool = False) -> argparse.Namespace:
     ap.add_argument('--device_metrics', action='store_true',
                     help='score the validation, training and test splits on the device (evaluate.evaluate): the '
                          'targets stay resident, the predictions are not copied to the host per batch')
+    ap.add_argument('--resident_graphs', action='store_true',
+                    help='keep the training split\'s graphs on the device as compact codes (graph_table.GraphTable): '
+                         'a step gathers its batch there instead of packing it on the host, and every split\'s '
+                         'scoring batches are built once per run; results are bitwise unchanged')
     a = ap.parse_args(argv)
     if not 1 <= a.ensemble_size <= ENSEMBLE_MAX_MODELS:
         raise ValueError(f'--ensemble_size must be in 1 .. {ENSEMBLE_MAX_MODELS}')
@@ -779,10 +792,36 @@ def run_training(a: argparse.Namespace) -> Dict[str, list]:
     def batch_targets(pos):
         return train_targets[pos] if spectra else [train_targets[p] for p in pos]
 
+    # --resident_graphs: the training split's graphs go to the device once per run as compact codes (built on
+    # first use: a run on cached encodings never needs them; epochs and ensemble members share the table), and
+    # the scoring batches of every split are built once per run instead of once per epoch
+    resident = bool(getattr(a, 'resident_graphs', False))
+    resident_state = {}
+    scoring_batches = {}
+
+    def graph_table():
+        """The training split's ``GraphTable``, or None when it refuses the split (logged once; the run then
+        continues on the list path)."""
+        if 'table' not in resident_state:
+            try:
+                resident_state['table'] = GraphTable([graphs[i] for i in train_idx], device)
+            except ValueError as e:
+                resident_state['table'] = None
+                print(f'--resident_graphs: the training graphs stay on the list path ({e})', flush=True)
+        return resident_state['table']
+
+    def batches_of(name, idx):
+        if not resident:
+            return None
+        if name not in scoring_batches:
+            scoring_batches[name] = make_batches([graphs[i] for i in idx], a.batch_size, shared=mpn_shared)
+        return scoring_batches[name]
+
     def run_predict(model, enc_cache, name, idx):
         return predict(model, graphs, idx, a.batch_size, scaler, enc_cache and enc_cache[name],
                        tables and tables[name], None if row_mask is None else row_mask[idx],
-                       atom_descriptors=desc_tables and desc_tables[name])
+                       atom_descriptors=desc_tables and desc_tables[name],
+                       batches=None if enc_cache is not None or not len(idx) else batches_of(name, idx))
     # --device_metrics: every split's target table and phase mask go to the device once per run, its
     # BatchMolGraphs are built once (on first use: a run on cached encodings never needs them), and a split is
     # scored by evaluate.evaluate without a host copy per batch
@@ -802,8 +841,8 @@ def run_training(a: argparse.Namespace) -> Dict[str, list]:
             batches = a.batch_size
         else:
             if name not in split_batches:
-                split_batches[name] = make_batches([graphs[i] for i in split_idx[name]], a.batch_size,
-                                                   shared=mpn_shared)
+                split_batches[name] = batches_of(name, split_idx[name]) or \
+                    make_batches([graphs[i] for i in split_idx[name]], a.batch_size, shared=mpn_shared)
             batches = split_batches[name]
         return evaluate(model, batches, table, metrics, scaler, tables and tables[name], split_masks[name],
                         enc_cache and enc_cache[name], evaluator=ev,
@@ -845,6 +884,8 @@ def run_training(a: argparse.Namespace) -> Dict[str, list]:
                 # the epoch's order as one validated index upload; every step takes a slice of it
                 findex = tables['train'].index(order) if tables is not None and order else None
                 dindex = desc_tables['train'].index(order) if desc_tables is not None and order else None
+                gtable = graph_table() if resident and enc_cache is None and order else None
+                gindex = None if gtable is None else gtable.index(order)
                 for s in range(0, len(order), a.batch_size):
                     pos = order[s:s + a.batch_size]
                     feats = None if findex is None else findex[s:s + a.batch_size]
@@ -854,7 +895,10 @@ def run_training(a: argparse.Namespace) -> Dict[str, list]:
                                           a.dataset_type, features_batch=feats, grad_clip=a.grad_clip,
                                           encodings=rows)
                     else:
-                        if n_mols == 1:
+                        if gindex is not None:  # (the step's graphs: a slice of the epoch's index)
+                            rows = gindex[s:s + a.batch_size]
+                            g = [rows.batch()] if n_mols == 1 else rows.slot_batch(shared=mpn_shared)
+                        elif n_mols == 1:
                             g = [BatchMolGraph([graphs[train_idx[p]] for p in pos])]
                         else:  # (one BatchMolGraph per slot, and the merged one for a shared encoder)
                             g = SlotBatch([[graphs[train_idx[p]][k] for p in pos] for k in range(n_mols)],
@@ -901,7 +945,8 @@ def run_training(a: argparse.Namespace) -> Dict[str, list]:
         # into one accumulator on the device, and the top-level scores and predictions are the ensemble's
         width = num_tasks * (a.multiclass_num_classes if multiclass else 1)
         acc = EnsembleAccumulator(len(test_idx), width, device, keep=True, n_models=a.ensemble_size)
-        test_batches = make_batches([graphs[i] for i in test_idx], a.batch_size, shared=mpn_shared)
+        test_batches = batches_of('test', test_idx) or \
+            make_batches([graphs[i] for i in test_idx], a.batch_size, shared=mpn_shared)
         test_mask = device_mask(row_mask, device, test_idx)
         best_epoch = []
         for k in range(a.ensemble_size):

@@ -297,10 +297,18 @@ class BatchMolGraph:
              'max_num_bonds')
 
     def __getattr__(self, name):
-        # only reached for attributes not set yet: a from_compact batch decodes its tables once
-        if name in BatchMolGraph._LAZY and self.__dict__.get('_compact') is not None and '_np' not in self.__dict__:
+        # only reached for attributes not set yet: a from_compact batch decodes its tables once; a batch of a
+        # resident table (``_source``, graph_table.py) first assembles its compact arrays on the host, and does
+        # either only when something reads them
+        d = self.__dict__
+        src = d.get('_source')
+        if name == '_compact' and src is not None:
+            d['_compact'] = src.host_compact(self)
+            return d['_compact']
+        if name in BatchMolGraph._LAZY and '_np' not in d and (d.get('_compact') is not None or src is not None):
+            self._compact  # noqa: B018 (assembled now if it was not)
             self._decode_compact()
-            return self.__dict__[name]
+            return d[name]
         raise AttributeError(name)
 
     def _decode_compact(self) -> None:
@@ -489,6 +497,12 @@ class BatchMolGraph:
         dg = self._device_cache.get(key)
         if dg is not None:
             return dg
+        src = self.__dict__.get('_source')
+        if src is not None and not atom_messages and (bond_fdim is None or bond_fdim == self._compact_dims[1]):
+            dg = src.device_graph(self, device)  # gathered on the device from the resident table, or None
+            if dg is not None:
+                self._device_cache[key] = dg
+                return dg
         if self._compact is not None and not atom_messages and device.type == 'cuda' and \
                 (bond_fdim is None or bond_fdim == self._compact_dims[1]):
             dg = self._device_graph_compact(device)
@@ -691,8 +705,22 @@ def upload_compact(device, staged: torch.Tensor, info, atom_fdim: int, bond_fdim
     batch.  ``info`` = (copied, counts, offsets, total) as the native stage functions return it.
     ``lean``: an inference-only graph (WDMPNN_GRAPH_LEAN: no dense feature rows, planes or transposed
     gathers); a training forward or an unblocked path on it raises NotImplementedError."""
-    _, (n_mols, n_atoms, n_bonds, n_blocks, nnz_msg, nnz_agg), off, total = info
+    _, (_, _, _, n_blocks, _, _), off, total = info
     buf = staged[:total].to(device, non_blocking=True)
+    blk_max = None
+    if n_blocks:  # the block plan's largest blocks, read from the staged image (WdGraph.blk_max_*)
+        blk = np.frombuffer(staged.numpy(), np.int32, count=8 * n_blocks, offset=off[4]).reshape(n_blocks, 8)
+        blk_max = (int(blk[:, 1].max()), int(blk[:, 3].max()))
+    return build_from_image(device, buf, info, blk_max, atom_fdim, bond_fdim, lean)
+
+
+def build_from_image(device, buf: torch.Tensor, info, blk_max, atom_fdim: int, bond_fdim: int,
+                     lean: bool = False) -> DeviceGraph:
+    """``wdmpnn_build_graph_ex`` on the current stream from a compact image already on the device (``buf``, laid
+    out as ``info`` says; ``upload_compact`` copies one there, ``graph_table`` gathers one): the DeviceGraph of the
+    batch, which keeps the image alive.  ``blk_max``: (largest block's bond rows, atom rows) of the plan, or None
+    without blocks."""
+    _, (n_mols, n_atoms, n_bonds, n_blocks, nnz_msg, nnz_agg), off, total = info
     base = buf.data_ptr()
     c = _native.WdCompact()
     c.n_mols, c.n_atoms, c.n_bonds, c.n_blocks = n_mols, n_atoms, n_bonds, n_blocks
@@ -706,9 +734,8 @@ def upload_compact(device, staged: torch.Tensor, info, atom_fdim: int, bond_fdim
     _native.check(L.wdmpnn_build_graph_ex(ctypes.byref(c), gbuf.data_ptr(), nbytes.value, ctypes.byref(s),
                                           _native.GRAPH_LEAN if lean else 0, _native.current_stream(device)),
                   'device graph build')
-    if n_blocks:  # the block plan's largest blocks, read from the staged image (WdGraph.blk_max_*)
-        blk = np.frombuffer(staged.numpy(), np.int32, count=8 * n_blocks, offset=off[4]).reshape(n_blocks, 8)
-        s.blk_max_bonds, s.blk_max_atoms = int(blk[:, 1].max()), int(blk[:, 3].max())
+    if blk_max is not None:
+        s.blk_max_bonds, s.blk_max_atoms = blk_max
     dg = DeviceGraph(gbuf, {'compact': buf}, s)
     dg.finish()
     dg.n_edges = n_bonds - 1

@@ -56,6 +56,32 @@ class SlotBatch(list):
         if shared:
             self.merged = BatchMolGraph([g for m in mol_lists for g in m], **batch_kwargs)
 
+    @classmethod
+    def from_batches(cls, batches: Sequence[BatchMolGraph], merged: Optional[BatchMolGraph] = None) -> 'SlotBatch':
+        """The ``SlotBatch`` of prebuilt ``BatchMolGraph`` s, one per slot (``graph_table.GraphRows.slot_batch``
+        gathers them from a resident table), and of their ``merged`` graph for a shared encoder: slot 0's
+        molecules, then slot 1's, and so on.  The same ``ValueError`` s as the constructor's."""
+        batches = list(batches)
+        n = len(batches)
+        if not 1 <= n <= _native.MAX_SLOTS:
+            raise ValueError(f'SlotBatch: {n} molecules per input (1 .. {_native.MAX_SLOTS})')
+        sizes = [len(b.a_scope) for b in batches]
+        if len(set(sizes)) != 1:
+            raise ValueError(f'SlotBatch: the slots hold {sizes} molecules: every row needs one molecule per slot')
+        if sizes[0] == 0:
+            raise ValueError('SlotBatch: no rows')
+        widths = {(b.atom_fdim, b.bond_fdim) for b in batches + ([] if merged is None else [merged])}
+        if len(widths) > 1:
+            raise ValueError(f'SlotBatch: (atom, bond) feature widths {sorted(widths)}: every slot needs the same')
+        if merged is not None and len(merged.a_scope) != n * sizes[0]:
+            raise ValueError(f'SlotBatch: a merged graph of {len(merged.a_scope)} molecules for {n} slots of '
+                             f'{sizes[0]}')
+        self = cls.__new__(cls)
+        list.__init__(self, batches)
+        self.n_rows = sizes[0]
+        self.merged = merged
+        return self
+
 
 def shares_encoder(model) -> bool:
     """Whether ``model`` runs one encoder for several molecules per input (``mpn_shared``)."""

@@ -198,17 +198,43 @@ struct Plan {
     std::vector<int32_t> blocks;     // [nblk][8]
     std::vector<int32_t> block_nnz;  // [nblk][2]
     int64_t nnz_msg = 0, nnz_agg = 0;
-    std::vector<int32_t> nz;         // scratch: nonzero in-weights per atom
+    std::vector<int32_t> nz;         // scratch: [B][2] entries per molecule (msg, agg)
     int n_blocks() const { return (int)(blocks.size() / 8); }
 };
 
-inline bool plan(const Batch &c, int target_blocks, Plan &p) {
+// Entries of one molecule's msg_gather / atom_gather rows, a function of its own pairs and weights alone:
+// nz(a) = bonds into a with a nonzero weight; msg row a1 -> a2 (reverse weight w21):
+// nz(a1) - [w21 != 0] + [w21 != 1]; agg row a: nz(a).  false when an endpoint leaves the molecule
+// (n_atoms <= BLK_ATOMS is the caller's check).
+inline bool mol_entries(const WdBondPair *pairs, int64_t n_pairs, int64_t n_atoms, int32_t &msg, int32_t &agg) {
+    int32_t nz[BLK_ATOMS] = {};
+    for (int64_t k = 0; k < n_pairs; ++k) {
+        const WdBondPair &q = pairs[k];
+        if (q.a1 >= n_atoms || q.a2 >= n_atoms) return false;
+        nz[q.a2] += q.w12 != 0.f;
+        nz[q.a1] += q.w21 != 0.f;
+    }
+    int32_t om = 0, oa = 0;
+    for (int64_t k = 0; k < n_pairs; ++k) {
+        const WdBondPair &q = pairs[k];
+        om += nz[q.a1] - (q.w21 != 0.f) + (q.w21 - 1.0f != 0.f);  // b1 = a1 -> a2
+        om += nz[q.a2] - (q.w12 != 0.f) + (q.w12 - 1.0f != 0.f);  // b2 = a2 -> a1
+    }
+    for (int64_t a = 0; a < n_atoms; ++a) oa += nz[a];
+    msg = om;
+    agg = oa;
+    return true;
+}
+
+// The plan of a batch from its molecules' rows alone: mols [B][4] as in Batch, nnz [B][2] = each molecule's
+// (msg, agg) entries (mol_entries).  Fills blocks, block_nnz and the totals; false when a molecule exceeds
+// a block.
+inline bool plan_mols(const int32_t *mols, const int32_t *nnz, int64_t B, int target_blocks, Plan &p) {
     p.blocks.clear(); p.block_nnz.clear();  // (capacity kept: see generate)
     p.nnz_msg = p.nnz_agg = 0;
-    const int64_t B = c.n_mols();
     int64_t big = 0, tot = 0;
     for (int64_t i = 0; i < B; ++i) {
-        const int64_t bn = c.mols[4 * i + 3], an = c.mols[4 * i + 1];
+        const int64_t bn = mols[4 * i + 3], an = mols[4 * i + 1];
         if (bn > BLK_BONDS || an > BLK_ATOMS) return false;
         big = std::max(big, bn);
         tot += bn;
@@ -218,7 +244,7 @@ inline bool plan(const Batch &c, int target_blocks, Plan &p) {
     int32_t cur[8];
     bool have = false;
     for (int64_t i = 0; i < B; ++i) {
-        const int32_t as = c.mols[4 * i], an = c.mols[4 * i + 1], bs = c.mols[4 * i + 2], bn = c.mols[4 * i + 3];
+        const int32_t as = mols[4 * i], an = mols[4 * i + 1], bs = mols[4 * i + 2], bn = mols[4 * i + 3];
         if (have && cur[1] + bn <= cap_b && cur[3] + an <= BLK_ATOMS && i - cur[4] < BLK_MOLS) {
             cur[1] += bn; cur[3] += an; cur[5] = (int32_t)i + 1;
         } else {
@@ -229,19 +255,6 @@ inline bool plan(const Batch &c, int target_blocks, Plan &p) {
         }
     }
     if (have) p.blocks.insert(p.blocks.end(), cur, cur + 8);
-    // entries: nz(a) = bonds into a with a nonzero weight; msg row a1 -> a2 (reverse weight w21):
-    // nz(a1) - [w21 != 0] + [w21 != 1]; agg row a: nz(a)
-    const int64_t V1 = c.n_atoms();
-    p.nz.assign((size_t)V1, 0);
-    std::vector<int32_t> &nz = p.nz;
-    for (int64_t i = 0; i < B; ++i) {
-        const int64_t ao = c.mols[4 * i], bo = c.mols[4 * i + 2];
-        for (int64_t lb = 0; lb < c.mols[4 * i + 3]; lb += 2) {
-            const WdBondPair &q = c.pairs[(size_t)((bo + lb - 1) / 2)];
-            nz[(size_t)(ao + q.a2)] += q.w12 != 0.f;
-            nz[(size_t)(ao + q.a1)] += q.w21 != 0.f;
-        }
-    }
     const int nblk = p.n_blocks();
     p.block_nnz.resize((size_t)nblk * 2);
     int64_t om = 0, oa = 0;
@@ -249,19 +262,42 @@ inline bool plan(const Batch &c, int target_blocks, Plan &p) {
         const int32_t *r = &p.blocks[(size_t)k * 8];
         p.block_nnz[(size_t)2 * k] = (int32_t)om;
         p.block_nnz[(size_t)2 * k + 1] = (int32_t)oa;
-        for (int32_t mi = r[4]; mi < r[5]; ++mi) {
-            const int64_t ao = c.mols[4 * mi], bo = c.mols[4 * mi + 2];
-            for (int64_t lb = 0; lb < c.mols[4 * mi + 3]; lb += 2) {
-                const WdBondPair &q = c.pairs[(size_t)((bo + lb - 1) / 2)];
-                om += nz[(size_t)(ao + q.a1)] - (q.w21 != 0.f) + (q.w21 - 1.0f != 0.f);  // b1 = a1 -> a2
-                om += nz[(size_t)(ao + q.a2)] - (q.w12 != 0.f) + (q.w12 - 1.0f != 0.f);  // b2 = a2 -> a1
-            }
-            for (int64_t la = 0; la < c.mols[4 * mi + 1]; ++la) oa += nz[(size_t)(ao + la)];
-        }
+        for (int32_t mi = r[4]; mi < r[5]; ++mi) { om += nnz[2 * mi]; oa += nnz[2 * mi + 1]; }
     }
     p.nnz_msg = om;
     p.nnz_agg = oa;
     return true;
+}
+
+inline bool plan(const Batch &c, int target_blocks, Plan &p) {
+    const int64_t B = c.n_mols();
+    p.nz.assign((size_t)B * 2, 0);
+    for (int64_t i = 0; i < B; ++i) {
+        const int64_t an = c.mols[4 * i + 1], bo = c.mols[4 * i + 2], bn = c.mols[4 * i + 3];
+        if (bn > BLK_BONDS || an > BLK_ATOMS) return false;
+        if (!mol_entries(c.pairs.data() + (bo - 1) / 2, bn / 2, an, p.nz[(size_t)2 * i], p.nz[(size_t)2 * i + 1]))
+            return false;
+    }
+    return plan_mols(c.mols.data(), p.nz.data(), B, target_blocks, p);
+}
+
+// The same plan for molecules known by their sizes alone (a batch assembled on the device from a resident
+// table of codes, wdmpnn_gather_compact): sizes [B][4] = {n_atoms, n_bonds, nnz_msg, nnz_agg} per molecule
+// in batch order.  Fills mols (the reference's numbering, pad row 0 first) and the plan.
+inline bool plan_sizes(const int32_t *sizes, int64_t B, int target_blocks, std::vector<int32_t> &mols, Plan &p) {
+    mols.resize((size_t)B * 4);
+    p.nz.resize((size_t)B * 2);
+    int64_t ao = 1, bo = 1;
+    for (int64_t i = 0; i < B; ++i) {
+        const int32_t *s = sizes + 4 * i;
+        if (s[0] < 0 || s[1] < 0 || s[1] % 2 || s[2] < 0 || s[3] < 0) return false;
+        mols[4 * i] = (int32_t)ao; mols[4 * i + 1] = s[0]; mols[4 * i + 2] = (int32_t)bo; mols[4 * i + 3] = s[1];
+        p.nz[(size_t)2 * i] = s[2]; p.nz[(size_t)2 * i + 1] = s[3];
+        ao += s[0];
+        bo += s[1];
+        if (ao > INT32_MAX || bo > INT32_MAX) return false;
+    }
+    return plan_mols(mols.data(), p.nz.data(), B, target_blocks, p);
 }
 
 // ----------------------------------------------------------------------------------------------
@@ -418,14 +454,18 @@ struct Staged {
 
 inline size_t a256(size_t x) { return (x + 255) & ~size_t(255); }
 
-inline Staged stage_layout(const Batch &c, const Plan &p) {
+inline Staged stage_layout(size_t n_mols, size_t n_atoms, size_t n_pairs, size_t n_blocks) {
     Staged s;
-    const size_t bytes[6] = {c.mols.size() * 4, c.xn.size() * 4, c.atoms.size() * sizeof(WdAtomCode),
-                             c.pairs.size() * sizeof(WdBondPair), p.blocks.size() * 4, p.block_nnz.size() * 4};
+    const size_t bytes[6] = {n_mols * 16, n_mols * 4, n_atoms * sizeof(WdAtomCode), n_pairs * sizeof(WdBondPair),
+                             n_blocks * 32, n_blocks * 8};
     size_t o = 0;
     for (int k = 0; k < 6; ++k) { s.off[k] = o; o = a256(o + bytes[k]); }
     s.total = std::max<size_t>(o, 256);
     return s;
+}
+
+inline Staged stage_layout(const Batch &c, const Plan &p) {
+    return stage_layout(c.xn.size(), c.atoms.size(), c.pairs.size(), (size_t)p.n_blocks());
 }
 
 inline void stage_copy(const Batch &c, const Plan &p, const Staged &s, uint8_t *dst) {

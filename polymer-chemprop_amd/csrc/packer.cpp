@@ -693,6 +693,82 @@ PyObject *compact_stage(PyObject *, PyObject *args) {
     return nullptr;
 }
 
+// compact_entries(mols, xn, atoms, pairs, fa, fb) -> int32 [B][2] bytes: every molecule's msg_gather and
+// atom_gather entries (compact::mol_entries), what a resident table keeps per molecule for compact_plan;
+// None when a molecule exceeds a block
+PyObject *compact_entries(PyObject *, PyObject *args) {
+    PyObject *o[4];
+    int fa, fb;
+    if (!PyArg_ParseTuple(args, "OOOOii", &o[0], &o[1], &o[2], &o[3], &fa, &fb)) return nullptr;
+    try {
+        compact::Batch c;
+        batch_from(o[0], o[1], o[2], o[3], fa, fb, c);
+        const int64_t B = c.n_mols();
+        std::vector<int32_t> nnz((size_t)B * 2, 0);
+        for (int64_t i = 0; i < B; ++i) {
+            const int64_t an = c.mols[4 * i + 1], bo = c.mols[4 * i + 2], bn = c.mols[4 * i + 3];
+            if (bn > compact::BLK_BONDS || an > compact::BLK_ATOMS ||
+                !compact::mol_entries(c.pairs.data() + (bo - 1) / 2, bn / 2, an, nnz[(size_t)2 * i], nnz[(size_t)2 * i + 1]))
+                Py_RETURN_NONE;
+        }
+        return bytes_of(nnz.data(), nnz.size() * 4);
+    } catch (const PyErrAlready &) {
+    } catch (const std::exception &e) {
+        PyErr_SetString(PyExc_RuntimeError, e.what());
+    }
+    if (!PyErr_Occurred()) PyErr_SetString(PyExc_RuntimeError, "compact_entries failed");
+    return nullptr;
+}
+
+// compact_plan(sizes, target_blocks, dst_address, capacity) -> None (a molecule exceeds a block) |
+// (copied, (n_mols, n_atoms, n_bonds, n_blocks, nnz_msg, nnz_agg), offsets[6], total, (mols, blocks, block_nnz
+// offsets in dst), (blk_max_bonds, blk_max_atoms)): the plan of the batch whose molecules have the int32 rows
+// sizes [B][4] = {n_atoms, n_bonds, nnz_msg, nnz_agg}, exactly what compact_stage gives for the assembled batch.
+// The three host-made sections go to dst (host memory, e.g. pinned) as mols | blocks | block_nnz, each 256-byte
+// aligned; blocks and block_nnz lie as far apart as in the image, so the pair uploads as one copy.
+PyObject *compact_plan(PyObject *, PyObject *args) {
+    PyObject *o_sizes;
+    int target;
+    unsigned long long dst;
+    Py_ssize_t cap;
+    if (!PyArg_ParseTuple(args, "OiKn", &o_sizes, &target, &dst, &cap)) return nullptr;
+    try {
+        In<int32_t> sizes(o_sizes, "i", "sizes");
+        if (sizes.n % 4) fail(PyExc_ValueError, "compact_plan: sizes is int32 [B][4]");
+        const int64_t B = sizes.n / 4;
+        std::vector<int32_t> mols;
+        compact::Plan p;
+        if (!compact::plan_sizes(sizes.p, B, target, mols, p)) Py_RETURN_NONE;
+        int64_t V1 = 1, E1 = 1;
+        int32_t mb = 0, ma = 0;
+        if (B) { V1 = mols[4 * (B - 1)] + mols[4 * (B - 1) + 1]; E1 = mols[4 * (B - 1) + 2] + mols[4 * (B - 1) + 3]; }
+        for (int k = 0; k < p.n_blocks(); ++k) {
+            mb = std::max(mb, p.blocks[(size_t)8 * k + 1]);
+            ma = std::max(ma, p.blocks[(size_t)8 * k + 3]);
+        }
+        const compact::Staged s = compact::stage_layout((size_t)B, (size_t)V1, (size_t)(E1 - 1) / 2, (size_t)p.n_blocks());
+        const size_t h_blocks = compact::a256(mols.size() * 4), h_nnz = h_blocks + (s.off[5] - s.off[4]);
+        const size_t h_total = std::max<size_t>(compact::a256(h_nnz + p.block_nnz.size() * 4), 256);
+        const bool fits = dst && (Py_ssize_t)h_total <= cap;
+        if (fits) {
+            uint8_t *d = reinterpret_cast<uint8_t *>(dst);
+            std::memcpy(d, mols.data(), mols.size() * 4);
+            std::memcpy(d + h_blocks, p.blocks.data(), p.blocks.size() * 4);
+            std::memcpy(d + h_nnz, p.block_nnz.data(), p.block_nnz.size() * 4);
+        }
+        return Py_BuildValue("(O(iiiiLL)(nnnnnn)n(nnn)(ii))", fits ? Py_True : Py_False, (int)B, (int)V1, (int)E1,
+                             p.n_blocks(), (long long)p.nnz_msg, (long long)p.nnz_agg, (Py_ssize_t)s.off[0],
+                             (Py_ssize_t)s.off[1], (Py_ssize_t)s.off[2], (Py_ssize_t)s.off[3], (Py_ssize_t)s.off[4],
+                             (Py_ssize_t)s.off[5], (Py_ssize_t)s.total, (Py_ssize_t)0, (Py_ssize_t)h_blocks,
+                             (Py_ssize_t)h_nnz, (int)mb, (int)ma);
+    } catch (const PyErrAlready &) {
+    } catch (const std::exception &e) {
+        PyErr_SetString(PyExc_RuntimeError, e.what());
+    }
+    if (!PyErr_Occurred()) PyErr_SetString(PyExc_RuntimeError, "compact_plan failed");
+    return nullptr;
+}
+
 // generate_stage(kind, B, seed, target_blocks, dst_address, capacity) -> as compact_stage, plus the
 // generated (mols, xn, atoms, pairs) when keep is set; generation, plan and copy run without the GIL
 // (the streaming producer thread, bench.py / chemprop_amd.stream)
@@ -751,6 +827,11 @@ PyMethodDef methods[] = {
     {"compact_generate", compact_generate, METH_VARARGS, "compact_generate(kind, B, seed) -> (mols, xn, atoms, pairs)"},
     {"compact_stage", compact_stage, METH_VARARGS,
      "compact_stage(mols, xn, atoms, pairs, fa, fb, target_blocks, dst, capacity) -> plan + upload image"},
+    {"compact_entries", compact_entries, METH_VARARGS,
+     "compact_entries(mols, xn, atoms, pairs, fa, fb) -> int32 [B][2] (msg, agg) entries per molecule | None"},
+    {"compact_plan", compact_plan, METH_VARARGS,
+     "compact_plan(sizes, target_blocks, dst, capacity) -> the plan of a batch from its molecules' sizes + its "
+     "host-made image sections (mols | blocks | block_nnz)"},
     {"generate_stage", generate_stage, METH_VARARGS,
      "generate_stage(kind, B, seed, target_blocks, dst, capacity[, keep]) -> generated batch's plan + upload image"},
     {nullptr, nullptr, 0, nullptr}};

@@ -40,6 +40,7 @@
 #include "ensemble.hpp"
 #include "evaluate.hpp"
 #include "atom_desc.hpp"
+#include "graph_table.hpp"
 
 using namespace wd;
 
@@ -1963,6 +1964,43 @@ int wdmpnn_desc_rows(const WdDescRows *r, void *stream) {
     A.n_atoms = g->n_atoms;
     hipLaunchKernelGGL(desc_rows_kernel, dim3(ew_blocks((size_t)r->rows * r->ld)), dim3(256), 0, (hipStream_t)stream, A);
     WD_CHECK_LAUNCH("desc_rows");
+    return 0;
+}
+
+int wdmpnn_gather_compact(const WdGatherCompact *g, void *stream) {
+    WD_KERNELS_OK();
+    if (!g) return fail(WD_ERR_ARG, "gather_compact: null struct");
+    if (g->n_mols < 0 || g->n_rows < 0)
+        return fail(WD_ERR_SHAPE, "gather_compact: n_mols %d n_rows %d", g->n_mols, g->n_rows);
+    if (g->n_mols == 0) return 0;
+    if (g->n_rows < 1 || g->n_slots < 1 || g->slot0 < 0 || g->n_mols % g->n_rows ||
+        (int64_t)g->slot0 + g->n_mols / g->n_rows > g->n_slots)
+        return fail(WD_ERR_SHAPE, "gather_compact: needs n_rows >= 1, n_slots >= 1, slot0 >= 0, n_mols a multiple of "
+                    "n_rows, slot0 + n_mols / n_rows <= n_slots (got n_mols %d n_rows %d n_slots %d slot0 %d)",
+                    g->n_mols, g->n_rows, g->n_slots, g->slot0);
+    if (!g->t_atoms || !g->t_pairs || !g->t_xn || !g->t_first || !g->ids || !g->mols || !g->xn || !g->atoms || !g->pairs)
+        return fail(WD_ERR_ARG, "gather_compact: null table array, ids, mols or image section");
+    // (records move as 16-byte vectors: hipMalloc'd tables and 256-byte aligned image sections always qualify)
+    if (!aligned16(g->t_atoms) || !aligned16(g->t_pairs) || !aligned16(g->mols) || !aligned16(g->atoms) ||
+        !aligned16(g->pairs))
+        return fail(WD_ERR_ARG, "gather_compact: t_atoms, t_pairs, mols, atoms and pairs must be 16-byte aligned");
+    static_assert(sizeof(WdAtomCode) == 16 && sizeof(WdBondPair) == 16, "compact records are 16 bytes");
+    GatherCompactArgs A{};
+    A.t_atoms = reinterpret_cast<const uint4 *>(g->t_atoms);
+    A.t_pairs = reinterpret_cast<const uint4 *>(g->t_pairs);
+    A.t_xn = g->t_xn;
+    A.t_first = g->t_first;
+    A.ids = g->ids;
+    A.mols = g->mols;
+    A.atoms = reinterpret_cast<uint4 *>(g->atoms);
+    A.pairs = reinterpret_cast<uint4 *>(g->pairs);
+    A.xn = g->xn;
+    A.n_mols = g->n_mols;
+    A.n_rows = g->n_rows;
+    A.n_slots = g->n_slots;
+    A.slot0 = g->slot0;
+    hipLaunchKernelGGL(gather_compact_kernel, dim3((g->n_mols + 3) / 4), dim3(256), 0, (hipStream_t)stream, A);
+    WD_CHECK_LAUNCH("gather_compact");
     return 0;
 }
 
