@@ -44,6 +44,8 @@
 extern "C" {
 #endif
 
+/* (ABI 12 also covers the extra-feature fields appended at the tail of WdGraph and WdCompact: zero there means
+ * "none", and every caller zero-initialises the structs, so the number did not change when they grew.) */
 #define WDMPNN_ABI_VERSION 12
 #define WDMPNN_ELL_WIDTH 8
 
@@ -98,7 +100,8 @@ typedef struct WdCsr {
 /* Categorical codes of one atom / one bond pair (see "Compact graphs" below). */
 typedef struct WdAtomCode {
     uint8_t col[8];         /* columns of f_atoms holding 1.0, ascending; 0xFF = unused slot     */
-    float last;             /* f_atoms[atom_fdim - 1] (mass * 0.01)                              */
+    float last;             /* the last column of the base block, f_atoms[atom_fdim - atom_extra_dim - 1]
+                               (mass * 0.01; column 132 of the default 133)                      */
     float w;                /* w_atoms                                                           */
 } WdAtomCode;
 typedef struct WdBondPair {
@@ -185,6 +188,16 @@ typedef struct WdGraph {
      * workgroup carrying its block from the input layer to the readout (small_fwd.hpp). */
     int32_t blk_max_bonds;
     int32_t blk_max_atoms;
+    /* Optional, with atom_codes (appended under ABI 12; 0 / NULL = none): extra atom / bond features, the dense
+     * tail of the rows (featurization.py:436-440, 460-468: f_atoms = [base | atom_extra], f_bonds = [f_atoms[src] |
+     * bond bits | bond_extra]).  atom_extra [n_atoms][atom_extra_dim] natural atom rows (pad row 0 zero);
+     * bond_extra [(n_bonds - 1) / 2][bond_extra_dim] one row per bond pair, so directed bond b reads row
+     * (b - 1) >> 1.  atom_fdim / bond_fdim include them; the codes' columns and WdAtomCode.last address the base
+     * block of atom_fdim - atom_extra_dim columns.  The fused forward's embed adds them as a dense tail. */
+    const float *atom_extra;
+    const float *bond_extra;
+    int32_t atom_extra_dim;
+    int32_t bond_extra_dim;
 } WdGraph;
 
 /* nn.Module parameters of MPNEncoder (mpn.py:17-64); all device pointers, row-major like nn.Linear. */
@@ -334,7 +347,7 @@ int wdmpnn_build_bond_features(const float *f_atoms, int32_t ld_atoms, int32_t a
  * ------------------------------------------------------------------------------------------------ */
 typedef struct WdCompact {
     int32_t n_mols, n_atoms, n_bonds, n_blocks;   /* n_atoms / n_bonds include the pad row        */
-    int32_t atom_fdim, bond_fdim;                 /* 133 / 147 by default (bond_fdim - atom_fdim <= 16) */
+    int32_t atom_fdim, bond_fdim;                 /* 133 / 147 by default (bond_fdim - atom_fdim - bond_extra_dim <= 16) */
     int32_t nnz_msg, nnz_agg;                     /* total entries of msg_gather / atom_gather    */
     const int32_t *mols;                          /* [n_mols][4]                                  */
     const float *xn;                              /* [n_mols] degree_of_polym                     */
@@ -342,6 +355,13 @@ typedef struct WdCompact {
     const WdBondPair *pairs;                      /* [(n_bonds - 1) / 2]                          */
     const int32_t *blocks;                        /* [n_blocks][8]                                */
     const int32_t *block_nnz;                     /* [n_blocks][2]                                */
+    /* Extra atom / bond features (appended under ABI 12; 0 / NULL = none): atom_fdim and bond_fdim include them,
+     * bond_fdim - atom_fdim - bond_extra_dim <= 16 are the bit columns, each dim <= 64.  atom_extra [n_atoms]
+     * [atom_extra_dim] fp32 natural rows (pad row 0 zero), bond_extra [(n_bonds - 1) / 2][bond_extra_dim] fp32
+     * one row per WdBondPair (both directed bonds carry the same values). */
+    int32_t atom_extra_dim, bond_extra_dim;
+    const float *atom_extra;
+    const float *bond_extra;
 } WdCompact;
 
 /* Device bytes of the graph wdmpnn_build_graph writes (one buffer, caller-allocated). */

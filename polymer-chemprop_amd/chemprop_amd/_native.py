@@ -81,7 +81,9 @@ class WdGraph(Structure):
                 ('msg_ell_idx', c_void_p), ('msg_ell_coef', c_void_p), ('atom_ell_idx', c_void_p),
                 ('atom_ell_coef', c_void_p), ('atom_codes', c_void_p), ('bond_src_blk', c_void_p),
                 ('bond_tail', c_void_p), ('atom_feat_sum_x6', c_void_p),
-                ('blk_max_bonds', c_int32), ('blk_max_atoms', c_int32)]
+                ('blk_max_bonds', c_int32), ('blk_max_atoms', c_int32),
+                ('atom_extra', c_void_p), ('bond_extra', c_void_p), ('atom_extra_dim', c_int32),
+                ('bond_extra_dim', c_int32)]
 
 
 class WdParams(Structure):
@@ -101,7 +103,8 @@ class WdCompact(Structure):
     _fields_ = [('n_mols', c_int32), ('n_atoms', c_int32), ('n_bonds', c_int32), ('n_blocks', c_int32),
                 ('atom_fdim', c_int32), ('bond_fdim', c_int32), ('nnz_msg', c_int32), ('nnz_agg', c_int32),
                 ('mols', c_void_p), ('xn', c_void_p), ('atoms', c_void_p), ('pairs', c_void_p), ('blocks', c_void_p),
-                ('block_nnz', c_void_p)]
+                ('block_nnz', c_void_p), ('atom_extra_dim', c_int32), ('bond_extra_dim', c_int32),
+                ('atom_extra', c_void_p), ('bond_extra', c_void_p)]
 
 
 class WdFeedSpec(Structure):

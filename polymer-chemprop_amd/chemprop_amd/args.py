@@ -25,6 +25,12 @@ class TrainArgs:
     atom_descriptors_size: int = 0
     atom_descriptors_path: Optional[str] = None      # args.py:99 (the .npz of per-molecule descriptor arrays)
     no_atom_descriptor_scaling: bool = False         # args.py:236
+    # extra atom / bond features appended to the f_atoms / f_bonds rows (atom_descriptors == 'feature',
+    # --bond_features_path): the widths the encoder was built for (args.py:238-243, 590-594)
+    atom_features_size: int = 0
+    bond_features_size: int = 0
+    bond_features_path: Optional[str] = None         # args.py:105
+    no_bond_features_scaling: bool = False           # args.py:232
     device: torch.device = field(default_factory=lambda: torch.device('cuda' if torch.cuda.is_available() else 'cpu'))
     # MPN (mpn.py:189-208)
     features_only: bool = False

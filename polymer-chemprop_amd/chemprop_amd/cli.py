@@ -152,14 +152,15 @@ def _plain(v):
 
 def save_checkpoint(path: str, model, scaler: Optional[StandardScaler] = None,
                     features_scaler: Optional[StandardScaler] = None, args=None,
-                    atom_descriptor_scaler: Optional[StandardScaler] = None) -> None:
+                    atom_descriptor_scaler: Optional[StandardScaler] = None,
+                    bond_feature_scaler: Optional[StandardScaler] = None) -> None:
     """utils.py:47-73: {'args', 'state_dict', 'data_scaler', 'features_scaler', 'atom_descriptor_scaler',
     'bond_feature_scaler'}; every value a plain type (weights_only-loadable)."""
     a = {} if args is None else {k: _plain(v) for k, v in (vars(args) if not isinstance(args, dict) else args).items()}
     torch.save({'args': a, 'state_dict': model.state_dict(), 'data_scaler': _scaler_to_dict(scaler),
                 'features_scaler': _scaler_to_dict(features_scaler),
                 'atom_descriptor_scaler': _scaler_to_dict(atom_descriptor_scaler),
-                'bond_feature_scaler': None}, path)
+                'bond_feature_scaler': _scaler_to_dict(bond_feature_scaler)}, path)
 
 
 def load_checkpoint(path: str, device=None):
@@ -175,6 +176,7 @@ def load_checkpoint(path: str, device=None):
     fields = set(TrainArgs.__dataclass_fields__)
     kw = {k: v for k, v in state['args'].items() if k in fields and k != 'device'}
     args = TrainArgs(**kw, device=torch.device(device) if device is not None else torch.device('cpu'))
+    set_feature_sizes(args)  # (the encoder's row widths: the extra atom / bond features the model was trained with)
     model = MoleculeModel(args)
     model.load_state_dict(sd)
     return model.to(args.device)
@@ -403,7 +405,17 @@ def read_csv_molecules(path: str, number_of_molecules: int):
     return header, smiles, targets
 
 
-def check_number_of_molecules(n: int, extra_graphs_path, atom_descriptors=None) -> None:
+def set_feature_sizes(args) -> None:
+    """The widths ``MPN`` takes from ``get_atom_fdim`` / ``get_bond_fdim`` for a model of these args (train /
+    make_predictions call ``set_extra_atom_fdim(args.atom_features_size)`` and ``set_extra_bond_fdim`` the same
+    way): the extra atom / bond feature columns, 0 without them."""
+    from .featurization import set_extra_atom_fdim, set_extra_bond_fdim
+    feature = getattr(args, 'atom_descriptors', None) == 'feature'
+    set_extra_atom_fdim(int(getattr(args, 'atom_features_size', 0) or 0) if feature else 0)
+    set_extra_bond_fdim(int(getattr(args, 'bond_features_size', 0) or 0))
+
+
+def check_number_of_molecules(n: int, extra_graphs_path, atom_descriptors=None, bond_features_path=None) -> None:
     """``--number_of_molecules`` in 1 .. 8 with one graph file per molecule (``--graphs_path`` for the first,
     ``--extra_graphs_path`` for the others), and no atom descriptors with several molecules (the reference's own
     refusal, mpn.py:249-251)."""
@@ -416,6 +428,9 @@ def check_number_of_molecules(n: int, extra_graphs_path, atom_descriptors=None) 
     if n > 1 and atom_descriptors is not None:
         raise ValueError('Atom descriptors are currently only supported with one molecule per input (i.e., '
                          'number_of_molecules = 1).')
+    if n > 1 and bond_features_path is not None:
+        raise ValueError('Bond descriptors are currently only supported with one molecule per input (i.e., '
+                         'number_of_molecules = 1): --bond_features_path with --number_of_molecules > 1')
 
 
 def load_molecule_graphs(graphs_path: str, extra_graphs_path, n_rows: int, smiles_rows=None, polymer: bool = False):
@@ -509,22 +524,65 @@ def scale_features(features: np.ndarray, train_idx: List[int], no_features_scali
 
 
 def check_atom_descriptor_args(mode: Optional[str], path: Optional[str]) -> None:
-    """args.py:97-103, 596-607 for what this package reads: ``--atom_descriptors descriptor`` with an ``.npz``
-    file.  ``ValueError`` with the reason for everything else."""
+    """args.py:97-103, 596-607 for what this package reads: ``--atom_descriptors descriptor`` (rows joined to the
+    atom hidden states) or ``feature`` (columns appended to the atom features) with an ``.npz`` file.
+    ``ValueError`` with the reason for everything else."""
     if mode is None and path is None:
         return
     if mode is None:
         raise ValueError('--atom_descriptors_path is given without --atom_descriptors: say how the descriptors are '
-                         'used (--atom_descriptors descriptor)')
-    if mode == 'feature':
-        raise ValueError('--atom_descriptors feature is not supported: such descriptors become columns of the atom '
-                         'features when a molecule is featurised, and this tool reads graphs that are featurised '
-                         'already (--graphs_path); featurise with them, or use --atom_descriptors descriptor')
-    if mode != 'descriptor':
-        raise ValueError(f'--atom_descriptors {mode}: "descriptor" is the supported mode')
+                         'used (--atom_descriptors descriptor, or feature)')
+    if mode not in ('descriptor', 'feature'):
+        raise ValueError(f'--atom_descriptors {mode}: "descriptor" and "feature" are the supported modes')
     if path is None:
-        raise ValueError('--atom_descriptors descriptor needs --atom_descriptors_path')
+        raise ValueError(f'--atom_descriptors {mode} needs --atom_descriptors_path')
     check_atom_descriptors_path(path)
+
+
+def check_bond_features_args(path: Optional[str], no_scaling: bool = False) -> None:
+    """``--bond_features_path`` (args.py:105, 609-612): an ``.npz`` file; ``--no_bond_features_scaling`` only with it."""
+    if path is None:
+        if no_scaling:
+            raise ValueError('--no_bond_features_scaling is given without --bond_features_path')
+        return
+    check_atom_descriptors_path(path)
+
+
+def load_bond_features(path: str, graphs) -> List[np.ndarray]:
+    """``--bond_features_path`` (features/utils.py:76-78, data.py:131-142): the arrays of an ``.npz`` file in file
+    order, one float64 ``[n_bonds / 2][db]`` array per graph -- one row per undirected bond, in the order the
+    graph's bond pairs were created (``bond_features_extra[bond.GetIdx()]``, featurization.py:460-468), both
+    directed bonds of a pair taking the row -- NaN replaced by 0.  ``ValueError`` naming the first offender."""
+    check_atom_descriptors_path(path)
+    with np.load(path, allow_pickle=False) as container:
+        arrays = [np.asarray(container[key]) for key in container]
+    if len(arrays) != len(graphs):
+        raise ValueError(f'{path} holds {len(arrays)} bond feature arrays for {len(graphs)} molecules')
+    out = []
+    for k, (a, g) in enumerate(zip(arrays, graphs)):
+        if a.ndim != 2 or a.shape[1] < 1 or a.dtype.kind not in 'fiu':
+            raise ValueError(f'{path}: array {k} has shape {a.shape} ({a.dtype}); a numeric [n_bonds / 2][d] array is '
+                             'expected')
+        if a.shape[1] != arrays[0].shape[1]:
+            raise ValueError(f'{path}: array {k} has {a.shape[1]} features per bond, array 0 has '
+                             f'{arrays[0].shape[1]}')
+        if a.shape[0] != g.n_bonds // 2:
+            raise ValueError(f'{path}: array {k} has {a.shape[0]} rows, molecule {k} has {g.n_bonds // 2} bonds (the '
+                             'number of bonds is different from the length of the extra bond features)')
+        a = a.astype(np.float64)
+        out.append(np.where(np.isnan(a), 0.0, a))
+    return out
+
+
+def join_extra_features(graphs, atom_features=None, bond_features=None) -> list:
+    """The graphs with their (scaled) extra atom / bond features appended to the rows, once per run
+    (``featurization.widen_mol_graph``, the reference's concatenating mode): batches of the result are ordinary
+    ``BatchMolGraph`` s whose extras travel beside the compact codes."""
+    from .featurization import widen_mol_graph
+    if atom_features is None and bond_features is None:
+        return list(graphs)
+    return [widen_mol_graph(g, None if atom_features is None else atom_features[k],
+                            None if bond_features is None else bond_features[k]) for k, g in enumerate(graphs)]
 
 
 def check_atom_descriptors_path(path: str) -> None:
@@ -622,11 +680,20 @@ def parse_args(argv=None, spectra: bool = False) -> argparse.Namespace:
                          'split, NaN -> 0)')
     ap.add_argument('--atom_descriptors', default=None, choices=['feature', 'descriptor'],
                     help='descriptor: per-atom descriptors joined to the atom hidden states before the readout '
-                         '(feature is refused: it belongs to featurisation)')
+                         '(feature, extra columns of the atom features, is spelled --atom_features_path here)')
     ap.add_argument('--atom_descriptors_path', default=None,
                     help='.npz file: one [n_atoms][d] array per data row, in data order')
     ap.add_argument('--no_atom_descriptor_scaling', action='store_true',
                     help='feed the atom descriptors as they are (default: standardised on the training split)')
+    ap.add_argument('--atom_features_path', default=None,
+                    help='.npz file of extra atom features: one [n_atoms][d] array per data row, in data order, '
+                         'appended to the atom features of the graphs (the reference\'s --atom_descriptors feature '
+                         '--atom_descriptors_path; --no_atom_descriptor_scaling applies)')
+    ap.add_argument('--bond_features_path', default=None,
+                    help='.npz file of extra bond features: one [n_bonds / 2][d] array per data row, in data order, '
+                         'appended to the bond features of the graphs')
+    ap.add_argument('--no_bond_features_scaling', action='store_true',
+                    help='feed the extra bond features as they are (default: standardised on the training split)')
     ap.add_argument('--save_dir', required=True)
     ap.add_argument('--polymer', action='store_true')
     ap.add_argument('--split_type', default='random', choices=['random'])
@@ -682,8 +749,20 @@ def parse_args(argv=None, spectra: bool = False) -> argparse.Namespace:
     if a.dataset_type == 'spectra' and not a.spectra_target_floor > 0:
         raise ValueError('--spectra_target_floor must be greater than 0')
     check_metrics(a.dataset_type, ([a.metric] if a.metric else []) + list(a.extra_metrics))
+    if a.atom_descriptors == 'feature':  # (the command line keeps the refusal it always had for this spelling)
+        raise ValueError('--atom_descriptors feature is not taken on the command line: in the reference such descriptors '
+                         'become columns of the atom features when a molecule is featurised, and this tool reads graphs '
+                         'that are featurised already (--graphs_path); give the file as --atom_features_path F.npz and '
+                         'its scaled columns are joined to the graphs\' atom features, or use --atom_descriptors '
+                         'descriptor')
+    if a.atom_features_path is not None:  # the same run as the reference's --atom_descriptors feature
+        if a.atom_descriptors is not None or a.atom_descriptors_path is not None:
+            raise ValueError('--atom_features_path cannot be combined with --atom_descriptors / --atom_descriptors_path: '
+                             'a run has one kind of atom descriptors, as in the reference')
+        a.atom_descriptors, a.atom_descriptors_path = 'feature', a.atom_features_path
     check_atom_descriptor_args(a.atom_descriptors, a.atom_descriptors_path)
-    check_number_of_molecules(a.number_of_molecules, a.extra_graphs_path, a.atom_descriptors)
+    check_bond_features_args(a.bond_features_path, a.no_bond_features_scaling)
+    check_number_of_molecules(a.number_of_molecules, a.extra_graphs_path, a.atom_descriptors, a.bond_features_path)
     return a
 
 
@@ -692,7 +771,8 @@ def run_training(a: argparse.Namespace) -> Dict[str, list]:
     n_mols = int(getattr(a, 'number_of_molecules', 1))
     mpn_shared = bool(getattr(a, 'mpn_shared', False))
     extra_graphs = getattr(a, 'extra_graphs_path', None)
-    check_number_of_molecules(n_mols, extra_graphs, getattr(a, 'atom_descriptors', None))
+    check_number_of_molecules(n_mols, extra_graphs, getattr(a, 'atom_descriptors', None),
+                              getattr(a, 'bond_features_path', None))
     if n_mols == 1:
         header, smiles, targets = read_csv(a.data_path)
         smiles_rows = [[s] for s in smiles]
@@ -740,11 +820,24 @@ def run_training(a: argparse.Namespace) -> Dict[str, list]:
         features = phase_features if features is None else np.concatenate([features, phase_features], axis=1)
     # --atom_descriptors descriptor: every molecule's [n_atoms][d] rows, standardised on the training split's
     # stacked rows (run_training.py:118-123)
-    descriptors = atom_descriptor_scaler = None
+    descriptors = atom_descriptor_scaler = atom_features = None
     if getattr(a, 'atom_descriptors', None) is not None:
         check_atom_descriptor_args(a.atom_descriptors, a.atom_descriptors_path)
         descriptors, atom_descriptor_scaler = scale_atom_descriptors(
             load_atom_descriptors(a.atom_descriptors_path, graphs), train_idx, a.no_atom_descriptor_scaling)
+        if a.atom_descriptors == 'feature':  # columns of the atom rows, not rows for the descriptor layer
+            atom_features, descriptors = descriptors, None
+    # --bond_features_path: every molecule's [n_bonds / 2][db] rows, standardised the same way
+    # (run_training.py:124-128); the scaled extras are joined to the graphs once, here
+    bond_features = bond_feature_scaler = None
+    bond_features_path = getattr(a, 'bond_features_path', None)
+    if bond_features_path is not None:
+        check_bond_features_args(bond_features_path)
+        bond_features, bond_feature_scaler = scale_atom_descriptors(
+            load_bond_features(bond_features_path, graphs), train_idx,
+            bool(getattr(a, 'no_bond_features_scaling', False)))
+    if atom_features is not None or bond_features is not None:
+        graphs = join_extra_features(graphs, atom_features, bond_features)
     args = TrainArgs(hidden_size=a.hidden_size, depth=a.depth, dropout=a.dropout, activation=a.activation,
                      aggregation=a.aggregation, aggregation_norm=a.aggregation_norm, bias=a.bias,
                      undirected=a.undirected, ffn_num_layers=a.ffn_num_layers,
@@ -759,13 +852,20 @@ def run_training(a: argparse.Namespace) -> Dict[str, list]:
                      no_features_scaling=bool(a.no_features_scaling),
                      use_input_features=features is not None,
                      features_size=0 if features is None else int(features.shape[1]),
-                     atom_descriptors=None if descriptors is None else 'descriptor',
+                     atom_descriptors='feature' if atom_features is not None else
+                     None if descriptors is None else 'descriptor',
                      atom_descriptors_size=0 if descriptors is None else int(descriptors[0].shape[1]),
-                     atom_descriptors_path=None if descriptors is None else a.atom_descriptors_path,
+                     atom_descriptors_path=None if descriptors is None and atom_features is None
+                     else a.atom_descriptors_path,
                      no_atom_descriptor_scaling=bool(getattr(a, 'no_atom_descriptor_scaling', False)),
+                     atom_features_size=0 if atom_features is None else int(atom_features[0].shape[1]),
+                     bond_features_size=0 if bond_features is None else int(bond_features[0].shape[1]),
+                     bond_features_path=bond_features_path,
+                     no_bond_features_scaling=bool(getattr(a, 'no_bond_features_scaling', False)),
                      polymer=bool(a.polymer), ensemble_size=a.ensemble_size, task_names=list(header[n_mols:]),
                      number_of_molecules=n_mols, mpn_shared=mpn_shared,
                      device_metrics=bool(getattr(a, 'device_metrics', False)))
+    set_feature_sizes(args)  # (MPN takes its row widths from get_atom_fdim / get_bond_fdim)
     torch.manual_seed(a.pytorch_seed)
     scaler = None
     train_targets = [targets[i] for i in train_idx]
@@ -787,7 +887,7 @@ def run_training(a: argparse.Namespace) -> Dict[str, list]:
     loss_func = get_loss_func(a.dataset_type, a.alternative_loss_function)
 
     def save(path, model):
-        save_checkpoint(path, model, scaler, features_scaler, args, atom_descriptor_scaler)
+        save_checkpoint(path, model, scaler, features_scaler, args, atom_descriptor_scaler, bond_feature_scaler)
 
     def batch_targets(pos):
         return train_targets[pos] if spectra else [train_targets[p] for p in pos]
@@ -1026,6 +1126,9 @@ def _prediction_parser(prog: str, description: str) -> argparse.ArgumentParser:
     ap.add_argument('--atom_descriptors_path', default=None,
                     help='.npz file of the atom descriptors the models were trained with (one [n_atoms][d] array '
                          'per CSV row); the mode, the width and the scaler come from each checkpoint')
+    ap.add_argument('--bond_features_path', default=None,
+                    help='.npz file of the extra bond features the models were trained with (one [n_bonds / 2][d] '
+                         'array per CSV row); the width and the scaler come from each checkpoint')
     ap.add_argument('--batch_size', type=int, default=50)
     ap.add_argument('--gpu', type=int, default=0)
     return ap
@@ -1039,6 +1142,8 @@ def _check_prediction_args(a: argparse.Namespace) -> argparse.Namespace:
         raise ValueError('--batch_size must be at least 1')
     if a.atom_descriptors_path is not None:
         check_atom_descriptors_path(a.atom_descriptors_path)
+    if a.bond_features_path is not None:
+        check_atom_descriptors_path(a.bond_features_path)
     return a
 
 
@@ -1200,19 +1305,33 @@ def _prediction_graphs(a: argparse.Namespace, info: Dict[str, object], header: L
                                 [r[:n_mols] for r in rows], bool(info['polymer']))
 
 
-def _prediction_descriptors(a: argparse.Namespace, paths: List[str], graphs):
-    """The raw atom descriptors of a prediction run, or None: ``--atom_descriptors_path`` must be given exactly
-    when the checkpoints were trained with ``--atom_descriptors descriptor`` (their stored args say)."""
+def _prediction_descriptors(a: argparse.Namespace, paths: List[str], graphs) -> Dict[str, object]:
+    """The raw per-atom / per-bond inputs of a prediction run as keyword arguments of ``predict_ensemble`` /
+    ``molecule_fingerprint``: ``atom_descriptors`` (checkpoints trained with ``--atom_descriptors descriptor``),
+    ``atom_features`` (``feature``) and ``bond_features`` (``--bond_features_path``), each None when the checkpoints
+    were trained without.  A file must be given exactly when they were trained with it (their stored args say)."""
     state = torch.load(paths[0], map_location='cpu', weights_only=True)
     mode = state['args'].get('atom_descriptors')
     path = getattr(a, 'atom_descriptors_path', None)
+    out = {'atom_descriptors': None, 'atom_features': None, 'bond_features': None}
     if mode is None:
         if path is not None:
             raise ValueError(f'{paths[0]} was trained without atom descriptors, but --atom_descriptors_path is given')
-        return None
-    if path is None:
+    elif path is None:
         raise ValueError(f'{paths[0]} was trained with --atom_descriptors {mode}: give --atom_descriptors_path')
-    return load_atom_descriptors(path, graphs)
+    else:
+        out['atom_features' if mode == 'feature' else 'atom_descriptors'] = load_atom_descriptors(path, graphs)
+    trained = state['args'].get('bond_features_path') is not None or int(state['args'].get('bond_features_size') or 0)
+    bpath = getattr(a, 'bond_features_path', None)
+    if not trained:
+        if bpath is not None:
+            raise ValueError(f'{paths[0]} was trained without extra bond features, but --bond_features_path is given')
+    elif bpath is None:
+        raise ValueError(f'{paths[0]} was trained with --bond_features_path: give --bond_features_path')
+    else:
+        out['bond_features'] = load_bond_features(bpath, graphs)
+    out['bond_feature_scaling'] = not bool(state['args'].get('no_bond_features_scaling', False))
+    return out
 
 
 def _descriptor_scaling_of(paths: List[str]) -> bool:
@@ -1246,8 +1365,7 @@ def make_predictions(a: argparse.Namespace):
         paths, graphs, a.batch_size, features=features, phase_features=phase_features, phase_mask=phase_mask,
         variance=a.ensemble_variance, individual=a.individual_ensemble_predictions,
         device=torch.device('cuda', a.gpu), features_scaling=not a.no_features_scaling, embeddings=save_embeddings,
-        atom_descriptors=_prediction_descriptors(a, paths, graphs),
-        atom_descriptor_scaling=_descriptor_scaling_of(paths))
+        atom_descriptor_scaling=_descriptor_scaling_of(paths), **_prediction_descriptors(a, paths, graphs))
     if save_embeddings:  # (make_predictions.py:191-195: averaged across the ensemble, next to the predictions)
         parent = os.path.dirname(a.graph_embeddings_path)
         if parent:
@@ -1304,8 +1422,8 @@ def make_fingerprints(a: argparse.Namespace) -> np.ndarray:
     fp = molecule_fingerprint(paths, graphs, a.batch_size, a.fingerprint_type, features=features,
                               phase_features=phase_features, features_scaling=not a.no_features_scaling,
                               device=torch.device('cuda', a.gpu),
-                              atom_descriptors=_prediction_descriptors(a, paths, graphs),
-                              atom_descriptor_scaling=_descriptor_scaling_of(paths))
+                              atom_descriptor_scaling=_descriptor_scaling_of(paths),
+                              **_prediction_descriptors(a, paths, graphs))
     n_mols = info['number_of_molecules']
     write_fingerprints(a.preds_path, header[0] if n_mols == 1 else header[:n_mols],
                        [r[0] if n_mols == 1 else list(r[:n_mols]) for r in rows], fp)

@@ -116,6 +116,14 @@ class EnsembleAccumulator(PredictionSink):
         return out
 
 
+def set_feature_sizes_of(model) -> None:
+    """``set_extra_atom_fdim`` / ``set_extra_bond_fdim`` as the model was built (a batch without bonds takes its
+    bond row width from them)."""
+    from .featurization import set_extra_atom_fdim, set_extra_bond_fdim
+    set_extra_atom_fdim(int(getattr(model.encoder, 'atom_features_size', 0) or 0))
+    set_extra_bond_fdim(int(getattr(model.encoder, 'bond_features_size', 0) or 0))
+
+
 def make_batches(graphs: Sequence, batch_size: int, shared: bool = False) -> list:
     """The data set as ``BatchMolGraph`` s of ``batch_size`` molecules, in order.  Rows given as tuples or lists of
     N ``MolGraph`` s (a model of N molecules per input) become ``slots.SlotBatch`` es, with their merged graph
@@ -194,6 +202,46 @@ def model_atom_descriptors(item, model, atom_descriptors, device, scaling: bool 
     return AtomDescriptorTable(arrays, device, scaler)
 
 
+def model_graphs(item, model, graphs, atom_features=None, bond_features=None, atom_scaling: bool = True,
+                 bond_scaling: bool = True, k: int = 0):
+    """The rows' graphs as model ``k`` sees them (make_predictions.py:143-153): the raw extra atom features
+    (``[n_atoms][da]`` per row) and extra bond features (``[n_bonds / 2][db]`` per row) through that model's own
+    ``atom_descriptor_scaler`` / ``bond_feature_scaler`` (found as ``model_atom_descriptors`` finds its scaler:
+    the checkpoint at ``item``, or ``item[3]`` / ``item[4]`` of a tuple), appended to the graphs' rows
+    (``featurization.widen_mol_graph``).  ``graphs`` itself for a model trained without either.  ``ValueError`` when
+    the model needs features and gets none, gets features it does not take, or another width than it was trained
+    on."""
+    from .featurization import widen_mol_graph
+    mpn = model.encoder
+    sizes = (int(getattr(mpn, 'atom_features_size', 0) or 0), int(getattr(mpn, 'bond_features_size', 0) or 0))
+    given = (atom_features, bond_features)
+    names = (('extra atom features', '--atom_descriptors_path'), ('extra bond features', '--bond_features_path'))
+    for size, x, (what, flag) in zip(sizes, given, names):
+        if size and x is None:
+            raise ValueError(f'model {k} was trained with {what}: give {flag} to predict')
+        if not size and x is not None:
+            raise ValueError(f'model {k} was trained without {what}, but they were given')
+    if not any(sizes):
+        return graphs
+    scalers = [None, None]
+    if isinstance(item, (str, bytes)) or hasattr(item, '__fspath__'):
+        from . import cli
+        scalers = list(cli.load_scalers(str(item))[2:4])
+    elif isinstance(item, (tuple, list)):
+        scalers = [item[3] if len(item) > 3 else None, item[4] if len(item) > 4 else None]
+    out = []
+    for size, x, scaler, scaling, (what, _) in zip(sizes, given, scalers, (atom_scaling, bond_scaling), names):
+        if x is None:
+            out.append(None)
+            continue
+        arrays = [np.where(np.isnan(a), 0.0, a) for a in (np.asarray(a, dtype=np.float64) for a in x)]
+        if arrays and arrays[0].ndim == 2 and arrays[0].shape[1] != size:
+            raise ValueError(f'model {k} was trained with {size} {what} per row and {arrays[0].shape[1]} were given')
+        out.append([scaler.transform(a) for a in arrays] if scaler is not None and scaling else arrays)
+    return [widen_mol_graph(g, None if out[0] is None else out[0][i], None if out[1] is None else out[1][i])
+            for i, g in enumerate(graphs)]
+
+
 def model_features(model, features, features_scaler, phase_features, k: int = 0) -> Optional[np.ndarray]:
     """The input feature rows as model ``k`` sees them: the raw ``features`` through that model's own
     ``features_scaler`` (NaN -> 0; as they are without one), then the phase features, unscaled, as
@@ -224,7 +272,8 @@ def model_features(model, features, features_scaler, phase_features, k: int = 0)
 def predict_ensemble(checkpoints_or_models, graphs: Sequence, batch_size: int, features=None, phase_features=None,
                      phase_mask=None, variance: bool = False, individual: bool = False, device=None,
                      n_models: Optional[int] = None, features_scaling: bool = True, embeddings: bool = False,
-                     atom_descriptors=None, atom_descriptor_scaling: bool = True):
+                     atom_descriptors=None, atom_descriptor_scaling: bool = True, atom_features=None,
+                     bond_features=None, bond_feature_scaling: bool = True):
     """The ensemble's predictions of ``graphs`` (``MolGraph`` records, one per row): ``(mean, variance,
     individual)`` as float64 numpy arrays, ``[N][W]``, ``[N][W]`` (for spectra models the per-row pairwise SID
     ``[N]``; None without ``variance``) and ``[M][N][W]`` (None without ``individual``).  W is the flat output width:
@@ -244,7 +293,11 @@ def predict_ensemble(checkpoints_or_models, graphs: Sequence, batch_size: int, f
 
     ``atom_descriptors``: one raw ``[n_atoms][d]`` array per row for models trained with ``--atom_descriptors
     descriptor``; every model builds its own device table with its own ``atom_descriptor_scaler``
-    (``model_atom_descriptors``; ``atom_descriptor_scaling=False``: as they are)."""
+    (``model_atom_descriptors``; ``atom_descriptor_scaling=False``: as they are).
+
+    ``atom_features`` / ``bond_features``: one raw ``[n_atoms][da]`` / ``[n_bonds / 2][db]`` array per row for models
+    trained with ``--atom_features_path`` / ``--bond_features_path``; every model sees the graphs widened by
+    them through its own scalers (``model_graphs``), batched once per model."""
     device = torch.device('cuda', 0) if device is None else torch.device(device)
     if n_models is None and hasattr(checkpoints_or_models, '__len__'):
         n_models = len(checkpoints_or_models)
@@ -256,9 +309,14 @@ def predict_ensemble(checkpoints_or_models, graphs: Sequence, batch_size: int, f
     for k, item in enumerate(checkpoints_or_models):
         model, data_scaler, features_scaler = _open_model(item, device)
         model.eval()
+        set_feature_sizes_of(model)
+        own = model_graphs(item, model, graphs, atom_features, bond_features, atom_descriptor_scaling,
+                           bond_feature_scaling, k)
+        if own is not graphs:  # (extra features through this model's scalers: its own batches)
+            batches = None
         if batches is None:  # (rows of several molecules: with the merged graphs a shared encoder runs once over)
             from .slots import shares_encoder
-            batches = make_batches(graphs, batch_size, shared=shares_encoder(model))
+            batches = make_batches(own, batch_size, shared=shares_encoder(model))
         is_spectra = bool(getattr(model, 'spectra', False))
         width = int([m for m in model.ffn if isinstance(m, torch.nn.Linear)][-1].out_features)
         if acc is None:

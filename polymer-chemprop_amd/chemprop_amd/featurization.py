@@ -186,8 +186,11 @@ class BatchMolGraph:
         columns + mass, binary bond columns, bonds in reverse pairs, featurization.py:190-250, 469-480)
         the batch also gets its compact codes (include/wdmpnn.h "Compact graphs", ~14 bytes per edge) and
         ``device_graph`` builds every device array from them on the GPU (``wdmpnn_build_graph``).
-        Other batches (extra / overwritten features, atom messages, molecules larger than a block) take
-        the host-built path: gather lists packed here, fp32 rows uploaded.
+        Extra atom / bond features in the reference's concatenating mode (rows wider than the default
+        133 / 14 columns, featurization.py:436-440, 460-468) ride along as two small dense arrays beside the
+        codes (at most 64 columns each; both directed bonds of a pair must hold the same values).
+        Other batches (overwritten features, extras beyond the caps, atom messages, molecules larger than a
+        block) take the host-built path: gather lists packed here, fp32 rows uploaded.
 
         ``block_target``: the molecule blocks a small batch is spread over at least (``molecule_blocks``).
         The default (BLK_TARGET) cuts a small batch into many part-filled blocks, so that ONE forward spreads
@@ -249,6 +252,7 @@ class BatchMolGraph:
         self.a2a = None
         self._device_cache: Dict[tuple, DeviceGraph] = {}
         self._compact = None  # (mols, xn, atoms, pairs) bytearrays, or None
+        self._compact_extra = None  # (atom_extra, bond_extra, da, db): the dense tails of a batch with extra features
         self._compact_why = 'disabled'
         if compact:
             self._compact_why = self._encode_compact(na, nb, device_bond_features)
@@ -260,20 +264,34 @@ class BatchMolGraph:
         tail_w = rows.shape[1] if tail_mode else rows.shape[1] - fa.shape[1]
         if tail_w < 0:
             return 'bond rows narrower than atom rows'
+        # columns past the default widths are extra features (narrower custom layouts: none)
+        da, db = max(0, fa.shape[1] - _PARAMS['ATOM_FDIM']), max(0, tail_w - _PARAMS['BOND_FDIM'])
+        if (da or db) and (self.overwrite_default_atom_features or self.overwrite_default_bond_features):
+            return 'overwrite_default_atom_features / overwrite_default_bond_features replace the coded columns'
         res = _packer().compact_encode(fa, rows, self._np['w_atoms'], self._np['w_bonds'], self._np['b2a'],
                                        self._np['b2revb'], self._deg, self._in_idx, na, nb,
-                                       np.asarray(self.degree_of_polym, np.float64), int(fa.shape[1]), int(tail_w))
+                                       np.asarray(self.degree_of_polym, np.float64), int(fa.shape[1]), int(tail_w),
+                                       int(da), int(db))
         if res[0] is None:
             return res[1]
-        self._compact = tuple(res)
+        self._compact = tuple(res[:4])
+        if da or db:
+            self._compact_extra = (res[4], res[5], int(da), int(db))
         self._compact_dims = (int(fa.shape[1]), int(fa.shape[1] + tail_w))
         return ''
 
     @classmethod
-    def from_compact(cls, mols, xn, atoms, pairs, atom_fdim: int = 133, bond_fdim: int = 147) -> 'BatchMolGraph':
+    def from_compact(cls, mols, xn, atoms, pairs, atom_fdim: int = 133, bond_fdim: int = 147, atom_extra=None,
+                     bond_extra=None, atom_extra_dim: int = 0, bond_extra_dim: int = 0) -> 'BatchMolGraph':
         """A batch given in compact form (e.g. ``chemprop_amd.stream``'s native generator): scope arrays
-        now, the reference's tables (f_atoms, f_bonds, a2b, ...) decoded natively on first access."""
+        now, the reference's tables (f_atoms, f_bonds, a2b, ...) decoded natively on first access.
+        ``atom_extra`` [n_atoms][atom_extra_dim] / ``bond_extra`` [pairs][bond_extra_dim] (fp32 buffers): the
+        extra-feature columns, the last ones of ``atom_fdim`` / ``bond_fdim``."""
         self = cls.__new__(cls)
+        self._compact_extra = None
+        if atom_extra_dim or bond_extra_dim:
+            self._compact_extra = (atom_extra if atom_extra is not None else b'',
+                                   bond_extra if bond_extra is not None else b'', int(atom_extra_dim), int(bond_extra_dim))
         self.overwrite_default_atom_features = False
         self.overwrite_default_bond_features = False
         self.atom_fdim, self.bond_fdim = int(atom_fdim), int(bond_fdim)
@@ -314,7 +332,7 @@ class BatchMolGraph:
     def _decode_compact(self) -> None:
         fa_w, fb_w = self._compact_dims
         (f_atoms, tail, w_atoms, w_bonds, b2a, b2revb, deg, in_idx, _, _) = \
-            _packer().compact_decode(*self._compact, fa_w, fb_w)
+            _packer().compact_decode(*self._compact, fa_w, fb_w, *(self.__dict__.get('_compact_extra') or ()))
         V1, E1 = self.n_atoms, self.n_bonds
         self._np = dict(f_atoms=np.frombuffer(f_atoms, np.float32).reshape(V1, fa_w),
                         w_atoms=np.frombuffer(w_atoms, np.float32), w_bonds=np.frombuffer(w_bonds, np.float32),
@@ -474,14 +492,15 @@ class BatchMolGraph:
     def _device_graph_compact(self, device):
         """The compact path of ``device_graph``: plan + image (native, one pinned buffer), one H2D,
         one build launch; None when a molecule exceeds a block."""
-        host = torch.empty(_stage_bound(self._compact), dtype=torch.uint8, pin_memory=True)
+        extra = self.__dict__.get('_compact_extra') or ()
+        host = torch.empty(_stage_bound(self._compact + tuple(extra[:2])), dtype=torch.uint8, pin_memory=True)
         info = _packer().compact_stage(*self._compact, *self._compact_dims,
                                        getattr(self, 'block_target', BLK_TARGET), host.data_ptr(),
-                                       host.numel())
+                                       host.numel(), *extra)
         if info is None:
             return None
         assert info[0], 'staged image larger than its bound'
-        return upload_compact(device, host, info, *self._compact_dims)
+        return upload_compact(device, host, info, *self._compact_dims, extra_dims=tuple(extra[2:]))
 
     def device_graph(self, device, atom_messages: bool = False, bond_fdim: int = None,
                      atom_blocks: bool = True) -> DeviceGraph:
@@ -699,33 +718,38 @@ class BatchMolGraph:
 
 
 def upload_compact(device, staged: torch.Tensor, info, atom_fdim: int, bond_fdim: int,
-                   lean: bool = False) -> DeviceGraph:
+                   lean: bool = False, extra_dims=()) -> DeviceGraph:
     """H2D of a staged compact image (pinned host tensor from ``compact_stage`` / ``generate_stage``)
     on the current stream, then ``wdmpnn_build_graph`` into one device buffer: the DeviceGraph of the
     batch.  ``info`` = (copied, counts, offsets, total) as the native stage functions return it.
     ``lean``: an inference-only graph (WDMPNN_GRAPH_LEAN: no dense feature rows, planes or transposed
-    gathers); a training forward or an unblocked path on it raises NotImplementedError."""
-    _, (_, _, _, n_blocks, _, _), off, total = info
+    gathers); a training forward or an unblocked path on it raises NotImplementedError.
+    ``extra_dims`` = (da, db) of a batch with extra features: ``info`` then carries the offsets of its two
+    dense sections as a fifth element."""
+    _, (_, _, _, n_blocks, _, _), off, total = info[:4]
     buf = staged[:total].to(device, non_blocking=True)
     blk_max = None
     if n_blocks:  # the block plan's largest blocks, read from the staged image (WdGraph.blk_max_*)
         blk = np.frombuffer(staged.numpy(), np.int32, count=8 * n_blocks, offset=off[4]).reshape(n_blocks, 8)
         blk_max = (int(blk[:, 1].max()), int(blk[:, 3].max()))
-    return build_from_image(device, buf, info, blk_max, atom_fdim, bond_fdim, lean)
+    return build_from_image(device, buf, info, blk_max, atom_fdim, bond_fdim, lean, extra_dims)
 
 
 def build_from_image(device, buf: torch.Tensor, info, blk_max, atom_fdim: int, bond_fdim: int,
-                     lean: bool = False) -> DeviceGraph:
+                     lean: bool = False, extra_dims=()) -> DeviceGraph:
     """``wdmpnn_build_graph_ex`` on the current stream from a compact image already on the device (``buf``, laid
     out as ``info`` says; ``upload_compact`` copies one there, ``graph_table`` gathers one): the DeviceGraph of the
     batch, which keeps the image alive.  ``blk_max``: (largest block's bond rows, atom rows) of the plan, or None
     without blocks."""
-    _, (n_mols, n_atoms, n_bonds, n_blocks, nnz_msg, nnz_agg), off, total = info
+    _, (n_mols, n_atoms, n_bonds, n_blocks, nnz_msg, nnz_agg), off, total = info[:4]
     base = buf.data_ptr()
     c = _native.WdCompact()
     c.n_mols, c.n_atoms, c.n_bonds, c.n_blocks = n_mols, n_atoms, n_bonds, n_blocks
     c.atom_fdim, c.bond_fdim, c.nnz_msg, c.nnz_agg = atom_fdim, bond_fdim, nnz_msg, nnz_agg
     c.mols, c.xn, c.atoms, c.pairs, c.blocks, c.block_nnz = (base + o for o in off)
+    if extra_dims and any(extra_dims):  # the dense tails: the embed reads them from the image, like the codes
+        c.atom_extra_dim, c.bond_extra_dim = extra_dims
+        c.atom_extra, c.bond_extra = (base + o for o in info[4])
     L = _native.lib()
     nbytes = ctypes.c_size_t()
     _native.check(L.wdmpnn_graph_bytes(ctypes.byref(c), ctypes.byref(nbytes)), 'graph bytes')
@@ -746,10 +770,39 @@ def build_from_image(device, buf: torch.Tensor, info, blk_max, atom_fdim: int, b
     return dg
 
 
+def widen_mol_graph(g, atom_extra=None, bond_extra=None):
+    """A copy of the MolGraph-like ``g`` with extra features appended to its rows as the reference's
+    featuriser does in its concatenating mode (featurization.py:436-440, 460-468, 509-513, 609-617):
+    ``f_atoms[a] += atom_extra[a]`` and ``f_bonds[b] = f_atoms[src(b)] + bond columns + bond_extra[b // 2]``
+    (both directed bonds of a pair carry the pair's values).  ``atom_extra`` [n_atoms][da] / ``bond_extra``
+    [n_bonds / 2][db] float arrays, or None for none.  Rows come back as lists of Python floats holding fp32
+    values; everything else is shared with ``g``."""
+    import copy
+    def rows(x, n):
+        x = np.asarray(x, np.float32)
+        return x if x.ndim == 2 and len(x) == n else x.reshape(n, -1)
+
+    xa = None if atom_extra is None else rows(atom_extra, g.n_atoms)
+    xb = None if bond_extra is None else rows(bond_extra, g.n_bonds // 2)
+    out = copy.copy(g)
+    fa_w = len(g.f_atoms[0]) if g.n_atoms else 0
+    f_atoms = [list(r) for r in g.f_atoms]
+    if xa is not None and xa.shape[1]:
+        f_atoms = [r + x for r, x in zip(f_atoms, xa.tolist())]
+    f_bonds = []
+    for b, r in enumerate(g.f_bonds):
+        row = f_atoms[g.b2a[b]] + list(r[fa_w:])
+        if xb is not None and xb.shape[1]:
+            row = row + xb[b // 2].tolist()
+        f_bonds.append(row)
+    out.f_atoms, out.f_bonds = f_atoms, f_bonds
+    return out
+
+
 def _stage_bound(arrays) -> int:
     """Upper bound of a staged image's bytes (blocks <= molecules)."""
     n_mols = len(arrays[1]) // 4
-    return sum(len(a) for a in arrays) + 40 * (n_mols + 1) + 6 * 256
+    return sum(len(a) for a in arrays) + 40 * (n_mols + 1) + 8 * 256
 
 
 def mol2graph(mols, atom_features_batch=(None,), bond_features_batch=(None,),

@@ -16,7 +16,8 @@ import numpy as np
 import torch
 
 from . import _native
-from .ensemble import _open_model, make_batches, model_atom_descriptors, model_features
+from .ensemble import (_open_model, make_batches, model_atom_descriptors, model_features, model_graphs,
+                       set_feature_sizes_of)
 from .slots import shares_encoder
 from .features import FeatureTable
 from .predict import LATENT_TYPES, PredictionSink, device_predictions
@@ -132,7 +133,8 @@ def fingerprint_width(model, fingerprint_type: str) -> int:
 
 def molecule_fingerprint(checkpoints_or_models, graphs: Sequence, batch_size: int, fingerprint_type: str = 'MPN',
                          features=None, phase_features=None, features_scaling: bool = True, device=None,
-                         atom_descriptors=None, atom_descriptor_scaling: bool = True) -> np.ndarray:
+                         atom_descriptors=None, atom_descriptor_scaling: bool = True, atom_features=None,
+                         bond_features=None, bond_feature_scaling: bool = True) -> np.ndarray:
     """The fingerprints of ``graphs`` (``MolGraph`` records, one per row) under every model, float64 numpy
     ``[N][fp][M]`` as the reference's ``molecule_fingerprint`` returns them.  ``checkpoints_or_models``: checkpoint
     paths, ``(model, data_scaler, features_scaler)`` tuples or models (a sequence: the array's last axis is its
@@ -141,8 +143,9 @@ def molecule_fingerprint(checkpoints_or_models, graphs: Sequence, batch_size: in
     unscaled.  ``MPN``: fp = ``hidden_size * number_of_molecules``, the feature columns dropped; features are not
     needed, even for a model trained with them (the encoders alone run).  ``last_FFN``: fp = ``ffn_hidden_size``.
     ``atom_descriptors``: one raw ``[n_atoms][d]`` array per row for descriptor models, each model scaling them
-    with its own ``atom_descriptor_scaler`` (``ensemble.model_atom_descriptors``).  One host copy, after the last
-    model."""
+    with its own ``atom_descriptor_scaler`` (``ensemble.model_atom_descriptors``).  ``atom_features`` /
+    ``bond_features``: the raw extra atom / bond features of models trained with them, appended to the graphs' rows
+    through each model's own scalers (``ensemble.model_graphs``).  One host copy, after the last model."""
     device = torch.device('cuda', 0) if device is None else torch.device(device)
     items = list(checkpoints_or_models)
     if not items:
@@ -153,8 +156,13 @@ def molecule_fingerprint(checkpoints_or_models, graphs: Sequence, batch_size: in
     for k, item in enumerate(items):
         model, _, features_scaler = _open_model(item, device)
         model.eval()
+        set_feature_sizes_of(model)
+        own = model_graphs(item, model, graphs, atom_features, bond_features, atom_descriptor_scaling,
+                           bond_feature_scaling, k)
+        if own is not graphs:  # (extra features through this model's scalers: its own batches)
+            batches = None
         if batches is None:  # (rows of several molecules: with the merged graphs a shared encoder runs once over)
-            batches = make_batches(graphs, batch_size, shared=shares_encoder(model))
+            batches = make_batches(own, batch_size, shared=shares_encoder(model))
         width = fingerprint_width(model, fingerprint_type)
         if acc is None:
             acc = LatentAccumulator(n, width, device, n_models=len(items))

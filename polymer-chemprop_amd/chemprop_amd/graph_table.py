@@ -66,6 +66,9 @@ class GraphTable:
                         raise ValueError(f'GraphTable: {self._name(c0 + j)} does not encode compactly: {why}')
                 raise ValueError(f'GraphTable: molecules {c0} .. {c0 + len(chunk)} do not encode compactly: '
                                  f'{b._compact_why}')
+            if b._compact_extra is not None:
+                raise ValueError('GraphTable: extra atom / bond features (--atom_features_path, '
+                                 '--bond_features_path) are not supported with --resident_graphs')
             if self.dims is None:
                 self.dims = b._compact_dims
                 self._flags = (b.overwrite_default_atom_features, b.overwrite_default_bond_features,

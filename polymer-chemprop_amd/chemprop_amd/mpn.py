@@ -688,7 +688,11 @@ class MPN(nn.Module):
         self.features_only = args.features_only
         self.use_input_features = args.use_input_features
         self.device = args.device
-        self.atom_descriptors = args.atom_descriptors
+        # 'feature' mode (extra atom features, columns of the graphs' rows already) needs nothing of the model but
+        # its widths: only 'descriptor' is a model mode
+        self.atom_descriptors = args.atom_descriptors if args.atom_descriptors == 'descriptor' else None
+        self.atom_features_size = int(getattr(args, 'atom_features_size', 0) or 0)
+        self.bond_features_size = int(getattr(args, 'bond_features_size', 0) or 0)
         self.overwrite_default_atom_features = args.overwrite_default_atom_features
         self.overwrite_default_bond_features = args.overwrite_default_bond_features
         if self.features_only:
@@ -704,7 +708,7 @@ class MPN(nn.Module):
                 bond_features_batch: List[np.ndarray] = None) -> torch.FloatTensor:
         if type(batch[0]) != BatchMolGraph:
             batch = [[mols[i] for mols in batch] for i in range(len(batch[0]))]
-            if self.atom_descriptors == 'feature' and len(batch) > 1:
+            if (self.atom_features_size or self.bond_features_size) and len(batch) > 1:
                 raise NotImplementedError('Atom/bond descriptors are currently only supported with one molecule '
                                           'per input (i.e., number_of_molecules = 1).')
             batch = [mol2graph(b) for b in batch]

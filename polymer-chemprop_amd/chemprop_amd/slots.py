@@ -51,6 +51,10 @@ class SlotBatch(list):
             raise ValueError(f'SlotBatch: atom feature widths {sorted(atom_w)} and bond feature widths '
                              f'{sorted(bond_w)}: every slot needs the same')
         super().__init__(BatchMolGraph(m, **batch_kwargs) for m in mol_lists)
+        if n > 1 and any(b.__dict__.get('_compact_extra') for b in self):
+            # (the reference refuses them as well: atom / bond features need number_of_molecules == 1)
+            raise ValueError('SlotBatch: extra atom / bond features (--atom_features_path, '
+                             '--bond_features_path) are not supported with --number_of_molecules > 1')
         self.n_rows = sizes[0]
         self.merged: Optional[BatchMolGraph] = None
         if shared:

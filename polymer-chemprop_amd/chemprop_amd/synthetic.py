@@ -284,3 +284,32 @@ def random_descriptors(graphs: List[SynthMolGraph], size: int, seed: int) -> Lis
     """Per-molecule atom descriptor arrays for ``--atom_descriptors descriptor`` (mpn.py:77-79)."""
     rng = np.random.default_rng(seed)
     return [rng.standard_normal((g.n_atoms, size)).astype(np.float32) for g in graphs]
+
+
+def with_extra_features(graphs: List[SynthMolGraph], da: int, db: int, seed: int) -> List[SynthMolGraph]:
+    """Widened copies of ``graphs``: ``da`` extra columns per atom and ``db`` per undirected bond, appended as the
+    reference's featuriser appends ``atom_features_extra`` / ``bond_features_extra`` (featurization.py:436-440,
+    460-468): ``f_atoms = [133 | da]``, ``f_bonds = [f_atoms[src] | 14 | db]``, both directed bonds of a pair with
+    the pair's values.  Seeded standard-normal fp32 values (so negatives), with special values planted at fixed
+    positions of the batch's value stream (atoms first, then bonds; as many as fit): exact zeros, one value of
+    magnitude 1e3 and one denormal."""
+    from .featurization import widen_mol_graph
+    rng = np.random.default_rng([seed, da, db])
+    xa = [rng.standard_normal((g.n_atoms, da)).astype(np.float32) for g in graphs]
+    xb = [rng.standard_normal((g.n_bonds // 2, db)).astype(np.float32) for g in graphs]
+    special = (0.0, -1.0e3, 1.0e-40, 0.0, -0.0)  # (1e-40: denormal in fp32)
+    flat = [a.reshape(-1) for a in xa + xb if a.size]
+    total = sum(len(a) for a in flat)
+    for k, v in enumerate(special):
+        pos = (k * 7 + 1) % total if total else 0
+        for a in flat:
+            if pos < len(a):
+                a[pos] = np.float32(v)
+                break
+            pos -= len(a)
+    if db and flat:  # ... and one of each on the bond side too, when there are bonds
+        for a in xb:
+            if a.size >= 3:
+                a.reshape(-1)[:3] = np.array([0.0, 1.0e3, -1.0e-40], np.float32)
+                break
+    return [widen_mol_graph(g, a if da else None, b if db else None) for g, a, b in zip(graphs, xa, xb)]

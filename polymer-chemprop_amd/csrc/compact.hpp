@@ -18,10 +18,14 @@ namespace compact {
 
 struct Batch {
     int fa = 133, fb = 147;             // f_atoms / f_bonds widths (bond tail = fb - fa columns)
+    int da = 0, db = 0;                 // extra atom / bond feature columns, the dense tails: f_atoms row = [base fa - da
+                                        // | da], bond tail = [fb - fa - db bit columns | db]
     std::vector<int32_t> mols;          // [B][4] {atom_start, n_atoms, bond_start, n_bonds}
     std::vector<float> xn;              // [B]
     std::vector<WdAtomCode> atoms;      // [V + 1], row 0 = pad
     std::vector<WdBondPair> pairs;      // [E / 2]
+    std::vector<float> ax;              // [V + 1][da] extra atom features, row 0 = pad (zeros)
+    std::vector<float> bx;              // [E / 2][db] extra bond features, one row per pair
     int n_atoms() const { return (int)atoms.size(); }
     int n_bonds() const { return 1 + 2 * (int)pairs.size(); }
     int n_mols() const { return (int)xn.size(); }
@@ -40,12 +44,21 @@ inline WdAtomCode pad_atom() {
 // false (with a reason) when some row is not in the reference's categorical layout
 // ----------------------------------------------------------------------------------------------
 // tail rows are `row_w` floats wide: the bond columns are their last tail_w; when row_w > tail_w the
-// rows are whole f_bonds rows and their first fa columns must equal the source atom's row (checked)
-inline bool encode(int fa, int tail_w, int row_w, const float *f_atoms, const float *tail, const float *w_atoms,
+// rows are whole f_bonds rows and their first fa columns must equal the source atom's row (checked).
+// Extra features (the reference's concatenating mode, featurization.py:436-440, 460-468): the last da of the
+// fa atom columns and the last db of the tail_w bond columns are dense values, kept as fp32 beside the codes;
+// the code columns and `last` then address the base block of fa - da columns.
+constexpr int MAX_EXTRA = 64;
+inline bool encode(int fa, int tail_w, int row_w, int da, int db, const float *f_atoms, const float *tail, const float *w_atoms,
                    const float *w_bonds, const int64_t *b2a, const int64_t *b2revb, const int64_t *deg,
                    const int64_t *in_idx, const int64_t *na, const int64_t *nb, const double *xn, int64_t B,
                    Batch &out, std::string &why) {
-    if (fa < 2 || fa > 255 || tail_w < 0 || tail_w > 16 || (row_w != tail_w && row_w != fa + tail_w)) {
+    if (da < 0 || db < 0 || da > MAX_EXTRA || db > MAX_EXTRA) {
+        why = "extra feature widths (at most 64 extra atom and 64 extra bond columns)";
+        return false;
+    }
+    const int fa0 = fa - da, bits = tail_w - db;  // the base atom block, the binary bond columns
+    if (fa0 < 2 || fa0 > 255 || bits < 0 || bits > 16 || (row_w != tail_w && row_w != fa + tail_w)) {
         why = "feature widths";
         return false;
     }
@@ -53,16 +66,19 @@ inline bool encode(int fa, int tail_w, int row_w, const float *f_atoms, const fl
     out = Batch{};
     out.fa = fa;
     out.fb = fa + tail_w;
+    out.da = da;
+    out.db = db;
     int64_t V = 0, E = 0;
     for (int64_t i = 0; i < B; ++i) { V += na[i]; E += nb[i]; }
     out.atoms.resize((size_t)V + 1);
     out.atoms[0] = pad_atom();
+    out.ax.assign(((size_t)V + 1) * da, 0.f);
     for (int64_t a = 1; a <= V; ++a) {
         const float *r = f_atoms + (size_t)a * fa;
         WdAtomCode c = pad_atom();
         int n = 0;
-        for (int k0 = 0; k0 < fa - 1; k0 += 8) {  // skip all-zero groups of 8 columns (bit test, no float compare)
-            const int k1 = std::min(k0 + 8, fa - 1);
+        for (int k0 = 0; k0 < fa0 - 1; k0 += 8) {  // skip all-zero groups of 8 columns (bit test, no float compare)
+            const int k1 = std::min(k0 + 8, fa0 - 1);
             uint32_t any = 0;
             for (int k = k0; k < k1; ++k) { uint32_t u; std::memcpy(&u, r + k, 4); any |= u << 1; }  // ignores -0.0
             if (!any) continue;
@@ -72,7 +88,8 @@ inline bool encode(int fa, int tail_w, int row_w, const float *f_atoms, const fl
                 c.col[n++] = (uint8_t)k;
             }
         }
-        c.last = r[fa - 1];
+        c.last = r[fa0 - 1];
+        if (da) std::memcpy(&out.ax[(size_t)a * da], r + fa0, (size_t)da * 4);
         c.w = w_atoms[a];
         out.atoms[(size_t)a] = c;
     }
@@ -84,6 +101,7 @@ inline bool encode(int fa, int tail_w, int row_w, const float *f_atoms, const fl
     out.mols.resize((size_t)B * 4);
     out.xn.resize((size_t)B);
     out.pairs.reserve((size_t)E / 2);
+    out.bx.reserve((size_t)E / 2 * db);
     int64_t ao = 1, bo = 1;
     for (int64_t i = 0; i < B; ++i) {
         out.mols[4 * i] = (int32_t)ao; out.mols[4 * i + 1] = (int32_t)na[i];
@@ -102,7 +120,15 @@ inline bool encode(int fa, int tail_w, int row_w, const float *f_atoms, const fl
                 why = "bond rows do not start with their source atom row";
                 return false;
             }
-            for (int k = 0; k < tail_w; ++k) {
+            if (db) {  // the dense tail: one row per pair, so both directions must hold the same bits
+                const float *x1 = tail + (size_t)b1 * row_w + t0 + bits, *x2 = tail + (size_t)b2 * row_w + t0 + bits;
+                if (std::memcmp(x1, x2, (size_t)db * 4)) {
+                    why = "extra bond features differ between the two directions of a pair";
+                    return false;
+                }
+                out.bx.insert(out.bx.end(), x1, x1 + db);
+            }
+            for (int k = 0; k < bits; ++k) {
                 const float v1 = tail[(size_t)b1 * row_w + t0 + k], v2 = tail[(size_t)b2 * row_w + t0 + k];
                 if (v1 != v2 || (v1 != 0.f && v1 != 1.f)) { why = "bond columns not binary / not shared"; return false; }
                 if (v1 == 1.f) q.tail |= (uint16_t)(1u << k);
@@ -142,7 +168,7 @@ struct Dense {
 };
 
 inline void decode(const Batch &c, Dense &d) {
-    const int fa = c.fa, tw = c.fb - c.fa;
+    const int fa = c.fa, tw = c.fb - c.fa, da = c.da, db = c.db, fa0 = fa - da, bits = tw - db;
     const int64_t V1 = c.n_atoms(), E1 = c.n_bonds(), B = c.n_mols();
     d.f_atoms.assign((size_t)V1 * fa, 0.f);
     d.tail.assign((size_t)E1 * tw, 0.f);
@@ -158,7 +184,8 @@ inline void decode(const Batch &c, Dense &d) {
         float *r = &d.f_atoms[(size_t)a * fa];
         for (int k = 0; k < 8; ++k)
             if (cd.col[k] != 0xFF) r[cd.col[k]] = 1.f;
-        r[fa - 1] = cd.last;
+        r[fa0 - 1] = cd.last;
+        if (da) std::memcpy(r + fa0, &c.ax[(size_t)a * da], (size_t)da * 4);
         d.w_atoms[(size_t)a] = cd.w;
     }
     std::vector<int64_t> dst((size_t)E1, 0);
@@ -167,16 +194,21 @@ inline void decode(const Batch &c, Dense &d) {
         d.na[(size_t)i] = c.mols[4 * i + 1];
         d.nb[(size_t)i] = c.mols[4 * i + 3];
         for (int64_t lb = 0; lb < c.mols[4 * i + 3]; lb += 2) {
-            const WdBondPair &q = c.pairs[(size_t)((bo + lb - 1) / 2)];
+            const size_t pr = (size_t)((bo + lb - 1) / 2);
+            const WdBondPair &q = c.pairs[pr];
             const int64_t b1 = bo + lb, b2 = b1 + 1;
             d.b2a[(size_t)b1] = ao + q.a1; d.b2a[(size_t)b2] = ao + q.a2;
             dst[(size_t)b1] = ao + q.a2; dst[(size_t)b2] = ao + q.a1;
             d.b2revb[(size_t)b1] = b2; d.b2revb[(size_t)b2] = b1;
             d.w_bonds[(size_t)b1] = q.w12; d.w_bonds[(size_t)b2] = q.w21;
-            for (int k = 0; k < tw; ++k) {
+            for (int k = 0; k < bits; ++k) {
                 const float v = (float)((q.tail >> k) & 1);
                 d.tail[(size_t)b1 * tw + k] = v;
                 d.tail[(size_t)b2 * tw + k] = v;
+            }
+            if (db) {
+                std::memcpy(&d.tail[(size_t)b1 * tw + bits], &c.bx[pr * db], (size_t)db * 4);
+                std::memcpy(&d.tail[(size_t)b2 * tw + bits], &c.bx[pr * db], (size_t)db * 4);
             }
         }
     }
@@ -401,7 +433,8 @@ inline void add_molecule(Batch &c, Rng &r, int n_atoms, const EdgeList &edges, c
 // 2 = ZINC-like U{15..37} atoms (w = 1, Xn = 1)
 inline void generate(int kind, int B, uint64_t seed, Batch &c) {
     // (c's vectors keep their capacity: a producer thread reuses one Batch, no allocation per batch)
-    c.fa = 133; c.fb = 147;
+    c.fa = 133; c.fb = 147; c.da = c.db = 0;
+    c.ax.clear(); c.bx.clear();
     c.mols.clear(); c.xn.clear(); c.atoms.clear(); c.pairs.clear();
     const int amax = kind == 0 ? 48 : kind == 1 ? 9 : 37;
     c.atoms.reserve((size_t)B * amax + 1);
@@ -446,26 +479,28 @@ inline void generate(int kind, int B, uint64_t seed, Batch &c) {
 }
 
 // ----------------------------------------------------------------------------------------------
-// staged upload image: mols | xn | atoms | pairs | blocks | block_nnz, each 256-byte aligned
+// staged upload image: mols | xn | atoms | pairs | blocks | block_nnz | atom_extra | bond_extra, each
+// 256-byte aligned (the two extra-feature sections are empty without extras: the image is then unchanged)
 // ----------------------------------------------------------------------------------------------
 struct Staged {
-    size_t off[6] = {0, 0, 0, 0, 0, 0}, total = 0;
+    size_t off[8] = {0, 0, 0, 0, 0, 0, 0, 0}, total = 0;
 };
 
 inline size_t a256(size_t x) { return (x + 255) & ~size_t(255); }
 
-inline Staged stage_layout(size_t n_mols, size_t n_atoms, size_t n_pairs, size_t n_blocks) {
+inline Staged stage_layout(size_t n_mols, size_t n_atoms, size_t n_pairs, size_t n_blocks, size_t da = 0,
+                           size_t db = 0) {
     Staged s;
-    const size_t bytes[6] = {n_mols * 16, n_mols * 4, n_atoms * sizeof(WdAtomCode), n_pairs * sizeof(WdBondPair),
-                             n_blocks * 32, n_blocks * 8};
+    const size_t bytes[8] = {n_mols * 16, n_mols * 4, n_atoms * sizeof(WdAtomCode), n_pairs * sizeof(WdBondPair),
+                             n_blocks * 32, n_blocks * 8, n_atoms * da * 4, n_pairs * db * 4};
     size_t o = 0;
-    for (int k = 0; k < 6; ++k) { s.off[k] = o; o = a256(o + bytes[k]); }
+    for (int k = 0; k < 8; ++k) { s.off[k] = o; o = a256(o + bytes[k]); }
     s.total = std::max<size_t>(o, 256);
     return s;
 }
 
 inline Staged stage_layout(const Batch &c, const Plan &p) {
-    return stage_layout(c.xn.size(), c.atoms.size(), c.pairs.size(), (size_t)p.n_blocks());
+    return stage_layout(c.xn.size(), c.atoms.size(), c.pairs.size(), (size_t)p.n_blocks(), (size_t)c.da, (size_t)c.db);
 }
 
 inline void stage_copy(const Batch &c, const Plan &p, const Staged &s, uint8_t *dst) {
@@ -475,6 +510,8 @@ inline void stage_copy(const Batch &c, const Plan &p, const Staged &s, uint8_t *
     std::memcpy(dst + s.off[3], c.pairs.data(), c.pairs.size() * sizeof(WdBondPair));
     std::memcpy(dst + s.off[4], p.blocks.data(), p.blocks.size() * 4);
     std::memcpy(dst + s.off[5], p.block_nnz.data(), p.block_nnz.size() * 4);
+    if (!c.ax.empty()) std::memcpy(dst + s.off[6], c.ax.data(), c.ax.size() * 4);
+    if (!c.bx.empty()) std::memcpy(dst + s.off[7], c.bx.data(), c.bx.size() * 4);
 }
 
 }  // namespace compact

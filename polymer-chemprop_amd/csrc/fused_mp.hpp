@@ -715,6 +715,23 @@ struct EmbedP {
                                  // layer's A operand, copied by LDS-DMA: mp_layer_kernel<..., PAIRS>)
 };
 
+// Graphs with extra features (the template's XTRA; WdGraph.atom_extra / bond_extra): the rows carry a small dense
+// tail behind the codes, f_atoms = [base | xa], f_bonds = [f_atoms[src] | bits | xb], and the sums gain its terms
+// in ascending column order, the order of the dense dot product's non-zero terms:
+//     Eo[a]  = code sum (W_o) + sum_j xa[a][j] W_o[:, Fa0 + j]                     (Fa0 = Fa - da: the base block)
+//     Ea[a]  = code sum (W_i) + sum_j xa[a][j] W_i[:, Fa0 + j]
+//     inp[b] = Ea[src(b)] + sum_{k in tail(b)} W_i[:, Fa + k] + sum_j xb[pair(b)][j] W_i[:, Fb - db + j] (+ b_i)
+// The weight rows are in the tiles the kernel stages anyway (W_i^T / W_o^T are packed in natural column order);
+// the block's xa rows (<= 64 x da) and xb rows (<= 64 pairs x db) are loaded with the other up-front loads into
+// LDS (da + db <= EMBED_MAXX, 3.3 KB).  A term whose x is 0.0 leaves its sum bitwise unchanged (fma(0, w, s) = s
+// for finite w, and no partial sum is -0), so all-zero extras give the base graph's inp and Eo exactly.
+struct EmbedXP : EmbedP {
+    const float *xa;             // atom_extra: natural atom rows [n_atoms][da] (da = 0: any readable address)
+    const float *xb;             // bond_extra: [pairs][db], directed bond b reads row (b - 1) >> 1 (db = 0: as xa)
+    int da, db;
+};
+constexpr int EMBED_MAXX = 13;   // da + db the embed serves: Fb <= 160 with the default 133 + 14 columns
+
 // s = sum_{c in code} T[c][c4 .. c4+3] + last * T[Fa - 1][c4 ..] (ascending columns, then the mass column:
 // the order of the f_atoms row's dot product terms that are not zero)
 // Straight-line: the eight slot rows and the mass row are read together and waited for once (a branch per
@@ -738,8 +755,8 @@ __device__ __forceinline__ float4 code_sum(const WdAtomCode &cd, const float *T,
     return s;
 }
 
-template <int BN, int ACT, int NJ = WD_MULTI, bool PAIRS = false>
-__global__ __launch_bounds__(512) void embed_kernel(const Multi<EmbedP, NJ> MP) {
+template <int BN, int ACT, int NJ = WD_MULTI, bool PAIRS = false, bool XTRA = false>
+__global__ __launch_bounds__(512) void embed_kernel(const Multi<std::conditional_t<XTRA, EmbedXP, EmbedP>, NJ> MP) {
     static_assert(!PAIRS || BN % 16 == 0, "pair groups of whole 16-column halves");
     constexpr int NT = 512, LDC = BN + 4, C4 = BN / 4, U8 = BN / 8, MAXK = 160, PER = (MAXK * C4 + NT - 1) / NT;
     constexpr int BU = (BLK_BONDS * U8 + NT - 1) / NT;  // bond units (8 columns of a row) per thread
@@ -747,11 +764,15 @@ __global__ __launch_bounds__(512) void embed_kernel(const Multi<EmbedP, NJ> MP) 
     __shared__ __attribute__((aligned(16))) float ea[BLK_ATOMS * LDC];  // Ea of the block's atoms
     __shared__ __attribute__((aligned(16))) float bb[BN];
     __shared__ WdAtomCode code[BLK_ATOMS];
-    static_assert(sizeof(float) * (MAXK * BN + BLK_ATOMS * LDC + BN) + sizeof(WdAtomCode) * BLK_ATOMS <= 80 * 1024,
+    // XTRA: the block's extra-feature rows, xa [64][da] then xb [64 pairs][db]
+    constexpr int XS = XTRA ? BLK_ATOMS * EMBED_MAXX : 1, XQ = (XS + NT - 1) / NT;
+    __shared__ float xs[XS];
+    static_assert(sizeof(float) * (MAXK * BN + BLK_ATOMS * LDC + BN + (XTRA ? XS : 0)) + sizeof(WdAtomCode) * BLK_ATOMS <= 80 * 1024,
                   "LDS of two co-resident workgroups");
+    static_assert(BLK_BONDS / 2 == BLK_ATOMS, "xb rows: one per pair of the block's bond rows");
     int tile;
     wd_estamp(0);
-    const EmbedP &P = multi_pick(MP, xcd_tile(blockIdx.x, gridDim.x), tile);
+    const auto &P = multi_pick(MP, xcd_tile(blockIdx.x, gridDim.x), tile);
     // The entry head by value, pinned in scalar registers: one batch of scalar loads and one wait, and every
     // address below is made of registers (through the reference the compiler re-read Hk and the table pointers
     // from the argument segment inside each load's branch: a scalar round trip in front of every vector load).
@@ -762,6 +783,13 @@ __global__ __launch_bounds__(512) void embed_kernel(const Multi<EmbedP, NJ> MP) 
     const int32_t *h_blocks = pin_s(P.blocks);
     const int h_Fa = pin_s(P.Fa), h_Fb = pin_s(P.Fb), h_Hk = pin_s(P.Hk), h_nt = pin_s(P.n_tiles);
     const uint32_t h_tm = pin_s(P.tmagic);
+    const float *h_xa = nullptr, *h_xb = nullptr;
+    int h_da = 0, h_db = 0;
+    if constexpr (XTRA) {
+        h_xa = pin_s(P.xa); h_xb = pin_s(P.xb);
+        h_da = pin_s(P.da); h_db = pin_s(P.db);
+    }
+    const int fa0 = h_Fa - h_da;  // the base block of an atom row (its last column: the mass)
     int blk, nt;
     tile_split(tile, h_nt, h_tm, blk, nt);
     const int n0 = nt * BN;
@@ -801,6 +829,27 @@ __global__ __launch_bounds__(512) void embed_kernel(const Multi<EmbedP, NJ> MP) 
             tl[u] = h_tail[B.bs + lb];
         }
     }
+    if constexpr (XTRA) {
+        // the block's xa and xb values, both contiguous in memory: element v of xa [an][da] for v < 64 da, then
+        // element v - 64 da of xb [bn / 2][db] (the block's first bond id is odd: pair (bs - 1) / 2 is its first).
+        // Unconditional, as the loads above: a thread past either range reads element 0 of the array (the pad
+        // atom's row, the first pair's row; the host points an absent side at readable memory) and stores 0.
+        float xv[XQ];
+        const int na = B.an * h_da, nb = (B.bn >> 1) * h_db, xa0 = BLK_ATOMS * h_da;
+#pragma unroll
+        for (int q = 0; q < XQ; ++q) {
+            const int v = tid + NT * q, w = v - xa0;
+            const size_t ia = v < na ? (size_t)B.as * h_da + v : 0;
+            const size_t ib = w >= 0 && w < nb ? (size_t)((B.bs - 1) >> 1) * h_db + w : 0;
+            const float *src = v < xa0 ? h_xa + ia : h_xb + ib;
+            xv[q] = *src;
+        }
+#pragma unroll
+        for (int q = 0; q < XQ; ++q) {
+            const int v = tid + NT * q, w = v - xa0;
+            if (v < XS) xs[v] = (v < xa0 ? v < na : w < nb) ? xv[q] : 0.f;
+        }
+    }
     if (tid < B.an) reinterpret_cast<u32x4 *>(code)[tid] = cd;
     if (tid >= NT - C4) st4(bb + 4 * (tid - (NT - C4)), bq);
     // The f_atoms half of W_o first.  (Last, while the M_0 stores drain, measured, same box: embed 10.00 vs 10.25
@@ -817,7 +866,10 @@ __global__ __launch_bounds__(512) void embed_kernel(const Multi<EmbedP, NJ> MP) 
         // Eo[a] = sum_{c in code(a)} W_o[:, c] + last(a) W_o[:, Fa-1] (the f_atoms half of W_o)
         for (int v = tid; v < B.an * C4; v += NT) {
             const int la = v / C4, c = 4 * (v % C4);
-            st4(P.eo + (size_t)(B.as + la) * h_Hk + n0 + c, code_sum<BN>(code[la], wt, h_Fa, c));
+            float4 s = code_sum<BN>(code[la], wt, fa0, c);
+            if constexpr (XTRA)
+                for (int j = 0; j < h_da; ++j) fma4(s, xs[la * h_da + j], ld4(wt + (fa0 + j) * BN + c));
+            st4(P.eo + (size_t)(B.as + la) * h_Hk + n0 + c, s);
         }
     };
     eo_half();
@@ -833,7 +885,10 @@ __global__ __launch_bounds__(512) void embed_kernel(const Multi<EmbedP, NJ> MP) 
     // Ea[a] = sum_{c in code(a)} W_i[:, c] + last(a) W_i[:, Fa-1]
     for (int v = tid; v < B.an * C4; v += NT) {
         const int la = v / C4, c = 4 * (v % C4);
-        st4(ea + la * LDC + c, code_sum<BN>(code[la], wt, h_Fa, c));
+        float4 s = code_sum<BN>(code[la], wt, fa0, c);
+        if constexpr (XTRA)
+            for (int j = 0; j < h_da; ++j) fma4(s, xs[la * h_da + j], ld4(wt + (fa0 + j) * BN + c));
+        st4(ea + la * LDC + c, s);
     }
     __syncthreads();
     wd_estamp(4);
@@ -853,6 +908,14 @@ __global__ __launch_bounds__(512) void embed_kernel(const Multi<EmbedP, NJ> MP) 
             const float4 w0 = ld4(w), w1 = ld4(w + 4);
             z0.x += w0.x; z0.y += w0.y; z0.z += w0.z; z0.w += w0.w;
             z1.x += w1.x; z1.y += w1.y; z1.z += w1.z; z1.w += w1.w;
+        }
+        if constexpr (XTRA) {  // the bond's dense tail: columns Fb - db .. Fb - 1, the pair's xb row
+            const float *x = xs + BLK_ATOMS * h_da + (lb >> 1) * h_db;
+            for (int j = 0; j < h_db; ++j) {
+                const float *w = wt + (h_Fb - h_db + j) * BN + c;
+                fma4(z0, x[j], ld4(w));
+                fma4(z1, x[j], ld4(w + 4));
+            }
         }
         const float4 b0 = ld4(bb + c), b1 = ld4(bb + c + 4);
         z0.x += b0.x; z0.y += b0.y; z0.z += b0.z; z0.w += b0.w;

@@ -6,7 +6,9 @@
 // It reproduces, value for value and entry for entry, what the host path builds:
 //   * feature rows: f_atoms[a] = one-hot columns from the atom code + the last column's value
 //     (featurization.py:190-211), f_bonds[b] = f_atoms[src(b)] ‖ bond columns (featurization.py:467-468,
-//     545-546, 616-617), fp32 with 16-byte aligned rows, and their bf16x3 plane tiles (planes.hpp):
+//     545-546, 616-617), fp32 with 16-byte aligned rows, and their bf16x3 plane tiles (planes.hpp);
+//     with extra features (WdCompact.atom_extra / bond_extra, featurization.py:436-440, 460-468) the rows are
+//     f_atoms[a] = base ‖ atom_extra[a] and f_bonds[b] = f_atoms[src(b)] ‖ bond bits ‖ bond_extra[pair(b)]:
 //     natural rows (BR 64) and, for atoms, the molecule-blocked layout of the fused W_o;
 //   * in(a) = the bonds into a in creation order (= a2b[a], featurization.py:471-476, 624-627);
 //   * msg_gather row b (mpn.py:112-120): j in in(src(b)), coefficient w_j - [j == rev(b)] (w - 1 is a
@@ -48,7 +50,7 @@ struct GraphBuildP {
     int planes;  // 0: no plane tiles of the feature rows (WDMPNN_GRAPH_NO_PLANES)
 };
 
-// value of f_atoms column c for an atom code (c < Fa)
+// value of f_atoms column c for an atom code (c < Fa: the base block's width, the mass in its last column)
 __device__ __forceinline__ float code_value(const WdAtomCode &a, int c, int Fa) {
     if (c == Fa - 1) return a.last;
     bool hit = false;
@@ -222,6 +224,8 @@ __global__ __launch_bounds__(256) void graph_build_kernel(const Multi<GraphBuild
     const int tid = threadIdx.x, sl = blockIdx.y, nsl = gridDim.y;
     const WdCompact &C = P.c;
     const int Fa = P.Fa, Fb = P.Fb, UA = P.lda / 8, UB = P.ldb / 8;
+    // extra features: columns [Fa0, Fa) of an atom row, [Fx, Fb) of a bond row (none: Fa0 = Fa, Fx = Fb)
+    const int da = C.atom_extra_dim, db = C.bond_extra_dim, Fa0 = Fa - da, Fx = Fb - db;
     if (k == C.n_blocks && sl != 0) return;
     if (k == C.n_blocks) {  // pad rows: atom / bond row 0, the rows up to the padded extents, CSR heads and tails
         const int V1 = C.n_atoms, E1 = C.n_bonds;
@@ -331,7 +335,10 @@ __global__ __launch_bounds__(256) void graph_build_kernel(const Multi<GraphBuild
         if (la < an) {
             const WdAtomCode &cd = s_code[la];
 #pragma unroll
-            for (int q = 0; q < 8; ++q) v[q] = c0 + q < Fa ? code_value(cd, c0 + q, Fa) : 0.f;
+            for (int q = 0; q < 8; ++q) {
+                const int c = c0 + q;
+                v[q] = c < Fa0 ? code_value(cd, c, Fa0) : (c < Fa ? C.atom_extra[(size_t)(as + la) * da + (c - Fa0)] : 0.f);
+            }
             put_row8(P.f_atoms + (size_t)(as + la) * P.lda, P.fa_x6, P.lda, as + la, c0, v);
         } else {
 #pragma unroll
@@ -349,7 +356,11 @@ __global__ __launch_bounds__(256) void graph_build_kernel(const Multi<GraphBuild
 #pragma unroll
         for (int q = 0; q < 8; ++q) {
             const int c = c0 + q;
-            v[q] = c < Fa ? code_value(cd, c, Fa) : (c < Fb ? (float)((tail >> (c - Fa)) & 1) : 0.f);
+            if (c < Fa0) v[q] = code_value(cd, c, Fa0);
+            else if (c < Fa) v[q] = C.atom_extra[(size_t)(as + s_src[lb]) * da + (c - Fa0)];
+            else if (c < Fx) v[q] = (float)((tail >> (c - Fa)) & 1);
+            else if (c < Fb) v[q] = C.bond_extra[(size_t)((bs + lb - 1) >> 1) * db + (c - Fx)];
+            else v[q] = 0.f;
         }
         put_row8(P.f_bonds + (size_t)(bs + lb) * P.ldb, P.fb_x6, P.ldb, bs + lb, c0, v);
     }

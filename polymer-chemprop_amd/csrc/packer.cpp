@@ -515,13 +515,15 @@ PyObject *bytes_of(const void *d, size_t n) {
     return b;
 }
 
+// (mols, xn, atoms, pairs), and with extra features (atom_extra, bond_extra) after them
 PyObject *batch_tuple(const compact::Batch &c) {
-    PyObject *t = PyTuple_New(4);
+    const int nt = c.da || c.db ? 6 : 4;
+    PyObject *t = PyTuple_New(nt);
     if (!t) throw PyErrAlready{};
-    const void *d[4] = {c.mols.data(), c.xn.data(), c.atoms.data(), c.pairs.data()};
-    const size_t n[4] = {c.mols.size() * 4, c.xn.size() * 4, c.atoms.size() * sizeof(WdAtomCode),
-                         c.pairs.size() * sizeof(WdBondPair)};
-    for (int k = 0; k < 4; ++k) {
+    const void *d[6] = {c.mols.data(), c.xn.data(), c.atoms.data(), c.pairs.data(), c.ax.data(), c.bx.data()};
+    const size_t n[6] = {c.mols.size() * 4, c.xn.size() * 4, c.atoms.size() * sizeof(WdAtomCode),
+                         c.pairs.size() * sizeof(WdBondPair), c.ax.size() * 4, c.bx.size() * 4};
+    for (int k = 0; k < nt; ++k) {
         PyObject *b;
         try { b = bytes_of(d[k], n[k]); } catch (...) { Py_DECREF(t); throw; }
         PyTuple_SET_ITEM(t, k, b);
@@ -531,7 +533,7 @@ PyObject *batch_tuple(const compact::Batch &c) {
 
 // (mols, xn, atoms, pairs) buffers -> Batch
 void batch_from(PyObject *o_mols, PyObject *o_xn, PyObject *o_atoms, PyObject *o_pairs, int fa, int fb,
-                compact::Batch &c) {
+                compact::Batch &c, PyObject *o_ax = nullptr, PyObject *o_bx = nullptr, int da = 0, int db = 0) {
     Buf m(o_mols), x(o_xn), a(o_atoms), q(o_pairs);
     if (!m.ok || !x.ok || !a.ok || !q.ok) fail(PyExc_TypeError, "compact arrays must support the buffer protocol");
     if (m.b.len % 16 || x.b.len % 4 || a.b.len % (Py_ssize_t)sizeof(WdAtomCode) ||
@@ -561,16 +563,37 @@ void batch_from(PyObject *o_mols, PyObject *o_xn, PyObject *o_atoms, PyObject *o
         bo += r[3];
     }
     if (ao != c.n_atoms() || bo != c.n_bonds()) fail(PyExc_ValueError, "compact molecules do not cover the tables");
+    // extra features: the dense sections beside the codes (sizes checked against the tables)
+    if (da < 0 || db < 0 || da > compact::MAX_EXTRA || db > compact::MAX_EXTRA || fa - da < 2 || fb - fa - db < 0 ||
+        fb - fa - db > 16)
+        fail(PyExc_ValueError, "compact extra feature widths out of range");
+    c.da = da; c.db = db;
+    if (da) {
+        if (!o_ax || o_ax == Py_None) fail(PyExc_ValueError, "compact atom_extra must hold n_atoms x atom_extra_dim floats");
+        Buf e(o_ax);
+        if (!e.ok || (size_t)e.b.len != c.atoms.size() * (size_t)da * 4) fail(PyExc_ValueError, "compact atom_extra must hold n_atoms x atom_extra_dim floats");
+        c.ax.resize(c.atoms.size() * (size_t)da);
+        if (e.b.len) std::memcpy(c.ax.data(), e.b.buf, (size_t)e.b.len);
+    }
+    if (db) {
+        if (!o_bx || o_bx == Py_None) fail(PyExc_ValueError, "compact bond_extra must hold pairs x bond_extra_dim floats");
+        Buf e(o_bx);
+        if (!e.ok || (size_t)e.b.len != c.pairs.size() * (size_t)db * 4) fail(PyExc_ValueError, "compact bond_extra must hold pairs x bond_extra_dim floats");
+        c.bx.resize(c.pairs.size() * (size_t)db);
+        if (e.b.len) std::memcpy(c.bx.data(), e.b.buf, (size_t)e.b.len);
+    }
 }
 
-// compact_encode(f_atoms, tail, w_atoms, w_bonds, b2a, b2revb, deg, in_idx, na, nb, xn(float64), fa, tail_w)
-// -> (mols, xn, atoms, pairs) or (None, reason); tail = the bond columns [E+1][tail_w] or whole f_bonds rows
+// compact_encode(f_atoms, tail, w_atoms, w_bonds, b2a, b2revb, deg, in_idx, na, nb, xn(float64), fa, tail_w
+//                [, da, db])
+// -> (mols, xn, atoms, pairs[, atom_extra, bond_extra]) or (None, reason); da / db: the last da of the fa atom
+// columns and the last db of the tail_w bond columns are extra (dense) features; tail = the bond columns [E+1][tail_w] or whole f_bonds rows
 // [E+1][fa + tail_w] (then checked to start with their source atom's row)
 PyObject *compact_encode(PyObject *, PyObject *args) {
     PyObject *o[11];
-    int fa, tw;
-    if (!PyArg_ParseTuple(args, "OOOOOOOOOOOii", &o[0], &o[1], &o[2], &o[3], &o[4], &o[5], &o[6], &o[7], &o[8], &o[9],
-                          &o[10], &fa, &tw))
+    int fa, tw, da = 0, db = 0;
+    if (!PyArg_ParseTuple(args, "OOOOOOOOOOOii|ii", &o[0], &o[1], &o[2], &o[3], &o[4], &o[5], &o[6], &o[7], &o[8], &o[9],
+                          &o[10], &fa, &tw, &da, &db))
         return nullptr;
     try {
         In<float> f_atoms(o[0], "f", "f_atoms"), tail(o[1], "f", "tail"), w_atoms(o[2], "f", "w_atoms"),
@@ -589,7 +612,7 @@ PyObject *compact_encode(PyObject *, PyObject *args) {
             fail(PyExc_ValueError, "compact_encode: array sizes do not match the molecule counts");
         compact::Batch c;
         std::string why;
-        if (!compact::encode(fa, tw, (int)row_w, f_atoms.p, tail.p, w_atoms.p, w_bonds.p, b2a.p, rev.p, deg.p, in.p, na.p, nb.p,
+        if (!compact::encode(fa, tw, (int)row_w, da, db, f_atoms.p, tail.p, w_atoms.p, w_bonds.p, b2a.p, rev.p, deg.p, in.p, na.p, nb.p,
                              static_cast<const double *>(xb.b.buf), B, c, why)) {
             PyObject *s = PyUnicode_FromString(why.c_str());
             if (!s) throw PyErrAlready{};
@@ -606,14 +629,15 @@ PyObject *compact_encode(PyObject *, PyObject *args) {
     return nullptr;
 }
 
-// compact_decode(mols, xn, atoms, pairs, fa, fb) -> pack()'s 10 outputs in tail mode
+// compact_decode(mols, xn, atoms, pairs, fa, fb[, atom_extra, bond_extra, da, db]) -> pack()'s 10 outputs in
+// tail mode (fa / fb include the extra columns)
 PyObject *compact_decode(PyObject *, PyObject *args) {
-    PyObject *o[4];
-    int fa, fb;
-    if (!PyArg_ParseTuple(args, "OOOOii", &o[0], &o[1], &o[2], &o[3], &fa, &fb)) return nullptr;
+    PyObject *o[4], *ox[2] = {nullptr, nullptr};
+    int fa, fb, da = 0, db = 0;
+    if (!PyArg_ParseTuple(args, "OOOOii|OOii", &o[0], &o[1], &o[2], &o[3], &fa, &fb, &ox[0], &ox[1], &da, &db)) return nullptr;
     try {
         compact::Batch c;
-        batch_from(o[0], o[1], o[2], o[3], fa, fb, c);
+        batch_from(o[0], o[1], o[2], o[3], fa, fb, c, ox[0], ox[1], da, db);
         compact::Dense d;
         compact::decode(c, d);
         PyObject *t = PyTuple_New(10);
@@ -661,24 +685,33 @@ PyObject *compact_generate(PyObject *, PyObject *args) {
 }
 
 PyObject *stage_result(const compact::Batch &c, const compact::Plan &p, const compact::Staged &s, bool copied) {
+    if (c.da || c.db)  // ... and the offsets of the two extra-feature sections as a fifth element
+        return Py_BuildValue("(O(iiiiLL)(nnnnnn)n(nn))", copied ? Py_True : Py_False, c.n_mols(), c.n_atoms(), c.n_bonds(),
+                             p.n_blocks(), (long long)p.nnz_msg, (long long)p.nnz_agg, (Py_ssize_t)s.off[0],
+                             (Py_ssize_t)s.off[1], (Py_ssize_t)s.off[2], (Py_ssize_t)s.off[3], (Py_ssize_t)s.off[4],
+                             (Py_ssize_t)s.off[5], (Py_ssize_t)s.total, (Py_ssize_t)s.off[6], (Py_ssize_t)s.off[7]);
     return Py_BuildValue("(O(iiiiLL)(nnnnnn)n)", copied ? Py_True : Py_False, c.n_mols(), c.n_atoms(), c.n_bonds(),
                          p.n_blocks(), (long long)p.nnz_msg, (long long)p.nnz_agg, (Py_ssize_t)s.off[0],
                          (Py_ssize_t)s.off[1], (Py_ssize_t)s.off[2], (Py_ssize_t)s.off[3], (Py_ssize_t)s.off[4],
                          (Py_ssize_t)s.off[5], (Py_ssize_t)s.total);
 }
 
-// compact_stage(mols, xn, atoms, pairs, fa, fb, target_blocks, dst_address, capacity)
+// compact_stage(mols, xn, atoms, pairs, fa, fb, target_blocks, dst_address, capacity[, atom_extra, bond_extra,
+//               da, db])
 // -> None (a molecule exceeds a block) | (copied, (n_mols, n_atoms, n_bonds, n_blocks, nnz_msg, nnz_agg),
-//    offsets[6], total): the plan and the upload image written to dst (host memory, e.g. pinned) when it fits
+//    offsets[6], total[, (atom_extra offset, bond_extra offset)]): the plan and the upload image written to dst
+//    (host memory, e.g. pinned) when it fits; the fifth element only with extra features
 PyObject *compact_stage(PyObject *, PyObject *args) {
-    PyObject *o[4];
-    int fa, fb, target;
+    PyObject *o[4], *ox[2] = {nullptr, nullptr};
+    int fa, fb, target, da = 0, db = 0;
     unsigned long long dst;
     Py_ssize_t cap;
-    if (!PyArg_ParseTuple(args, "OOOOiiiKn", &o[0], &o[1], &o[2], &o[3], &fa, &fb, &target, &dst, &cap)) return nullptr;
+    if (!PyArg_ParseTuple(args, "OOOOiiiKn|OOii", &o[0], &o[1], &o[2], &o[3], &fa, &fb, &target, &dst, &cap, &ox[0],
+                          &ox[1], &da, &db))
+        return nullptr;
     try {
         compact::Batch c;
-        batch_from(o[0], o[1], o[2], o[3], fa, fb, c);
+        batch_from(o[0], o[1], o[2], o[3], fa, fb, c, ox[0], ox[1], da, db);
         compact::Plan p;
         if (!compact::plan(c, target, p)) Py_RETURN_NONE;
         const compact::Staged s = compact::stage_layout(c, p);

@@ -143,6 +143,7 @@ constexpr int EMBED40_BN = 40;
 struct Dims {
     int H, Hk, T, R, Rp, Va, Vap, B, Fa, Fak, Fb, Fbk, d, dk, Hd, Hdk, Kin, Kink;
     int ldx, Ko, Kd;
+    int da, db;  // extra atom / bond feature columns of a compact graph (the dense tails of Fa and Fb; 0: none)
     bool atom, undirected, save, desc;
     Variant V;
     bool x6;   // plane-tile pipeline: gathers emit bf16x3 plane tiles, GEMMs run gemm_x6g_kernel
@@ -194,7 +195,14 @@ int get_dims(const WdGraph *g, const WdParams *p, const WdConfig *c, Dims &D) {
     // molecule-blocked fused forward, also for training (the fused kernels then save Z_t, A and Zo in
     // natural rows for the backward)
     // (an embed-capable graph -- categorical codes -- needs no feature planes)
-    D.codes = g->atom_codes && g->bond_src_blk && g->bond_tail && D.Fb <= WO_MAXK && D.Fa <= WO_MAXK;
+    // (extra features: the embed adds them as a dense tail when they fit its LDS tile; wider graphs run the plane
+    // GEMM input layer on the device-built rows)
+    D.da = g->atom_codes ? g->atom_extra_dim : 0; D.db = g->atom_codes ? g->bond_extra_dim : 0;
+    if (D.atom) D.da = D.db = 0;  // (atom messages never read the codes)
+    if (D.da < 0 || D.db < 0 || (D.da && D.da >= D.Fa) || (D.db && D.db > D.Fb - D.Fa))
+        return fail(WD_ERR_SHAPE, "extra feature widths %d / %d do not fit atom_fdim %d / bond_fdim %d", D.da, D.db, D.Fa, D.Fb);
+    D.codes = g->atom_codes && g->bond_src_blk && g->bond_tail && D.Fb <= WO_MAXK && D.Fa <= WO_MAXK &&
+              D.da + D.db <= EMBED_MAXX && (!D.da || g->atom_extra) && (!D.db || g->bond_extra || g->n_bonds <= 1);
     // (any Hk: a consumer folds its block's h2 scale words 64 at a time, planes.hpp lane_word)
     const bool blk_common = !D.desc && D.T >= 2 && g->n_blocks > 0 && g->blocks &&
                             g->atom_ell_idx && g->atom_ell_coef;
@@ -209,7 +217,7 @@ int get_dims(const WdGraph *g, const WdParams *p, const WdConfig *c, Dims &D) {
     D.nblk = D.blocked ? g->n_blocks : 0;
     // QM9-sized blocks, inference: the one-launch forward
     D.small = D.blocked && D.codes && !D.atom && !D.save && c->dropout == 0.f && D.Hk == SF_HK && !D.undirected &&
-              V.one_launch && g->blk_max_bonds > 0 && g->blk_max_bonds <= SF_ROWS && g->blk_max_atoms <= SF_ATOMS &&
+              !D.da && !D.db && V.one_launch && g->blk_max_bonds > 0 && g->blk_max_bonds <= SF_ROWS && g->blk_max_atoms <= SF_ATOMS &&
               D.Fa <= WO_MAXK && D.Fb <= WO_MAXK && D.Fb - D.Fa <= SF_ROWS;
     // inference through the embed (codes), bond messages, 80-column layer tiles, <= 64 embed words per block:
     // the layers read M_{t-1} as fp16 pair tiles written by its producer (fused_mp.hpp PAIRS; DESIGN.md §4 "Pair
@@ -809,7 +817,11 @@ int graph_layout(const WdCompact *c, GraphLayout &L) {
         c->nnz_msg < 0 || c->nnz_agg < 0)
         return fail(WD_ERR_SHAPE, "compact graph: bad counts (atoms %d bonds %d mols %d blocks %d)", c->n_atoms,
                     c->n_bonds, c->n_mols, c->n_blocks);
-    if (c->atom_fdim < 2 || c->atom_fdim > 255 || c->bond_fdim < c->atom_fdim || c->bond_fdim - c->atom_fdim > 16)
+    const int da = c->atom_extra_dim, db = c->bond_extra_dim;
+    if (da < 0 || da > 64 || db < 0 || db > 64)
+        return fail(WD_ERR_SHAPE, "compact graph: extra feature widths %d / %d out of range (0..64)", da, db);
+    if (c->atom_fdim - da < 2 || c->atom_fdim - da > 255 || c->bond_fdim - db < c->atom_fdim ||
+        c->bond_fdim - c->atom_fdim - db > 16)
         return fail(WD_ERR_SHAPE, "compact graph: atom_fdim %d / bond_fdim %d out of range", c->atom_fdim, c->bond_fdim);
     L.lda = rup(c->atom_fdim, 32); L.ldb = rup(c->bond_fdim, 32);
     L.Vap = rup(c->n_atoms, 128); L.Rbp = rup(c->n_bonds, 128);
@@ -910,8 +922,7 @@ int fused_input(const FusedCtx &X) {
     const PackLayout &PL = X.PL;
     const int Hk = X.Hk;
     if (D0.codes) {
-        Multi<EmbedP> M;
-        const int grid = launch_multi(X.jobs, X.n, D0.etiles, [&](EmbedP &E, const FusedJob &J) {
+        auto fill = [&](EmbedP &E, const FusedJob &J) {
             const WdGraph *g = J.g;
             E.codes = g->atom_codes; E.src_blk = g->bond_src_blk; E.tail = g->bond_tail;
             E.wt = X.W(PL.WiT); E.woat = X.W(PL.WoaT); E.eo = X.F(J, J.L.Eo); E.bias = X.p->b_i ? X.W(PL.bi) : nullptr;
@@ -920,18 +931,39 @@ int fused_input(const FusedCtx &X) {
             E.inp = X.F(J, J.L.Z[0]);
             E.slope = X.p->prelu; E.amax = X.slot(J, 0);
             E.m0 = D0.lay_pairs ? (uint8_t *)(J.ws + J.L.Mp[0]) : nullptr;
-        }, M);
-        if (!tile_magic_ok(grid, D0.etiles)) return fail(WD_ERR_SHAPE, "fused forward: %d embed tiles", grid);
-        host_with_act(X.c->activation, [&](auto act_c) {
-            constexpr int A = decltype(act_c)::value;
-            with_jobs(X.n, M, [&](const auto &Mn, auto nj) {
-                constexpr int NJ = decltype(nj)::value;
-                if (D0.lay_pairs) hipLaunchKernelGGL((embed_kernel<EPB, A, NJ, true>), dim3(grid), dim3(512), 0, X.st, Mn);
-                else if (D0.ebn == 40) hipLaunchKernelGGL((embed_kernel<40, A, NJ>), dim3(grid), dim3(512), 0, X.st, Mn);
-                else if (D0.ebn == 80) hipLaunchKernelGGL((embed_kernel<80, A, NJ>), dim3(grid), dim3(512), 0, X.st, Mn);
-                else hipLaunchKernelGGL((embed_kernel<64, A, NJ>), dim3(grid), dim3(512), 0, X.st, Mn);
+        };
+        // XT: the graphs carry extra features (EmbedXP, the kernel's dense tail)
+        auto launch = [&](const auto &M, int grid, auto xt) {
+            constexpr bool XT = decltype(xt)::value;
+            host_with_act(X.c->activation, [&](auto act_c) {
+                constexpr int A = decltype(act_c)::value;
+                with_jobs(X.n, M, [&](const auto &Mn, auto nj) {
+                    constexpr int NJ = decltype(nj)::value;
+                    if (D0.lay_pairs) hipLaunchKernelGGL((embed_kernel<EPB, A, NJ, true, XT>), dim3(grid), dim3(512), 0, X.st, Mn);
+                    else if (D0.ebn == 40) hipLaunchKernelGGL((embed_kernel<40, A, NJ, false, XT>), dim3(grid), dim3(512), 0, X.st, Mn);
+                    else if (D0.ebn == 80) hipLaunchKernelGGL((embed_kernel<80, A, NJ, false, XT>), dim3(grid), dim3(512), 0, X.st, Mn);
+                    else hipLaunchKernelGGL((embed_kernel<64, A, NJ, false, XT>), dim3(grid), dim3(512), 0, X.st, Mn);
+                });
             });
-        });
+        };
+        if (D0.da || D0.db) {
+            Multi<EmbedXP> M;
+            const int grid = launch_multi(X.jobs, X.n, D0.etiles, [&](EmbedXP &E, const FusedJob &J) {
+                fill(E, J);
+                // (a side without columns, or a batch without bonds, is never read for a value: it points at
+                // readable memory, because the kernel's up-front loads are unconditional)
+                E.da = J.D.da; E.db = J.D.db;
+                E.xa = J.D.da ? J.g->atom_extra : E.wt;
+                E.xb = J.D.db && J.g->n_bonds > 1 ? J.g->bond_extra : E.wt;
+            }, M);
+            if (!tile_magic_ok(grid, D0.etiles)) return fail(WD_ERR_SHAPE, "fused forward: %d embed tiles", grid);
+            launch(M, grid, std::true_type{});
+        } else {
+            Multi<EmbedP> M;
+            const int grid = launch_multi(X.jobs, X.n, D0.etiles, fill, M);
+            if (!tile_magic_ok(grid, D0.etiles)) return fail(WD_ERR_SHAPE, "fused forward: %d embed tiles", grid);
+            launch(M, grid, std::false_type{});
+        }
         WD_CHECK_LAUNCH("embed");
         return 0;
     }
@@ -1101,7 +1133,7 @@ int fused_forward(const FusedJob *jobs, int n, const WdParams *p, const WdConfig
     for (int j = 1; j < n; ++j) {
         const Dims &D = jobs[j].D;
         if (D.codes != D0.codes || D.Hk != D0.Hk || D.T != D0.T || D.atom != D0.atom || D.Fa != D0.Fa ||
-            D.Fb != D0.Fb || D.save != D0.save || D.pairs != D0.pairs)
+            D.Fb != D0.Fb || D.da != D0.da || D.db != D0.db || D.save != D0.save || D.pairs != D0.pairs)
             return fail(WD_ERR_UNSUPPORTED, "fused forward: batches of one launch differ in layout");
     }
     const FusedCtx X{jobs, n, p, c, PL, pk, st, D0, D0.Hk, D0.bn};
@@ -1173,6 +1205,17 @@ int wdmpnn_debug_fwd_offsets(const WdGraph *g, const WdParams *p, const WdConfig
     const size_t v[15] = {L.Z.empty() ? 0 : L.Z[0], L.Mp[0], L.Mp[1], L.Ab, L.amax[0], L.amax[1], L.Zb[0], L.Zb[1],
                           L.total, (size_t)D.pairs, PL.WoH, PL.wo_amax, PL.WhH, PL.amax, L.Eo};
     memcpy(out, v, sizeof(v));
+    return 0;
+}
+
+// debug (tests/test_extra_features_gpu.py; not in the header): which input layer wdmpnn_forward runs for these
+// arguments: 0 the unblocked GEMM path, 1 the blocked plane-tile GEMM, 2 the code embed, 3 the code embed with the
+// dense tail of extra features, 4 the one-launch forward (its own embed)
+int wdmpnn_debug_input_path(const WdGraph *g, const WdParams *p, const WdConfig *c, int32_t *out) {
+    Dims D;
+    WD_TRY(get_dims(g, p, c, D));
+    if (!out) return fail(WD_ERR_ARG, "null out");
+    *out = !D.blocked ? 0 : D.small ? 4 : !D.codes ? 1 : (D.da || D.db) ? 3 : 2;
     return 0;
 }
 
@@ -2246,6 +2289,8 @@ int graph_build_prepare(const WdCompact *c, void *buffer, size_t bytes, int32_t 
     if (c->n_mols && (!c->mols || !c->xn)) return fail(WD_ERR_ARG, "null molecule arrays");
     if (!c->atoms || (c->n_bonds > 1 && !c->pairs) || (c->n_blocks && (!c->blocks || !c->block_nnz)))
         return fail(WD_ERR_ARG, "null compact arrays");
+    if ((c->atom_extra_dim && !c->atom_extra) || (c->bond_extra_dim && c->n_bonds > 1 && !c->bond_extra))
+        return fail(WD_ERR_ARG, "null extra feature arrays");
     char *base = (char *)buffer;
     auto F = [&](size_t o) { return (float *)(base + o); };
     auto I = [&](size_t o) { return (int32_t *)(base + o); };
@@ -2286,6 +2331,9 @@ int graph_build_prepare(const WdCompact *c, void *buffer, size_t bytes, int32_t 
     G.msg_ell_idx = P.msg_ell_idx; G.msg_ell_coef = P.msg_ell_coef;
     G.atom_ell_idx = P.agg_ell_idx; G.atom_ell_coef = P.agg_ell_coef;
     G.atom_codes = c->atoms; G.bond_src_blk = P.bond_src_blk; G.bond_tail = P.bond_tail;
+    // (the embed reads the extras where they were uploaded, like the codes: a lean graph keeps them)
+    G.atom_extra = c->atom_extra_dim ? c->atom_extra : nullptr; G.atom_extra_dim = c->atom_extra_dim;
+    G.bond_extra = c->bond_extra_dim ? c->bond_extra : nullptr; G.bond_extra_dim = c->bond_extra_dim;
     if (lean) {  // what was not built is not handed out: a path that needs it fails in get_dims
         G.f_atoms = G.f_bonds = nullptr;
         G.f_atoms_x6 = G.f_bonds_x6 = G.f_atoms_blk_x6 = nullptr;

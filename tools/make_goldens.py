@@ -73,6 +73,9 @@ CASES = {
                                                               number_of_molecules=2, use_input_features=True,
                                                               features_size=5, dataset_type='classification',
                                                               num_tasks=2), 'model', True),
+    # extra atom / bond features in the reference's concatenating mode (set_extra_atom_fdim(3), set_extra_bond_fdim(2);
+    # widened synthetic graphs, synthetic.with_extra_features): written to tests/golden/extra_features/
+    'enc_extra_features': (('polymer', 4, 34), dict(hidden_size=32, bias=True, extra_features=(3, 2)), 'encoder', True),
 }
 
 
@@ -86,12 +89,12 @@ def make_graphs(kind, b, seed):
     return [synthetic.make_batch(kind, b, seed)]
 
 
-def pack_mols(prefix, graphs, out):
+def pack_mols(prefix, graphs, out, fa_w=133, fb_w=147):
     """Per-molecule MolGraph arrays (local indices), concatenated with counts."""
     out[f'{prefix}n_atoms'] = np.array([g.n_atoms for g in graphs], np.int64)
     out[f'{prefix}n_bonds'] = np.array([g.n_bonds for g in graphs], np.int64)
-    fa = [np.asarray(g.f_atoms, np.float32).reshape(g.n_atoms, 133) for g in graphs]
-    fb = [np.asarray(g.f_bonds, np.float32).reshape(g.n_bonds, 147) for g in graphs]
+    fa = [np.asarray(g.f_atoms, np.float32).reshape(g.n_atoms, fa_w) for g in graphs]
+    fb = [np.asarray(g.f_bonds, np.float32).reshape(g.n_bonds, fb_w) for g in graphs]
     out[f'{prefix}f_atoms'] = np.concatenate(fa)
     out[f'{prefix}f_bonds'] = np.concatenate(fb)
     out[f'{prefix}w_atoms'] = np.concatenate([np.asarray(g.w_atoms, np.float32) for g in graphs])
@@ -115,11 +118,17 @@ def main():
     for name, ((kind, b, seed), overrides, level, grads) in CASES.items():
         if only and name not in only:
             continue
+        overrides = dict(overrides)
+        da, db = overrides.pop('extra_features', (0, 0))
         args = types.SimpleNamespace(**{**BASE_ARGS, **overrides})
         if args.ffn_hidden_size is None:
             args.ffn_hidden_size = args.hidden_size
         torch.manual_seed(0)
         mol_lists = make_graphs(kind, b, seed)
+        if da or db:
+            mol_lists = [synthetic.with_extra_features(gs, da, db, seed) for gs in mol_lists]
+        ref.featurization.set_extra_atom_fdim(da)
+        ref.featurization.set_extra_bond_fdim(db)
         batches = [ref.featurization.BatchMolGraph(gs) for gs in mol_lists]
         out = {'config': np.array(json.dumps({k: v for k, v in vars(args).items() if k != 'device'})),
                'level': np.array(level), 'param_seed': np.array(seed), 'n_slots': np.array(len(batches))}
@@ -134,7 +143,7 @@ def main():
                         for _ in range(len(mol_lists[0]))]
             out['features'] = np.stack(features)
         for s, (gs, bmg) in enumerate(zip(mol_lists, batches)):
-            pack_mols(f's{s}_mol_', gs, out)
+            pack_mols(f's{s}_mol_', gs, out, 133 + da, 147 + da + db)
             out[f's{s}_a2b'] = bmg.a2b.numpy()
             out[f's{s}_b2a'] = bmg.b2a.numpy()
             out[f's{s}_b2revb'] = bmg.b2revb.numpy()
@@ -162,6 +171,10 @@ def main():
                     out[f'grad/{pname}'] = p.grad.numpy()
         out['param_names'] = np.array(json.dumps([n for n, _ in module.named_parameters()]))
         path = os.path.join(OUT, f'{name}.npz')
+        if da or db:  # (beside the top-level fixtures, which the parametrised parity tests enumerate at 133 / 147 columns)
+            out['extra_dims'] = np.array([da, db], np.int64)
+            os.makedirs(os.path.join(OUT, 'extra_features'), exist_ok=True)
+            path = os.path.join(OUT, 'extra_features', f'{name}.npz')
         np.savez_compressed(path, **out)
         print(f'{name}: out {tuple(y.shape)} |y|max={float(y.detach().abs().max()):.4g} '
               f'{os.path.getsize(path) / 1024:.0f} KiB')
