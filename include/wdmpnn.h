@@ -381,6 +381,34 @@ int wdmpnn_build_graph(const WdCompact *c, void *buffer, size_t bytes, WdGraph *
 #define WDMPNN_GRAPH_NO_PLANES 2
 int wdmpnn_build_graph_ex(const WdCompact *c, void *buffer, size_t bytes, WdGraph *g, int32_t flags, void *stream);
 
+/* Atom-message mode (WdGraph.atom_messages = 1; mpn.py:47-53, 93-94, 104-108, 126-128) from the same compact
+ * image and block plan: one launch, one workgroup per molecule block and slice + one for the pad rows.
+ * Message rows are atoms and every list's row a has deg(a) entries (msg_gather: deg(a) + 1), so every offset
+ * follows from the block table alone: c->nnz_msg, c->nnz_agg and c->block_nnz are not read (a resident table
+ * needs no per-batch entry counts).  max_num_bonds = the batch's largest atom degree (>= 1,
+ * BatchMolGraph.max_num_bonds).  With Fb' = c->bond_fdim - c->atom_fdim the graph holds
+ *   f_atoms (+ natural and molecule-blocked planes), w_atoms, the scope arrays, b2revb, blocks, bond_blk_row
+ *                      as wdmpnn_build_graph writes them (atom extras included);
+ *   f_bonds [.][rup(Fb', 32)]  the bond's own columns: the bit columns, then bond_extra[pair]; bond_fdim = Fb';
+ *   bond_feat_gather   row a = the bonds into a in creation order, coefficient 1;
+ *   atom_feat_sum_x6   planes of sum_{j in in(a)} f_bonds[j], fp32, added in list order;
+ *   msg_gather         row a = (b2a[j], 1) for j in in(a), then ONE pad entry (0, max_num_bonds - deg(a)),
+ *                      written even when the coefficient is 0; row 0 = (0, max_num_bonds);
+ *   atom_gather        row a = (b2a[j], w_bonds[b2a[j]]) for j in in(a): the reference's quirk (mpn.py:128), the
+ *                      weight looked up by the ATOM id used as a bond id; zero coefficients are kept, and an id
+ *                      past the bonds reads 0 (callers route such batches to the host packer);
+ *   msg_gather_t, atom_gather_t   the exact transposes over atom rows, entries by increasing forward row, then
+ *                      position; msg_gather_t row 0 = the n_atoms pad entries;
+ *   msg_ell_*, atom_ell_*   per atom: the first 8 real a2a entries (pad entry dropped) / the first 8 atom_gather
+ *                      entries, block-local atom indices, bit 7 of slot 7 set when deg(a) > 8.
+ * atom_codes, bond_src_blk, bond_tail, atom_extra and bond_extra stay NULL.  After dropping zero coefficients
+ * every list equals the host packer's entry for entry, so outputs and gradients are bitwise the host-built
+ * graph's.  Buffer contract as wdmpnn_build_graph (256-byte aligned, WD_ERR_WORKSPACE when short); no lean
+ * variant, no batching of several builds per launch. */
+int wdmpnn_graph_bytes_atom(const WdCompact *c, size_t *bytes);
+int wdmpnn_build_graph_atom(const WdCompact *c, void *buffer, size_t bytes, WdGraph *g, int32_t max_num_bonds,
+                            void *stream);
+
 /* Resident graph tables: the compact image of a batch assembled on the device from the codes of a whole data
  * split, uploaded once per run (chemprop_amd.graph_table).  A molecule's compact record is position-independent
  * (WdAtomCode holds nothing batch-relative, WdBondPair.a1 / a2 are molecule-local), so the xn, atoms and pairs

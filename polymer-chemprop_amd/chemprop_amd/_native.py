@@ -50,7 +50,7 @@ EXPORTED_SYMBOLS = ('wdmpnn_abi_version', 'wdmpnn_last_error', 'wdmpnn_workspace
                     'wdmpnn_ensemble_sid', 'wdmpnn_eval_add', 'wdmpnn_eval_spectra', 'wdmpnn_eval_auc',
                     'wdmpnn_head_stack_latent', 'wdmpnn_latent_add', 'wdmpnn_desc_join', 'wdmpnn_desc_layer',
                     'wdmpnn_desc_layer_backward', 'wdmpnn_desc_rows', 'wdmpnn_slots_join', 'wdmpnn_slots_split',
-                    'wdmpnn_gather_compact')
+                    'wdmpnn_gather_compact', 'wdmpnn_graph_bytes_atom', 'wdmpnn_build_graph_atom')
 HEAD_MAX_LAYERS = 6  # WD_HEAD_MAX_LAYERS
 HEAD_MAX_SPECTRUM = 8192  # WD_HEAD_MAX_SPECTRUM
 SPECTRA_ACTIVATIONS = {'exp': 0, 'softplus': 1}  # WdHeadSpectra.spectra_act
@@ -375,6 +375,8 @@ def lib() -> ctypes.CDLL:
     L.wdmpnn_build_bond_features.argtypes = [c_void_p, c_int32, c_int32, c_int32, c_void_p, c_void_p, c_int32, c_int32,
                                              c_int32, c_void_p, c_int32, c_void_p]
     L.wdmpnn_build_graph_ex.argtypes = [POINTER(WdCompact), c_void_p, c_size_t, POINTER(WdGraph), c_int32, c_void_p]
+    L.wdmpnn_graph_bytes_atom.argtypes = [POINTER(WdCompact), POINTER(c_size_t)]
+    L.wdmpnn_build_graph_atom.argtypes = [POINTER(WdCompact), c_void_p, c_size_t, POINTER(WdGraph), c_int32, c_void_p]
     L.wdmpnn_head_mse.argtypes = [POINTER(WdHead), c_void_p]
     L.wdmpnn_head_predict.argtypes = [POINTER(WdHeadPredict), c_void_p]
     L.wdmpnn_head_stack_scratch_bytes.argtypes = [c_int32, c_int32, c_int32, c_int32, c_int32, POINTER(c_size_t)]
@@ -430,7 +432,8 @@ def lib() -> ctypes.CDLL:
              'wdmpnn_head_spectra_predict', 'wdmpnn_join_rows', 'wdmpnn_ensemble_add', 'wdmpnn_ensemble_sid',
              'wdmpnn_eval_add', 'wdmpnn_eval_spectra', 'wdmpnn_eval_auc', 'wdmpnn_head_stack_latent',
              'wdmpnn_latent_add', 'wdmpnn_desc_join', 'wdmpnn_desc_layer', 'wdmpnn_desc_layer_backward',
-             'wdmpnn_desc_rows', 'wdmpnn_slots_join', 'wdmpnn_slots_split', 'wdmpnn_gather_compact'):
+             'wdmpnn_desc_rows', 'wdmpnn_slots_join', 'wdmpnn_slots_split', 'wdmpnn_gather_compact',
+             'wdmpnn_graph_bytes_atom', 'wdmpnn_build_graph_atom'):
         getattr(L, fn).restype = c_int
     v = L.wdmpnn_abi_version()
     if v != ABI_VERSION:

@@ -55,6 +55,10 @@ restated here:
   slice of it (one gather launch assembles the batch's compact image, the usual build launch expands it), and
   every split's scoring batches are built once per run; a split the table refuses (extra features, a molecule
   larger than a block) is reported in one line and trains on the list path; every output is bitwise unchanged;
+* ``--atom_messages`` (args.py:323): messages between atoms; the batches' graphs come from the same compact codes
+  (``wdmpnn_build_graph_atom``), with ``--resident_graphs`` too, and the step skips autograd as for bond messages;
+  the flag is stored in the checkpoint, where ``chemprop_predict`` and ``chemprop_fingerprint`` find it; with
+  ``--undirected`` it is an argument error;
 * every prediction above walks its split with ``predict.device_predictions``: ``predict`` copies the batches to the
   host, the ensemble's accumulator and ``evaluate``'s evaluator take them where the head wrote them.
 
@@ -718,6 +722,9 @@ def parse_args(argv=None, spectra: bool = False) -> argparse.Namespace:
     ap.add_argument('--aggregation_norm', type=int, default=100)
     ap.add_argument('--bias', action='store_true')
     ap.add_argument('--undirected', action='store_true')
+    ap.add_argument('--atom_messages', action='store_true',
+                    help='pass messages between atoms instead of directed bonds (args.py:323); stored in the '
+                         'checkpoint, which chemprop_predict and chemprop_fingerprint read it from')
     ap.add_argument('--gpu', type=int, default=0)
     ap.add_argument('--weight_decay', type=float, default=0.0)
     ap.add_argument('--optimizer', default='adam', choices=['adam', 'adamw'])
@@ -741,6 +748,8 @@ def parse_args(argv=None, spectra: bool = False) -> argparse.Namespace:
                          'a step gathers its batch there instead of packing it on the host, and every split\'s '
                          'scoring batches are built once per run; results are bitwise unchanged')
     a = ap.parse_args(argv)
+    if a.atom_messages and a.undirected:  # (the reference indexes atom messages with b2revb there, mpn.py:101-102)
+        ap.error('--atom_messages cannot be combined with --undirected')
     if not 1 <= a.ensemble_size <= ENSEMBLE_MAX_MODELS:
         raise ValueError(f'--ensemble_size must be in 1 .. {ENSEMBLE_MAX_MODELS}')
     if a.alternative_loss_function is not None and a.dataset_type != 'spectra':
@@ -840,7 +849,8 @@ def run_training(a: argparse.Namespace) -> Dict[str, list]:
         graphs = join_extra_features(graphs, atom_features, bond_features)
     args = TrainArgs(hidden_size=a.hidden_size, depth=a.depth, dropout=a.dropout, activation=a.activation,
                      aggregation=a.aggregation, aggregation_norm=a.aggregation_norm, bias=a.bias,
-                     undirected=a.undirected, ffn_num_layers=a.ffn_num_layers,
+                     undirected=a.undirected, atom_messages=bool(getattr(a, 'atom_messages', False)),
+                     ffn_num_layers=a.ffn_num_layers,
                      ffn_hidden_size=a.ffn_hidden_size or a.hidden_size, dataset_type=a.dataset_type,
                      num_tasks=num_tasks, multiclass_num_classes=a.multiclass_num_classes, device=device,
                      frzn_encoder=bool(a.frzn_encoder or a.frzn_ffn_layers > 0), frzn_ffn_layers=a.frzn_ffn_layers,

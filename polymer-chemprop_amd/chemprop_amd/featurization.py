@@ -189,7 +189,8 @@ class BatchMolGraph:
         Extra atom / bond features in the reference's concatenating mode (rows wider than the default
         133 / 14 columns, featurization.py:436-440, 460-468) ride along as two small dense arrays beside the
         codes (at most 64 columns each; both directed bonds of a pair must hold the same values).
-        Other batches (overwritten features, extras beyond the caps, atom messages, molecules larger than a
+        Atom-message graphs are built from the same codes (``wdmpnn_build_graph_atom``).
+        Other batches (overwritten features, extras beyond the caps, molecules larger than a
         block) take the host-built path: gather lists packed here, fp32 rows uploaded.
 
         ``block_target``: the molecule blocks a small batch is spread over at least (``molecule_blocks``).
@@ -489,7 +490,7 @@ class BatchMolGraph:
         return np.array(rows, np.int32).reshape(-1, 8)
 
     # ------------------------------------------------------------------ device packing
-    def _device_graph_compact(self, device):
+    def _device_graph_compact(self, device, atom_messages: bool = False):
         """The compact path of ``device_graph``: plan + image (native, one pinned buffer), one H2D,
         one build launch; None when a molecule exceeds a block."""
         extra = self.__dict__.get('_compact_extra') or ()
@@ -500,7 +501,8 @@ class BatchMolGraph:
         if info is None:
             return None
         assert info[0], 'staged image larger than its bound'
-        return upload_compact(device, host, info, *self._compact_dims, extra_dims=tuple(extra[2:]))
+        return upload_compact(device, host, info, *self._compact_dims, extra_dims=tuple(extra[2:]),
+                              max_num_bonds=self.max_num_bonds if atom_messages else None)
 
     def device_graph(self, device, atom_messages: bool = False, bond_fdim: int = None,
                      atom_blocks: bool = True) -> DeviceGraph:
@@ -508,7 +510,8 @@ class BatchMolGraph:
         ``atom_blocks`` (atom messages only): also build what the molecule-blocked fused atom-message
         forward reads (blocks, block-local ELL lists, per-atom bond-feature sums).  Only a bias-free
         inference forward can take that path (wdmpnn.hip get_dims), so the encoder asks for them only
-        then: a training or biased graph skips their host work and upload."""
+        then: a training or biased graph skips their host work and upload.  A compact batch on a GPU gets one
+        device-built graph for both (``atom_blocks`` is moot: nothing is packed on the host)."""
         device = torch.device(device)
         atom_blocks = bool(atom_blocks) or not atom_messages
         key = (str(device), bool(atom_messages), bond_fdim) if atom_blocks else \
@@ -517,17 +520,30 @@ class BatchMolGraph:
         if dg is not None:
             return dg
         src = self.__dict__.get('_source')
-        if src is not None and not atom_messages and (bond_fdim is None or bond_fdim == self._compact_dims[1]):
-            dg = src.device_graph(self, device)  # gathered on the device from the resident table, or None
+        # the width the device build gives f_bonds: the full rows, or in atom-message mode the bond's own columns.
+        # Atom messages: the readout indexes w_bonds with atom ids (mpn.py:128), so the device build serves only
+        # batches where no atom id can overrun it; the others get the host path's IndexError
+        dims = self._compact_dims if src is not None or self._compact is not None else None
+        on_device = dims is not None and (bond_fdim is None or bond_fdim == dims[1] - atom_messages * dims[0]) and \
+            (not atom_messages or self.n_atoms <= self.n_bonds)
+        host_key = key
+        if on_device and atom_messages and device.type == 'cuda':  # (one graph, with or without atom_blocks)
+            key = (str(device), True, bond_fdim)
+            dg = self._device_cache.get(key)
+            if dg is not None:
+                return dg
+        if src is not None and on_device:
+            # gathered on the device from the resident table, or None
+            dg = src.device_graph(self, device, True) if atom_messages else src.device_graph(self, device)
             if dg is not None:
                 self._device_cache[key] = dg
                 return dg
-        if self._compact is not None and not atom_messages and device.type == 'cuda' and \
-                (bond_fdim is None or bond_fdim == self._compact_dims[1]):
-            dg = self._device_graph_compact(device)
+        if on_device and device.type == 'cuda' and self._compact is not None:
+            dg = self._device_graph_compact(device, atom_messages)
             if dg is not None:
                 self._device_cache[key] = dg
                 return dg
+        key = host_key  # (a molecule larger than a block: the host path, cached per atom_blocks as before)
         fa = self._np['f_atoms']
         tail = self._np.get('bond_tail')
         dev_bonds = tail is not None and device.type == 'cuda'  # rebuild f_bonds on the device
@@ -718,29 +734,30 @@ class BatchMolGraph:
 
 
 def upload_compact(device, staged: torch.Tensor, info, atom_fdim: int, bond_fdim: int,
-                   lean: bool = False, extra_dims=()) -> DeviceGraph:
+                   lean: bool = False, extra_dims=(), max_num_bonds: int = None) -> DeviceGraph:
     """H2D of a staged compact image (pinned host tensor from ``compact_stage`` / ``generate_stage``)
     on the current stream, then ``wdmpnn_build_graph`` into one device buffer: the DeviceGraph of the
     batch.  ``info`` = (copied, counts, offsets, total) as the native stage functions return it.
     ``lean``: an inference-only graph (WDMPNN_GRAPH_LEAN: no dense feature rows, planes or transposed
     gathers); a training forward or an unblocked path on it raises NotImplementedError.
     ``extra_dims`` = (da, db) of a batch with extra features: ``info`` then carries the offsets of its two
-    dense sections as a fifth element."""
+    dense sections as a fifth element.  ``max_num_bonds``: build the atom-message graph (``build_from_image``)."""
     _, (_, _, _, n_blocks, _, _), off, total = info[:4]
     buf = staged[:total].to(device, non_blocking=True)
     blk_max = None
     if n_blocks:  # the block plan's largest blocks, read from the staged image (WdGraph.blk_max_*)
         blk = np.frombuffer(staged.numpy(), np.int32, count=8 * n_blocks, offset=off[4]).reshape(n_blocks, 8)
         blk_max = (int(blk[:, 1].max()), int(blk[:, 3].max()))
-    return build_from_image(device, buf, info, blk_max, atom_fdim, bond_fdim, lean, extra_dims)
+    return build_from_image(device, buf, info, blk_max, atom_fdim, bond_fdim, lean, extra_dims, max_num_bonds)
 
 
 def build_from_image(device, buf: torch.Tensor, info, blk_max, atom_fdim: int, bond_fdim: int,
-                     lean: bool = False, extra_dims=()) -> DeviceGraph:
+                     lean: bool = False, extra_dims=(), max_num_bonds: int = None) -> DeviceGraph:
     """``wdmpnn_build_graph_ex`` on the current stream from a compact image already on the device (``buf``, laid
     out as ``info`` says; ``upload_compact`` copies one there, ``graph_table`` gathers one): the DeviceGraph of the
     batch, which keeps the image alive.  ``blk_max``: (largest block's bond rows, atom rows) of the plan, or None
-    without blocks."""
+    without blocks.  ``max_num_bonds`` (the batch's largest atom degree, >= 1): the atom-message graph of the same
+    image instead (``wdmpnn_build_graph_atom``; f_bonds holds the bond's own columns, bond_fdim - atom_fdim wide)."""
     _, (n_mols, n_atoms, n_bonds, n_blocks, nnz_msg, nnz_agg), off, total = info[:4]
     base = buf.data_ptr()
     c = _native.WdCompact()
@@ -752,12 +769,22 @@ def build_from_image(device, buf: torch.Tensor, info, blk_max, atom_fdim: int, b
         c.atom_extra, c.bond_extra = (base + o for o in info[4])
     L = _native.lib()
     nbytes = ctypes.c_size_t()
-    _native.check(L.wdmpnn_graph_bytes(ctypes.byref(c), ctypes.byref(nbytes)), 'graph bytes')
-    gbuf = torch.empty(nbytes.value, dtype=torch.uint8, device=device)
     s = _native.WdGraph()
-    _native.check(L.wdmpnn_build_graph_ex(ctypes.byref(c), gbuf.data_ptr(), nbytes.value, ctypes.byref(s),
-                                          _native.GRAPH_LEAN if lean else 0, _native.current_stream(device)),
-                  'device graph build')
+    if max_num_bonds is not None:
+        if lean:
+            raise ValueError('an atom-message graph has no lean form')
+        _native.check(L.wdmpnn_graph_bytes_atom(ctypes.byref(c), ctypes.byref(nbytes)), 'graph bytes')
+        gbuf = torch.empty(nbytes.value, dtype=torch.uint8, device=device)
+        _native.check(L.wdmpnn_build_graph_atom(ctypes.byref(c), gbuf.data_ptr(), nbytes.value, ctypes.byref(s),
+                                                int(max_num_bonds), _native.current_stream(device)),
+                      'device graph build (atom messages)')
+        nnz_msg = (n_bonds - 1) + n_atoms  # one entry per bond and one pad entry per atom row
+    else:
+        _native.check(L.wdmpnn_graph_bytes(ctypes.byref(c), ctypes.byref(nbytes)), 'graph bytes')
+        gbuf = torch.empty(nbytes.value, dtype=torch.uint8, device=device)
+        _native.check(L.wdmpnn_build_graph_ex(ctypes.byref(c), gbuf.data_ptr(), nbytes.value, ctypes.byref(s),
+                                              _native.GRAPH_LEAN if lean else 0, _native.current_stream(device)),
+                      'device graph build')
     if blk_max is not None:
         s.blk_max_bonds, s.blk_max_atoms = blk_max
     dg = DeviceGraph(gbuf, {'compact': buf}, s)

@@ -54,7 +54,7 @@ class GraphTable:
         self.n_rows = len(graphs)
         self.block_target = BLK_TARGET if block_target is None else int(block_target)
         self.device = _device(device)
-        sizes, xn, atoms, pairs = [], [], [], []
+        sizes, xn, atoms, pairs, max_deg = [], [], [], [], []
         self.dims = None
         for c0 in range(0, len(mols), _CHUNK):
             chunk = mols[c0:c0 + _CHUNK]
@@ -86,12 +86,15 @@ class GraphTable:
             if ent is None:
                 raise ValueError(f'GraphTable: molecules {c0} .. {c0 + len(chunk)}: a bond leaves its molecule')
             sizes.append(np.concatenate([m[:, [1, 3]], np.frombuffer(ent, np.int32).reshape(-1, 2)], axis=1))
+            max_deg.append([int(b._deg[s:s + n].max()) if n else 0 for s, n in b.a_scope])
             xn.append(np.frombuffer(b._compact[1], np.float32))
             atoms.append(np.frombuffer(b._compact[2], np.uint8).reshape(-1, 16)[1:])  # (without the pad row)
             pairs.append(np.frombuffer(b._compact[3], np.uint8).reshape(-1, 16))
         # host side: what a plan and a lazy decode need
         self.sizes = np.ascontiguousarray(np.concatenate(sizes), np.int32)  # [M][4] n_atoms, n_bonds, nnz_msg, nnz_agg
         self.xn = np.ascontiguousarray(np.concatenate(xn), np.float32)
+        # [M] largest atom degree: a batch's max_num_bonds (the atom-message graph's pad slots) without a decode
+        self.max_deg = np.concatenate([np.asarray(d, np.int32) for d in max_deg])
         self.atoms = np.concatenate(atoms)
         self.pairs = np.concatenate(pairs)
         first = np.zeros((len(mols), 2), np.int64)
@@ -199,7 +202,7 @@ class GraphRows:
 
 class _TableSource:
     """What makes a ``BatchMolGraph`` a batch of a :class:`GraphTable` (its ``_source``): scopes and sizes come from
-    the host plan, ``device_graph`` (bond messages, on the table's GPU) gathers the compact image on the device,
+    the host plan, ``device_graph`` (on the table's GPU) gathers the compact image on the device,
     and the reference's tables are decoded, from the table's host copy of the codes, only if a host attribute is
     read."""
 
@@ -227,6 +230,7 @@ class _TableSource:
         g.a_scope = list(zip(a0.tolist(), sz[:, 0].tolist()))
         g.b_scope = list(zip(b0.tolist(), sz[:, 1].tolist()))
         g.degree_of_polym = t.xn[self.mol_ids].astype(np.float64).tolist()
+        g.max_num_bonds = max(1, int(t.max_deg[self.mol_ids].max()))  # featurization.py:802-803
         g._a2b = None
         g._gathers = None
         g.b2b = None
@@ -249,11 +253,12 @@ class _TableSource:
         return (bytearray(mols.tobytes()), bytearray(t.xn[self.mol_ids].tobytes()),
                 bytearray(np.concatenate(atoms).tobytes()), bytearray(np.concatenate(pairs).tobytes()))
 
-    def device_graph(self, g: BatchMolGraph, device):
+    def device_graph(self, g: BatchMolGraph, device, atom_messages: bool = False):
         """The batch's DeviceGraph on the table's GPU: plan -> small pinned image -> H2D -> gather ->
-        ``wdmpnn_build_graph_ex``; None on any other device (the batch then takes the paths of a ``from_compact``
-        batch, from its host arrays).  Atom-message encoders do not use compact graphs and never get here: they
-        take the existing dense path from the lazily decoded tables."""
+        ``wdmpnn_build_graph_ex``, or for an atom-message encoder ``wdmpnn_build_graph_atom`` (the same image; its
+        offsets follow from the block table, and the pad slots' count from the table's per-molecule degrees);
+        None on any other device (the batch then takes the paths of a ``from_compact`` batch, from its host
+        arrays)."""
         t = self.rows.table
         device = _device(device)
         if device.type != 'cuda' or device != t.device:
@@ -287,7 +292,8 @@ class _TableSource:
         c.t_first, c.ids = t._d_first.data_ptr(), self.rows._idx.data_ptr()
         c.mols, c.xn, c.atoms, c.pairs = base + off[0], base + off[1], base + off[2], base + off[3]
         _native.check(_native.lib().wdmpnn_gather_compact(ctypes.byref(c), stream.cuda_stream), 'gather compact')
-        dg = build_from_image(device, buf, (True, counts, off, total), blk_max, *g._compact_dims)
+        dg = build_from_image(device, buf, (True, counts, off, total), blk_max, *g._compact_dims,
+                              max_num_bonds=g.max_num_bonds if atom_messages else None)
         dg.h2d_bytes = 16 * B + (off[5] - off[4]) + 8 * n_blocks
         dg.gathered = True
         return dg

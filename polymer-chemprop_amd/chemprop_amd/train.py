@@ -923,12 +923,14 @@ def _descriptors_ok(mpn, enc, atom_descriptors_batch) -> bool:
     """The descriptor side of a direct step: a model without ``atom_descriptors_layer`` gets none; a model with
     it gets rows of a device table (``atom_descriptors.AtomDescriptorRows``) and has no encoder dropout, so that the
     layer runs after the readout (``MPNEncoder._after_readout``).  A list of numpy arrays and active dropout keep
-    the autograd path."""
+    the autograd path, and so does an atom-message encoder with descriptors: the layer after the readout joins
+    the bond-message encoder's atom states (a model without descriptors takes the direct step in either mode)."""
     has = hasattr(enc, 'atom_descriptors_layer')
     if not mpn.atom_descriptors and not has:
         return atom_descriptors_batch is None
     from .atom_descriptors import is_device_descriptors
-    return mpn.atom_descriptors == 'descriptor' and has and is_device_descriptors(atom_descriptors_batch) and \
+    return mpn.atom_descriptors == 'descriptor' and has and not enc.atom_messages and \
+        is_device_descriptors(atom_descriptors_batch) and \
         atom_descriptors_batch.device.type == 'cuda' and enc.dropout == 0 and enc._after_readout()
 
 
@@ -946,8 +948,7 @@ def _direct_encoder(model: nn.Module, mol_batch, features_batch, head, atom_desc
             len(mpn.encoder) != 1 or not isinstance(mol_batch, (list, tuple)) or len(mol_batch) != 1:
         return None
     enc = mpn.encoder[0]
-    if type(enc) is not MPNEncoder or enc.depth < 2 or enc.atom_messages or \
-            not _descriptors_ok(mpn, enc, atom_descriptors_batch):
+    if type(enc) is not MPNEncoder or enc.depth < 2 or not _descriptors_ok(mpn, enc, atom_descriptors_batch):
         return None
     if type(mol_batch[0]).__name__ != 'BatchMolGraph':
         return None
@@ -1025,7 +1026,7 @@ def _frozen_plan(model: nn.Module, mol_batch, features_batch, head, cached: bool
                        type(mol_batch[0]).__name__ != 'BatchMolGraph'):
         return None
     enc = mpn.encoder[0]
-    if type(enc) is not MPNEncoder or enc.depth < 2 or enc.atom_messages or hasattr(enc, 'atom_descriptors_layer'):
+    if type(enc) is not MPNEncoder or enc.depth < 2 or hasattr(enc, 'atom_descriptors_layer'):
         return None
     st = head
     if not isinstance(head, _StackHead):
@@ -1307,7 +1308,7 @@ def train_step(model: nn.Module, mol_batch, target_batch, loss_func: Callable, o
     device-resident ``atom_descriptors.AtomDescriptorTable`` take the direct step when the encoder has no dropout
     (the descriptor layer runs after the readout: encoder forward, join, layer, features join if any, head,
     layer backward, encoder backward).  A list of numpy arrays as in the reference, active dropout, atom
-    messages, depth 1 and partly frozen models take the autograd path.
+    messages together with descriptors, depth 1 and partly frozen models take the autograd path.
 
     A model of several molecules per input (``number_of_molecules > 1``; ``mol_batch`` is the list of one
     ``BatchMolGraph`` per molecule, or a ``slots.SlotBatch``) takes the direct step as well (``_direct_slots``,

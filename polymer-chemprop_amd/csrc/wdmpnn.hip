@@ -858,6 +858,52 @@ int graph_layout(const WdCompact *c, GraphLayout &L) {
     return 0;
 }
 
+// the atom-message graph of a compact batch (graph_build.hpp graph_build_atom_kernel): every entry count is a
+// function of the atom and bond counts alone (c->nnz_msg, c->nnz_agg and c->block_nnz are not read)
+struct AtomGraphLayout {
+    int lda = 0, ldb = 0, Vap = 0, Rbp = 0;
+    size_t f_atoms = 0, f_bonds = 0, fa_x6 = 0, fb_x6 = 0, fa_blk_x6 = 0, fs_x6 = 0, w_atoms = 0, mol_start = 0,
+           mol_size = 0, xn = 0, b2revb = 0, blocks = 0, bond_blk_row = 0, atom_blk_row = 0, msg_ell_idx = 0,
+           msg_ell_coef = 0, agg_ell_idx = 0, agg_ell_coef = 0, csr[5][3] = {}, total = 0;
+};
+
+int atom_graph_layout(const WdCompact *c, AtomGraphLayout &L) {
+    GraphLayout bond_mode;
+    WD_TRY(graph_layout(c, bond_mode));  // (the same image: the same checks of its counts and widths)
+    L.lda = rup(c->atom_fdim, 32); L.ldb = rup(std::max(c->bond_fdim - c->atom_fdim, 1), 32);
+    L.Vap = rup(c->n_atoms, 128); L.Rbp = rup(c->n_bonds, 128);
+    size_t off = 0;
+    auto take = [&](size_t bytes) { size_t o = off; off = align256(off + bytes); return o; };
+    L.f_atoms = take((size_t)L.Vap * L.lda * 4);
+    L.f_bonds = take((size_t)L.Rbp * L.ldb * 4);
+    L.fa_x6 = take((size_t)L.Vap * L.lda * 6);
+    L.fb_x6 = take((size_t)L.Rbp * L.ldb * 6);
+    L.fa_blk_x6 = take((size_t)std::max(c->n_blocks, 1) * BLK_ATOMS * L.lda * 6);
+    L.fs_x6 = take((size_t)L.Vap * L.ldb * 6);
+    L.w_atoms = take((size_t)c->n_atoms * 4);
+    L.mol_start = take((size_t)c->n_mols * 4 + 4);
+    L.mol_size = take((size_t)c->n_mols * 4 + 4);
+    L.xn = take((size_t)c->n_mols * 4 + 4);
+    L.b2revb = take((size_t)c->n_bonds * 4);
+    L.blocks = take((size_t)c->n_blocks * 32 + 32);
+    L.bond_blk_row = take((size_t)L.Rbp * 4);
+    L.atom_blk_row = take((size_t)L.Vap * 4);
+    L.msg_ell_idx = take((size_t)L.Vap * GB_ELLW);
+    L.msg_ell_coef = take((size_t)L.Vap * GB_ELLW * 4);
+    L.agg_ell_idx = take((size_t)L.Vap * GB_ELLW);
+    L.agg_ell_coef = take((size_t)L.Vap * GB_ELLW * 4);
+    // feat, msg, agg, msg_t, agg_t: {ptr, idx, coef}; rows = atoms; one entry per bond, msg / msg_t + one per atom
+    const size_t E = (size_t)c->n_bonds - 1, V1 = (size_t)c->n_atoms;
+    const size_t nnz[5] = {E, E + V1, E, E + V1, E};
+    for (int q = 0; q < 5; ++q) {
+        L.csr[q][0] = take((V1 + 1) * 4);
+        L.csr[q][1] = take((nnz[q] + GB_CSR_PAD) * 4);
+        L.csr[q][2] = take((nnz[q] + GB_CSR_PAD) * 4);
+    }
+    L.total = off;
+    return 0;
+}
+
 // ------------------------------------------------------------------------------------------------
 // molecule-blocked fused forward (fused_mp.hpp): embed (or the W_i GEMM) -> (T-1) x mp_layer ->
 // wo_readout, for up to WD_MULTI independent batches per launch (wdmpnn_forward_many; one batch for
@@ -2271,6 +2317,72 @@ int wdmpnn_build_graph_ex(const WdCompact *c, void *buffer, size_t bytes, WdGrap
     hipLaunchKernelGGL(graph_build_kernel, dim3(c->n_blocks + 1, M.p[0].lean ? 1 : GB_SLICES), dim3(256), 0,
                        (hipStream_t)stream, M);
     WD_CHECK_LAUNCH("graph_build");
+    return 0;
+}
+
+int wdmpnn_graph_bytes_atom(const WdCompact *c, size_t *bytes) {
+    AtomGraphLayout L;
+    WD_TRY(atom_graph_layout(c, L));
+    if (!bytes) return fail(WD_ERR_ARG, "null bytes");
+    *bytes = L.total;
+    return 0;
+}
+
+int wdmpnn_build_graph_atom(const WdCompact *c, void *buffer, size_t bytes, WdGraph *g, int32_t max_num_bonds,
+                            void *stream) {
+    if (!g) return fail(WD_ERR_ARG, "null graph");
+    AtomGraphLayout L;
+    WD_TRY(atom_graph_layout(c, L));
+    if (max_num_bonds < 1) return fail(WD_ERR_ARG, "max_num_bonds must be >= 1 (got %d)", max_num_bonds);
+    if (!buffer) return fail(WD_ERR_ARG, "null buffer");
+    if (bytes < L.total) return fail(WD_ERR_WORKSPACE, "graph buffer too small: need %zu bytes, got %zu", L.total, bytes);
+    if ((uintptr_t)buffer % 256) return fail(WD_ERR_ARG, "graph buffer must be 256-byte aligned");
+    if (c->n_mols && (!c->mols || !c->xn)) return fail(WD_ERR_ARG, "null molecule arrays");
+    if (!c->atoms || (c->n_bonds > 1 && !c->pairs) || (c->n_blocks && !c->blocks))
+        return fail(WD_ERR_ARG, "null compact arrays");
+    if ((c->atom_extra_dim && !c->atom_extra) || (c->bond_extra_dim && c->n_bonds > 1 && !c->bond_extra))
+        return fail(WD_ERR_ARG, "null extra feature arrays");
+    WD_KERNELS_OK();
+    char *base = (char *)buffer;
+    auto F = [&](size_t o) { return (float *)(base + o); };
+    auto I = [&](size_t o) { return (int32_t *)(base + o); };
+    auto U = [&](size_t o) { return (uint8_t *)(base + o); };
+    GraphBuildAtomP P{};
+    P.c = *c;
+    P.Fa = c->atom_fdim; P.Fb = c->bond_fdim - c->atom_fdim; P.lda = L.lda; P.ldb = L.ldb; P.Vap = L.Vap; P.Rbp = L.Rbp;
+    P.max_nb = max_num_bonds;
+    P.f_atoms = F(L.f_atoms); P.f_bonds = F(L.f_bonds);
+    P.fa_x6 = U(L.fa_x6); P.fb_x6 = U(L.fb_x6); P.fa_blk_x6 = U(L.fa_blk_x6); P.fs_x6 = U(L.fs_x6);
+    P.w_atoms = F(L.w_atoms); P.xn = F(L.xn); P.mol_start = I(L.mol_start); P.mol_size = I(L.mol_size);
+    P.b2revb = I(L.b2revb); P.blocks = I(L.blocks); P.bond_blk_row = I(L.bond_blk_row);
+    P.atom_blk_row = I(L.atom_blk_row);
+    P.msg_ell_idx = U(L.msg_ell_idx); P.msg_ell_coef = F(L.msg_ell_coef);
+    P.agg_ell_idx = U(L.agg_ell_idx); P.agg_ell_coef = F(L.agg_ell_coef);
+    P.feat_ptr = I(L.csr[0][0]); P.feat_idx = I(L.csr[0][1]); P.feat_coef = F(L.csr[0][2]);
+    P.msg_ptr = I(L.csr[1][0]); P.msg_idx = I(L.csr[1][1]); P.msg_coef = F(L.csr[1][2]);
+    P.agg_ptr = I(L.csr[2][0]); P.agg_idx = I(L.csr[2][1]); P.agg_coef = F(L.csr[2][2]);
+    P.msgt_ptr = I(L.csr[3][0]); P.msgt_idx = I(L.csr[3][1]); P.msgt_coef = F(L.csr[3][2]);
+    P.aggt_ptr = I(L.csr[4][0]); P.aggt_idx = I(L.csr[4][1]); P.aggt_coef = F(L.csr[4][2]);
+    WdGraph G{};
+    G.n_atoms = c->n_atoms; G.n_bonds = c->n_bonds; G.n_mols = c->n_mols;
+    G.atom_fdim = P.Fa; G.bond_fdim = P.Fb; G.ld_atoms = L.lda; G.ld_bonds = L.ldb; G.bond_col0 = 0;
+    G.f_atoms = P.f_atoms; G.f_bonds = P.f_bonds; G.w_atoms = P.w_atoms;
+    G.mol_start = P.mol_start; G.mol_size = P.mol_size; G.degree_of_polym = P.xn;
+    G.msg_gather = WdCsr{P.msg_ptr, P.msg_idx, P.msg_coef};
+    G.bond_feat_gather = WdCsr{P.feat_ptr, P.feat_idx, P.feat_coef};
+    G.atom_gather = WdCsr{P.agg_ptr, P.agg_idx, P.agg_coef};
+    G.msg_gather_t = WdCsr{P.msgt_ptr, P.msgt_idx, P.msgt_coef};
+    G.atom_gather_t = WdCsr{P.aggt_ptr, P.aggt_idx, P.aggt_coef};
+    G.b2revb = P.b2revb;
+    G.atom_messages = 1;
+    G.f_atoms_x6 = P.fa_x6; G.f_bonds_x6 = P.fb_x6; G.atom_feat_sum_x6 = P.fs_x6;
+    G.n_blocks = c->n_blocks; G.blocks = P.blocks; G.bond_blk_row = P.bond_blk_row; G.f_atoms_blk_x6 = P.fa_blk_x6;
+    G.msg_ell_idx = P.msg_ell_idx; G.msg_ell_coef = P.msg_ell_coef;
+    G.atom_ell_idx = P.agg_ell_idx; G.atom_ell_coef = P.agg_ell_coef;
+    // (no codes, bond maps or extras: the atom-message kernels read the dense rows, which hold the extras)
+    hipLaunchKernelGGL(graph_build_atom_kernel, dim3(c->n_blocks + 1, GB_SLICES), dim3(256), 0, (hipStream_t)stream, P);
+    WD_CHECK_LAUNCH("graph_build_atom");
+    *g = G;
     return 0;
 }
 
